@@ -14,10 +14,18 @@ timed region; games shard across ranks with no collective on the data path (weak
 
 Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the step launch `k_step` -- search wave, network tower
 and value-FC tile of every game in one launch, 96 % of GPU time -- timed with HIP events around sampled launches on the
-launch stream and priced with the FULL forward's FLOP against the dense MFMA peak) and, at N=1, `cpu_baseline` (the CPU
-oracle = port of the reference algorithm, timed on the host cores on a bounded sample).  `also_tower` keeps the tower-only
-figure (separate launches), `phases_us` the split of a step launch, `also_encode_steps` / `also_match` the widened rows
-(SURVEY.md 8f rank 1 and 2).  Exits non-zero when the engine reports error flags.
+launch stream and priced with the FULL forward's FLOP against the dense MFMA peak).  Exits non-zero when the engine
+reports error flags.
+
+A plain run sets up, warms up for W plies, times exactly K plies in one region and prints the line.  `--full` adds what
+takes work of its own: three timed regions of K plies (the median one is reported), at N=1 `cpu_baseline` (the CPU
+oracle = port of the reference algorithm, timed on the host cores on a bounded sample), `also_tower` (the tower-only
+figure, separate launches), `phases_us` (the split of a step launch), the short extra configurations (`also`,
+`also_steady`, `also_fp8`, ...) and `also_encode_steps` / `also_match` (the widened rows).
+
+`--dump-outputs DIR` writes, after the timed plies and before anything else runs on the handle, what the self-play
+handle hands its caller about every game after the last timed ply (slot state, the move just played, the last
+descent's path, the counters) as float64 .npy files; the inputs are seeded, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -201,7 +209,10 @@ def run_gpu(args, rank, world, local_rank):
                         sims_all=s1["sims_done"] - nn0["sims_done"], err=s1["error_flags"],
                         step_ms=sum(t["ms_tower_sum"] for t in tms) / max(nl, 1), steps_timed=nl,
                         span_ms=max(t["ms_total"] for t in tms), groups=K, games=G, launches_per_step=sps[0].launches_per_step())
-        if tag == "main" and K == 1:
+        if tag == "main" and args.dump_outputs:
+            progress("dump outputs")
+            dump_outputs(args.dump_outputs, sps, s1, rank, world)
+        if tag == "main" and K == 1 and args.full:
             progress("phase stamps")
             res[tag]["phases_us"] = step_phases(sps[0], R)
             progress("tower-only sample")
@@ -216,7 +227,7 @@ def run_gpu(args, rank, world, local_rank):
         if tag == "steady":
             plies = [sps[0].slot(g)["ply"] for g in range(0, G, 8)]
             res[tag]["ply_min_max"] = (min(plies), max(plies))
-        if tag in ("main", "sharp", "steady"):   # tree levels walked by the last descent of a sample of games
+        if tag in ("main", "sharp", "steady") and args.full:   # tree levels walked by the last descent of a sample of games
             lens = [len(sps[0].slot(g)["path"]) for g in range(0, G, 4)]
             res[tag]["mean_path_len"] = sum(lens) / len(lens)
         if tag == "main" and args.alt and world == 1:
@@ -229,6 +240,35 @@ def run_gpu(args, rank, world, local_rank):
         progress("match")
         res["match"] = match_rate(scamd, args.blocks, args.channels, local_rank)
     return res
+
+
+def dump_outputs(out_dir, sps, st, rank, world):
+    """--dump-outputs: what the self-play handle(s) report after the last timed ply, one row per slot (its current game), as
+    float64 arrays (every value is an integer below 2**53).  The timed loop ended with a synchronise, which completes the ply:
+    the move was chosen and the tree reset to the new root, whose move field holds the move just played.  last_path is the
+    node path of the ply's last descent, padded with -1.  stats: sims_done, nn_evals, games_finished, games_active, plies_done,
+    error_flags of the whole run.  Rows are in game-id order: when several games end in the same launch, which slot starts
+    which next game id depends on the order the slots claim them, while each game's play depends only on its id."""
+    import numpy as np
+    slots = [sp.slot(g) for sp in sps for g in range(sp.cfg.n_slots)]
+    roots = [sp.tree(g, cap=1)["move"] for sp in sps for g in range(sp.cfg.n_slots)]
+    moves = [int(m[0]) if len(m) else -1 for m in roots]
+    order = sorted(range(len(slots)), key=lambda i: slots[i]["game_id"])
+    slots, moves = [slots[i] for i in order], [moves[i] for i in order]
+    width = max([len(s["path"]) for s in slots] + [1])
+    path = np.full((len(slots), width), -1.0)
+    for i, s in enumerate(slots):
+        path[i, :len(s["path"])] = s["path"]
+    arrays = {"last_move": np.array(moves, np.float64), "last_path": path,
+              "last_path_len": np.array([len(s["path"]) for s in slots], np.float64),
+              "stats": np.array([st[k] for k in ("sims_done", "nn_evals", "games_finished", "games_active", "plies_done", "error_flags")],
+                                np.float64)}
+    for k in ("ply", "sim", "status", "game_id"):
+        arrays[k] = np.array([s[k] for s in slots], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f".rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def step_phases(sp, R):
@@ -351,12 +391,11 @@ def barrier():
 
 
 def cuda_sync():
-    try:
-        import torch
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-    except Exception:
-        pass
+    """device-wide synchronise where torch is loaded (under a launcher); a single process has only the handles' own streams,
+    which their sync() has already drained"""
+    torch = sys.modules.get("torch")
+    if torch is not None and torch.cuda.is_available():
+        torch.cuda.synchronize()
 
 
 def main():
@@ -365,22 +404,36 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps plies each; the median one is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes work of its own: 3 timed regions (median reported), CPU baseline, phase stamps, "
+                         "tower-only sample, extra configurations, encode_steps and match rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the self-play state after the last timed ply as DIR/<name>.npy (float64)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps plies each; the median one is reported (default 1, with --full 3)")
     ap.add_argument("--games", type=int, default=256, help="concurrent games per GPU")
     ap.add_argument("--rollout", type=int, default=180)
     ap.add_argument("--blocks", type=int, default=10)
     ap.add_argument("--channels", type=int, default=128, help="trunk width: 128 = BASELINE configs[1]; 256 = reference module")
-    ap.add_argument("--no-alt", dest="alt", action="store_false", help="skip the short extra runs (steady state, other width, 2x games, fp8)")
+    ap.add_argument("--no-alt", dest="alt", action="store_false",
+                    help="with --full: skip the short extra runs (steady state, other width, 2x games, fp8, encode_steps, match)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp8"], help="network precision of the main run (BASELINE configs[1]: bf16)")
     ap.add_argument("--groups", type=int, default=1, help="split the games of a GPU into K groups on K HIP streams (overlap)")
     ap.add_argument("--timing-stride", type=int, default=8,
                     help="every n-th simulation step's launch(es) are bracketed by a HIP event pair on the launch stream for the roofline "
                          "figure (the launch form is not changed)")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU work for cpu_baseline (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="with --full: seconds of CPU work for cpu_baseline (0 = skip)")
     ap.add_argument("--cpu-dry-run", action="store_true",
                     help="HARNESS TEST ONLY (gloo, no GPU): exercises sharding/timing/aggregation with the oracle's "
                          "synthetic self-play as stand-in workload; its numbers are meaningless")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if not args.full:
+        args.alt = False
+        args.cpu_budget = 0.0
+    if args.dump_outputs and args.cpu_dry_run:
+        ap.error("--dump-outputs needs the GPU path, not --cpu-dry-run")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -401,13 +454,8 @@ def main():
     # under a launcher (torch.distributed.run sets RANK / MASTER_ADDR) the process group is used even with one rank, so the
     # RCCL path -- rendezvous, barrier, all-reduce of the timing scalars on device tensors -- is the same code at every N
     use_dist = world > 1 or ("RANK" in os.environ and "MASTER_ADDR" in os.environ)
-    torch = None
-    try:
-        import torch  # plumbing only: rendezvous, barrier, max-over-ranks
-    except Exception:
-        if use_dist:
-            raise
     if use_dist:
+        import torch  # plumbing only: rendezvous, barrier, max-over-ranks
         import torch.distributed as dist
         backend = "gloo" if args.cpu_dry_run else "nccl"
         if backend == "nccl":

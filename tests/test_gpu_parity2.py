@@ -527,10 +527,35 @@ def test_bench_runs_under_the_launcher_with_rccl(tmp_path):
         port = so.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1",
-                        "--no-alt", "--cpu-budget", "0"], capture_output=True, text=True, timeout=900)
+                        "--no-alt", "--cpu-budget", "0", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 1e5 and line["error_flags"] == 0 and line["roofline"]["frac"] > 0.1
+    assert line["steps"] == 2 and line["repeats"]["regions"] == 1
+    # --dump-outputs: the 256 games after warm-up + 2 timed plies of 180 simulations each, none of them finished
+    out = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert (out["ply"] == 3).all() and (out["sim"] == 0).all() and (out["game_id"] == np.arange(256)).all()
+    assert (out["last_move"] > 0).all() and (out["last_path_len"] > 0).all() and out["last_path"].shape[0] == 256
+    assert list(out["stats"]) == [3 * 180 * 256, out["stats"][1], 0, 256, 3 * 256, 0]
+
+
+def test_bench_dump_outputs_repeat(tmp_path):
+    """two plain `bench.py --dump-outputs` processes with the same arguments write identical files, including games that
+    ended and were replaced during the run (the rows are in game-id order, not slot order)"""
+    import subprocess
+    import sys
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs.append({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))})
+    assert sorted(outs[0]) == ["game_id", "last_move", "last_path", "last_path_len", "ply", "sim", "stats", "status"]
+    assert outs[0]["stats"][2] > 0 and outs[0]["stats"][5] == 0     # some games finished; no error flags
+    for f, a in outs[0].items():
+        assert a.shape == outs[1][f].shape and (a == outs[1][f]).all(), f
 
 
 @pytest.mark.parametrize("C,precision,n_slots", [(128, "bf16", 24), (256, "bf16", 24), (128, "fp8", 24),

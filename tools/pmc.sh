@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-pmc}; CH=${2:-256}
 OUT=$R/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 1 --warmup 1 --no-alt --cpu-budget 0 --channels $CH"
+ARGS="--steps 1 --warmup 1 --full --no-alt --cpu-budget 0 --channels $CH"
 rocprofv3 -L > $OUT/counters.txt 2>&1 || true
 i=0
 for SET in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
