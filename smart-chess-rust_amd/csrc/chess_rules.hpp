@@ -326,8 +326,9 @@ SC_HD void make_move(Position& p, move_t m) {
 // The board half of make_move alone: pieces, occupancy, castling rights, ep square, clocks, side to move.  key and flags are left
 // zero: the training-tensor encoder walks a game with this (one wave per game, a chain of dependent steps) and computes the keys,
 // the irreversibility flag and the repetition flags of all plies in parallel afterwards (mcts_kernels.hpp: k_replay_raw,
-// k_ply_keys, k_ply_rep).  Must stay in step with make_move above (tests/test_gpu_parity.py::test_encode_steps_* compare the result
-// with the oracle).
+// k_ply_keys, k_ply_rep).  Must stay in step with make_move above: tests/test_engine_rules_host.py::test_make_move_board_matches_make_move
+// compares the two field by field on every legal move of ~10^5 positions, and tests/test_gpu_parity.py::test_encode_steps_* and
+// tests/test_gpu_rules.py::test_encode_steps_on_edge_lines compare the encoder's result with the oracle.
 SC_HD void make_move_board(Position& p, move_t m) {
     int from = mv_from(m), to = mv_to(m), promo = mv_promo(m);
     int us = p.turn, them = !us;

@@ -6,8 +6,10 @@
 // moves per lane is turned into output positions by ONE packed suffix scan (lanes in descending order = python-chess's
 // from-square order), and every lane writes its own moves.  The result -- the list AND its order -- is identical to
 // gen_legal (python-chess generate_legal_moves: non-pawn pieces by from-square descending / to-square descending,
-// castling, pawn captures, single pushes, double pushes, en passant; evasions: king steps first); the parity tests
-// compare both against the oracle on ~10^5 positions.
+// castling, pawn captures, single pushes, double pushes, en passant; evasions: king steps first).  Tests against the
+// oracle: tests/test_gpu_rules.py (every position 3 and 4 plies from the start, every ply of the edge-case corpus
+// tests/golden/edge_lines.json and two plies below its final positions, games that play special moves whenever they can)
+// and tests/test_gpu_parity.py::test_encode_positions_bit_exact; gen_legal itself: tests/test_engine_rules_host.py.
 #pragma once
 #include <hip/hip_runtime.h>
 

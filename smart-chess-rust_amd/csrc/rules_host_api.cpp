@@ -142,6 +142,30 @@ uint64_t sct_pos_hash(const sct_state* s) { return synth_pos_hash(s->hist.back()
 uint64_t sct_key(const sct_state* s) { return s->hist.back().key; }
 uint64_t sct_key_full(const sct_state* s) { return position_key(s->hist.back()); }
 uint64_t sct_rng(uint64_t a, uint64_t b, uint64_t c, uint64_t d, uint64_t e) { return sc_rng(a, b, c, d, e); }
+// make_move_board against make_move, for every legal move of the current position, each applied to its own copy: returns the OR
+// over the moves of the fields that disagree (bit 0 pcs, 1 occ, 2 castling, 3 ep, 4 halfmove, 5 fullmove, 6 turn); *n_moves: how
+// many moves were compared
+int sct_board_diff_legal(const sct_state* s, int* n_moves) {
+    move_t buf[MAX_MOVES];
+    MoveList l{buf, 0};
+    const Position& p = s->hist.back();
+    gen_legal(p, l);
+    int diff = 0;
+    for (int i = 0; i < l.n; i++) {
+        Position a = p, b = p;
+        make_move(a, l.m[i]);
+        make_move_board(b, l.m[i]);
+        if (memcmp(a.pcs, b.pcs, sizeof a.pcs)) diff |= 1;
+        if (memcmp(a.occ, b.occ, sizeof a.occ)) diff |= 2;
+        if (a.castling != b.castling) diff |= 4;
+        if (a.ep != b.ep) diff |= 8;
+        if (a.halfmove != b.halfmove) diff |= 16;
+        if (a.fullmove != b.fullmove) diff |= 32;
+        if (a.turn != b.turn) diff |= 64;
+    }
+    if (n_moves) *n_moves = l.n;
+    return diff;
+}
 void sct_synth_eval(const sct_state* s, float* priors, float* value) {
     move_t buf[MAX_MOVES];
     MoveList l{buf, 0};

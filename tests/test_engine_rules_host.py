@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import random_games
+from helpers import load_edge_lines, random_games
 from test_oracle_rules import PERFT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,6 +46,7 @@ def H():
     L.sct_is_repetition.argtypes = [C.c_void_p, C.c_int]
     L.sct_outcome.argtypes = [C.c_void_p, C.c_void_p]
     L.sct_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sct_board_diff_legal.argtypes = [C.c_void_p, C.c_void_p]
     L.sct_synth_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
@@ -71,6 +72,39 @@ def test_perft_known_answers(H):
     H.sct_free(s)
 
 
+def _check_position(H, orc, s, o, buf, chk):
+    """every per-position check of the engine's host rules against the oracle: move order, check flag, planes, meta,
+    repetition 2/3/5, outcome(claim_draw), hashes, incremental key == full key, action indices -> (legal moves, outcome)"""
+    n = H.sct_legal_moves(s, buf, C.byref(chk))
+    mine = [buf[i] for i in range(n)]
+    assert mine == o.legal_moves(), o.fen()
+    assert bool(chk.value) == o.is_check()
+    b = np.zeros((8, 8, 112), np.int8)
+    m = np.zeros(7, np.int32)
+    H.sct_encode(s, b.ctypes.data, m.ctypes.data)
+    ob, om = o.encode()
+    assert np.array_equal(b, ob) and np.array_equal(m, om), o.fen()
+    for c in (2, 3, 5):
+        assert bool(H.sct_is_repetition(s, c)) == o.is_repetition(c)
+    oo = _check_outcome(H, orc, s, o)
+    assert H.sct_pos_hash(s) == o.pos_hash()
+    assert H.sct_key(s) == H.sct_key_full(s)      # incremental transposition key == full recompute
+    for mv in mine:
+        assert H.sct_move_index(mv, o.turn) == orc.move_index(mv, o.turn) >= 0
+    return mine, oo
+
+
+def _check_outcome(H, orc, s, o):
+    w = C.c_int(0)
+    t = H.sct_outcome(s, C.byref(w))
+    oo = o.outcome()
+    assert (t == 0) == (oo is None), (o.fen(), t, oo)
+    if oo:
+        assert orc.TERMINATION[t] == oo["termination"]
+        assert {1: "White", 0: "Black", -1: None}[w.value] == oo["winner"]
+    return oo
+
+
 def test_cross_check_against_oracle(H, orc):
     """move order, check flag, planes, meta, repetition, outcome(claim_draw), hashes, action indices
     along 120 random games (~25k positions)"""
@@ -85,29 +119,10 @@ def test_cross_check_against_oracle(H, orc):
         H.sct_reset(s)
         o = orc.State()
         for ply in range(300):
-            n = H.sct_legal_moves(s, buf, C.byref(chk))
-            mine = [buf[i] for i in range(n)]
-            assert mine == o.legal_moves(), o.fen()
-            assert bool(chk.value) == o.is_check()
-            b = np.zeros((8, 8, 112), np.int8)
-            m = np.zeros(7, np.int32)
-            H.sct_encode(s, b.ctypes.data, m.ctypes.data)
-            ob, om = o.encode()
-            assert np.array_equal(b, ob) and np.array_equal(m, om), o.fen()
-            for c in (2, 3, 5):
-                assert bool(H.sct_is_repetition(s, c)) == o.is_repetition(c)
-            w = C.c_int(0)
-            t = H.sct_outcome(s, C.byref(w))
-            oo = o.outcome()
-            assert (t == 0) == (oo is None), (o.fen(), t, oo)
+            mine, oo = _check_position(H, orc, s, o, buf, chk)
+            n = len(mine)
             if oo:
-                assert orc.TERMINATION[t] == oo["termination"]
-                assert {1: "White", 0: "Black", -1: None}[w.value] == oo["winner"]
                 seen_terms.add(oo["termination"])
-            assert H.sct_pos_hash(s) == o.pos_hash()
-            assert H.sct_key(s) == H.sct_key_full(s)      # incremental transposition key == full recompute
-            for mv in mine:
-                assert H.sct_move_index(mv, o.turn) == orc.move_index(mv, o.turn) >= 0
             n_pos += 1
             if n == 0 or (oo and oo["termination"] in ("SeventyfiveMoves", "FivefoldRepetition", "InsufficientMaterial")):
                 break
@@ -166,3 +181,64 @@ def test_synth_evaluator_and_rng_match_oracle(H, orc):
     for args in [(0, 0, 0, 1, 0), (123, 7, 33, 3, 99), (2 ** 63, 5, 1, 2, 0)]:
         assert H.sct_rng(*args) == L.orc_rng(*args)
     H.sct_free(s)
+
+
+def test_edge_lines_every_ply(H, orc):
+    """every ply of every line of the edge-case corpus (tests/golden/edge_lines.json) through all the per-position checks; the
+    positions up to two plies below each final position through the move list, check flag and outcome; perft(3) there"""
+    s = H.sct_new()
+    buf = (C.c_uint16 * 256)()
+    chk = C.c_int(0)
+    n_pos = n_sub = 0
+    for e in load_edge_lines():
+        H.sct_reset(s)
+        o = orc.State()
+        for u in e["uci"] + [None]:
+            mine, _ = _check_position(H, orc, s, o, buf, chk)
+            n_pos += 1
+            if u is None:
+                break
+            mv = orc.from_uci(u)
+            assert mv in mine, (e["name"], u)
+            H.sct_push(s, mv)
+            o.push(mv)
+        assert H.sct_perft(s, 3) == o.perft(3), e["name"]
+        if o.outcome():
+            continue
+
+        def sub(depth):
+            nonlocal n_sub
+            n = H.sct_legal_moves(s, buf, C.byref(chk))
+            mine = [buf[i] for i in range(n)]
+            assert mine == o.legal_moves(), (e["name"], o.fen())
+            assert bool(chk.value) == o.is_check()
+            _check_outcome(H, orc, s, o)
+            n_sub += 1
+            if depth:
+                for mv in mine:
+                    H.sct_push(s, mv)
+                    o.push(mv)
+                    sub(depth - 1)
+                    H.sct_pop(s)
+                    o.pop()
+        sub(2)
+    H.sct_free(s)
+    assert n_pos > 4000 and n_sub > 30000, (n_pos, n_sub)
+
+
+def test_make_move_board_matches_make_move(H, orc):
+    """make_move_board (the training-tensor encoder's board update) == make_move on pcs, occ, castling, ep, clocks and turn for
+    every legal move of every position of the edge-case corpus and of 120 random games"""
+    s = H.sct_new()
+    nm = C.c_int(0)
+    lines = [[orc.from_uci(u) for u in e["uci"]] for e in load_edge_lines()] + [g for g, _ in random_games(orc, 120, 300, seed=5)]
+    n_moves = 0
+    for moves in lines:
+        H.sct_reset(s)
+        for mv in moves + [None]:
+            assert H.sct_board_diff_legal(s, C.byref(nm)) == 0, [orc.uci(x) for x in moves]
+            n_moves += nm.value
+            if mv is not None:
+                H.sct_push(s, mv)
+    H.sct_free(s)
+    assert n_moves > 500000, n_moves

@@ -555,9 +555,9 @@ def test_single_call_search_reuses_its_handle(scamd, orc):
 
 @pytest.mark.gpu
 def test_encode_steps_very_long_game(scamd, orc):
-    """a 700-ply game of knight shuffles (every position repeats: both repetition planes set, the scan's window grows until the
-    75-move counter's irreversibility never comes) next to a short one: the game walk keeps the keys of the first 512 plies in LDS and
-    reads older... later ones from the records in global memory -- both paths against the oracle"""
+    """a 700-ply game of knight shuffles (every position repeats: both repetition planes set, and no irreversible move ever
+    bounds the scan) next to a short one, against the oracle: rep_flags_wave's repetition scan over more than 64 earlier plies,
+    and k_replay_raw's walk, which loads the game's moves 64 at a time, across many of those batches"""
     cyc = ["g1f3", "g8f6", "f3g1", "f6g8", "b1c3", "b8c6", "c3b1", "c6b8"]
     long_moves = [cyc[i % 8] for i in range(700)]
     games = []
