@@ -139,6 +139,32 @@ int sc_encode_steps(sc_engine* engine_or_null, int device_id, int n_games, const
  * kernels (game walk, keys, repetition flags, planes + moves, dist: all chunks) and wall time of the whole call including the PCIe copies */
 int sc_encode_steps_last_timing(float* kernels_ms, float* total_ms);
 
+/* Training tensors straight into DEVICE memory, for a trainer on the same GPU (no copy through the host).
+ * sc_encode_steps_device takes the host inputs of sc_encode_steps; sc_selfplay_encode_traces reads finished games from the
+ * self-play handle's trace ring in place.  Outputs (P = plies of the call), device pointers, any may be NULL except status:
+ *   layout 0 (reference): boards int8 [P][8][8][112], meta int32 [P][7] -- bit-identical to sc_encode_steps
+ *   layout 1 (trainer, py/dataset.py _prepare): boards float32 [P][112][8][8] (channel-major), meta float32 [P][7]: the same
+ *            integers, converted exactly
+ *   dist float32 [P][4672] as sc_encode_steps; legal_idx uint16 [P][SC_MAX_MOVES] and n_legal int32 [P] as sc_encode_steps
+ *   dist_legal float32 [P][SC_MAX_MOVES]: entry i = the visit share of legal move i (the same float dist holds at
+ *            legal_idx[p][i]), 0 past n_legal.  The dense row is  zeros(P, 4672).scatter_add_(1, legal_idx.long(), dist_legal)
+ *            -- scatter_add_, NOT scatter_: the padding entries point at action 0, which can be a legal move, and a plain
+ *            scatter would overwrite its share with the padding's 0.
+ *   status int32 [n_games] (device): sc_encode_steps's codes (0, 1000+i, -(i+1): the first failing ply of the game, a
+ *            children mismatch before an illegal move at the same ply), reduced on the device.
+ * Output pointers are checked (hipPointerGetAttributes): host memory or memory of another GPU than the engine's / handle's /
+ * device_id's returns -1.
+ * Stream contract: `stream` is a hipStream_t (NULL: the default stream).  The call returns once the work is enqueued on it and
+ * does not synchronise; read the outputs after the stream's work (e.g. hipStreamSynchronize).  Its scratch memory is a
+ * per-device arena the library keeps: an event recorded behind each call's work makes the next call (on any stream) wait for
+ * it on the device, and only growing the arena waits on the host for the previous call before freeing the old buffer.  Keep
+ * the host input arrays unchanged until the work is done (they are uploaded with hipMemcpyAsync on `stream`).
+ * Returns 0, or < 0 as every entry point (-3: no HIP device). */
+int sc_encode_steps_device(sc_engine* engine_or_null, int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off,
+                           const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int layout,
+                           void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
+                           int32_t* n_legal, int32_t* status);
+
 /* ------------------------------------------------------------------ self-play (L-search) */
 /* SYNTH: integer-hash evaluator for exact search-parity tests; SYNTH_COARSE: the same with 2-bit priors and values from
  * {-0.5, 0, 0.5} (exact PUCT ties between some siblings); SYNTH_UNIFORM: uniform priors, value 0 (every unvisited sibling
@@ -242,6 +268,18 @@ int sc_selfplay_get_trace(sc_selfplay*, int game /*0..n_games-1*/, sc_trace_info
  * since they were last reported.  With trace_hold the traces reported by the PREVIOUS call are released first (their ring
  * rows become free for new games), so the host reads each batch between two polls.  < 0: error. */
 int sc_selfplay_poll(sc_selfplay*, int32_t* finished_games, int cap);
+/* Training tensors of finished games, from the trace ring rows in place (see sc_encode_steps_device for the outputs, layouts,
+ * the scatter_add_ rule and the stream contract).  games[0..n): handle-local game indices (host).  ply_off (host, n+1) receives
+ * the plies of game i: [ply_off[i], ply_off[i+1]); call with every output (status included) NULL to get the sizes only.
+ * Readiness as sc_selfplay_get_trace: returns 1 if a requested game has not finished, 2 if its row has been overwritten or
+ * released (2 wins over 1); nothing is enqueued then.  If every requested game was reported by sc_selfplay_poll and is held
+ * (trace_hold), the rows are final and are read without waiting for the handle's stream (simulation steps enqueued before
+ * may still run); the next sc_selfplay_poll waits for this work before it releases them.  Otherwise the handle's work is
+ * completed first, and the handle's later steps wait on the device for this work.  A poisoned handle refuses with
+ * SC_ERR_HANDOFF. */
+int sc_selfplay_encode_traces(sc_selfplay*, int n, const int32_t* games, int apply_mirror, int layout, void* stream, uint32_t* ply_off,
+                              void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal,
+                              int32_t* status);
 /* Writes the reference's trace JSON (src/trace.rs:23-32; serde_json pretty, keys "outcome","steps"). */
 int sc_selfplay_write_trace_json(sc_selfplay*, int game, const char* path);
 

@@ -575,6 +575,220 @@ int sc_encode_steps_last_timing(float* kernels_ms, float* total_ms) {
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ device-resident training tensors
+// sc_encode_steps_device / sc_selfplay_encode_traces (include/sc_engine.h): the kernels of sc_encode_steps, writing into the
+// caller's device buffers on the caller's stream.  Nothing is staged and nothing waits for the device in the steady state.
+// The scratch of a call lives in a per-device arena that the library keeps and reuses: an event recorded behind each call's
+// work orders the next call after it on the device (hipStreamWaitEvent, whatever its stream); only growing the arena waits
+// on the host, for that previous call, before the old buffer is freed.
+namespace {
+struct EncArena {
+    char* base = nullptr;
+    size_t cap = 0;
+    hipEvent_t ev = nullptr;   // behind the last call's work
+    bool used = false;
+};
+std::mutex g_enc_mu;   // held across a call's enqueue: calls on one device take the arena in turn
+std::map<int, EncArena> g_enc_arena;
+struct ArenaRelease {   // scope guard: on every path out of the call (failures included), later calls wait for what was enqueued
+    EncArena& a;
+    hipStream_t s;
+    bool armed = false;
+    ~ArenaRelease() {
+        if (armed && hipEventRecord(a.ev, s) == hipSuccess) a.used = true;
+    }
+};
+
+struct DevEncodeOut {
+    int layout;
+    void* boards;
+    void* meta;
+    float* dist;
+    float* dist_legal;
+    uint16_t* legal_idx;
+    int32_t* n_legal;
+    int32_t* status;
+};
+// the trace ring as the encoder's source (sc_selfplay_encode_traces)
+struct RingSrc {
+    const int32_t* rows;   // host: ring row of each requested game
+    const sc::SpParams* p;
+};
+}  // namespace
+
+// output pointers must be device memory of `dev` (a host pointer, or memory of another GPU, would be written by kernels that
+// cannot reach it)
+static int check_device_ptr(const void* ptr, int dev, const char* name) {
+    if (!ptr) return 0;
+    hipPointerAttribute_t a{};
+    const hipError_t e = hipPointerGetAttributes(&a, ptr);
+    (void)hipGetLastError();   // (an unknown host pointer is an error of this query only)
+    if (e != hipSuccess || a.type != hipMemoryTypeDevice)
+        return fail(std::string(name) + ": not device memory (outputs of this call are device pointers, e.g. hipMalloc or a torch "
+                    "tensor on the handle's GPU)");
+    if (a.device != dev)
+        return fail(std::string(name) + ": memory of device " + std::to_string(a.device) + ", the call runs on device " + std::to_string(dev));
+    return 0;
+}
+
+static int check_device_outputs(const DevEncodeOut& o, int dev) {
+    if (o.layout != 0 && o.layout != 1) return fail("layout must be 0 (reference) or 1 (trainer)");
+    const std::pair<const void*, const char*> outs[] = {{o.boards, "boards"}, {o.meta, "meta"}, {o.dist, "dist"}, {o.dist_legal, "dist_legal"},
+                                                        {o.legal_idx, "legal_idx"}, {o.n_legal, "n_legal"}, {o.status, "status"}};
+    for (const auto& x : outs) {
+        const int rc = check_device_ptr(x.first, dev, x.second);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// ply_off: host, n_games + 1 (the plies of game g are [ply_off[g], ply_off[g+1])).  Host path: moves / child_mv / child_n /
+// child_off are host arrays as sc_encode_steps takes them; ring path (ring != nullptr): the moves and children are read from the
+// trace ring rows on the device.
+static int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
+                              const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror,
+                              const DevEncodeOut& o, hipStream_t st) {
+    const uint32_t P = ply_off[n_games];
+    // the game records of one group of games: (games in the group) x (longest game of the group + 2) <= REC_BUDGET, so one long
+    // game among many short ones does not size the buffer for all of them (80 B per record: 80 MiB)
+    const size_t REC_BUDGET = (size_t)1 << 20;
+    const uint32_t CH = 32768;   // plies per launch of the per-ply kernels (bounds their legal-move / meta scratch: 15 MB)
+    struct Group {
+        int g0, ng, hist_cap;
+    };
+    std::vector<Group> groups;
+    size_t max_rec = 1;
+    for (int g0 = 0; g0 < n_games;) {
+        uint32_t mx = ply_off[g0 + 1] - ply_off[g0];
+        int g1 = g0 + 1;
+        while (g1 < n_games) {
+            const uint32_t m2 = std::max(mx, ply_off[g1 + 1] - ply_off[g1]);
+            if ((size_t)(g1 - g0 + 1) * (m2 + 2) > REC_BUDGET) break;
+            mx = m2;
+            g1++;
+        }
+        groups.push_back({g0, g1 - g0, (int)mx + 2});
+        max_rec = std::max(max_rec, (size_t)(g1 - g0) * (mx + 2));
+        g0 = g1;
+    }
+    const bool has_ring = ring != nullptr;
+    const uint32_t nchild = has_ring ? 0 : child_off[P];
+    const uint32_t cap = std::max<uint32_t>(std::min(CH, P), 1);
+    size_t bytes = 0;
+    auto take = [&](size_t n) {
+        const size_t o = bytes;
+        bytes += (std::max<size_t>(n, 1) + 255) & ~(size_t)255;
+        return o;
+    };
+    const size_t o_off = take(((size_t)n_games + 1) * 4), o_moves = take((size_t)P * 2), o_hoff = take((size_t)P * 4);
+    const size_t o_plen = take((size_t)P * 4), o_pgame = take((size_t)P * 4), o_hist = take(max_rec * sizeof(sc::Position));
+    const size_t o_lm = take((size_t)cap * 448), o_meta = take((size_t)cap * 28), o_nl = take((size_t)cap * 4);
+    const size_t o_rows = has_ring ? take((size_t)n_games * 4) : 0, o_src = has_ring ? take((size_t)P * 4) : 0;
+    const size_t o_coff = has_ring ? 0 : take(((size_t)P + 1) * 4), o_cmv = has_ring ? 0 : take((size_t)nchild * 2);
+    const size_t o_cn = has_ring ? 0 : take((size_t)nchild * 4);
+    std::lock_guard<std::mutex> lk(g_enc_mu);
+    EncArena& A = g_enc_arena[dev];
+    if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
+    if (bytes > A.cap) {
+        if (A.used) HIPOK(hipEventSynchronize(A.ev));   // the previous call's work still reads the old arena
+        dfree({A.base});
+        A.base = nullptr;
+        A.cap = 0;
+        A.used = false;
+        HIPOK(hipMalloc(reinterpret_cast<void**>(&A.base), bytes));
+        A.cap = bytes;
+    } else if (A.used) {
+        HIPOK(hipStreamWaitEvent(st, A.ev, 0));   // ... possibly on another stream
+    }
+    ArenaRelease guard{A, st};
+    guard.armed = true;
+    char* base = A.base;
+    uint32_t* d_off = reinterpret_cast<uint32_t*>(base + o_off);
+    uint16_t* d_moves = reinterpret_cast<uint16_t*>(base + o_moves);
+    uint32_t* d_hoff = reinterpret_cast<uint32_t*>(base + o_hoff);
+    uint32_t* d_plen = reinterpret_cast<uint32_t*>(base + o_plen);
+    uint32_t* d_pgame = reinterpret_cast<uint32_t*>(base + o_pgame);
+    sc::Position* d_hist = reinterpret_cast<sc::Position*>(base + o_hist);
+    uint16_t* d_lm = reinterpret_cast<uint16_t*>(base + o_lm);
+    int32_t* d_meta = reinterpret_cast<int32_t*>(base + o_meta);
+    int32_t* d_nl = reinterpret_cast<int32_t*>(base + o_nl);
+    int32_t* d_rows = has_ring ? reinterpret_cast<int32_t*>(base + o_rows) : nullptr;
+    uint32_t* d_src = has_ring ? reinterpret_cast<uint32_t*>(base + o_src) : nullptr;
+    uint32_t* d_coff = has_ring ? nullptr : reinterpret_cast<uint32_t*>(base + o_coff);
+    uint16_t* d_cmv = has_ring ? nullptr : reinterpret_cast<uint16_t*>(base + o_cmv);
+    uint32_t* d_cn = has_ring ? nullptr : reinterpret_cast<uint32_t*>(base + o_cn);
+    HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
+    if (ring) {
+        HIPOK(hipMemcpyAsync(d_rows, ring->rows, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
+    } else {
+        if (P) HIPOK(hipMemcpyAsync(d_moves, moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
+        HIPOK(hipMemcpyAsync(d_coff, child_off, ((size_t)P + 1) * 4, hipMemcpyHostToDevice, st));
+        if (nchild) {
+            HIPOK(hipMemcpyAsync(d_cmv, child_mv, (size_t)nchild * 2, hipMemcpyHostToDevice, st));
+            HIPOK(hipMemcpyAsync(d_cn, child_n, (size_t)nchild * 4, hipMemcpyHostToDevice, st));
+        }
+    }
+    HIPOK(hipMemsetAsync(o.status, 0x7f, (size_t)n_games * 4, st));   // sc::STATUS_NONE: no failing ply yet
+    const size_t bsz = o.layout == 1 ? 4 : 1, msz = 4;
+    for (const Group& gr : groups) {
+        const uint32_t p0 = ply_off[gr.g0], p1 = ply_off[gr.g0 + gr.ng];
+        if (p1 == p0) continue;
+        scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, d_rows, ring ? ring->p->num_steps : 0,
+                       ring ? ring->p->t_move : nullptr, d_moves, d_src, st);
+        scl::replay_group(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st);
+        for (uint32_t c0 = p0; c0 < p1; c0 += CH) {
+            const uint32_t n = std::min(CH, p1 - c0);
+            scl::encode_plies_dev(o.layout, (int)n, d_hist, d_hoff + c0, d_plen + c0,
+                                  o.boards ? static_cast<char*>(o.boards) + (size_t)c0 * 7168 * bsz : nullptr, d_meta, d_lm,
+                                  o.legal_idx ? o.legal_idx + (size_t)c0 * 224 : nullptr, d_nl, st);
+            scl::steps_dist_dev((int)n, d_lm, d_nl, d_moves + c0, ring ? ring->p->t_cmove : d_cmv,
+                                ring ? reinterpret_cast<const uint32_t*>(ring->p->t_cn) : d_cn, ring ? nullptr : d_coff + c0,
+                                ring ? d_src + c0 : nullptr, ring ? ring->p->t_nchild : nullptr, d_pgame + c0, d_plen + c0, apply_mirror,
+                                d_meta, o.layout, o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr,
+                                o.dist ? o.dist + (size_t)c0 * 4672 : nullptr, o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr,
+                                o.n_legal ? o.n_legal + c0 : nullptr, o.status, st);
+        }
+    }
+    scl::status_final(n_games, o.status, st);
+    HIPOK(hipGetLastError());
+    return 0;
+}
+
+extern "C" {
+
+int sc_encode_steps_device(sc_engine* e, int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off,
+                           const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int layout,
+                           void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
+                           int32_t* n_legal, int32_t* status) {
+    if (n_games < 0 || !move_off || !child_off || !status) return fail("bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
+    const int dev = e ? e->device : device_id;
+    if (dev < 0 || dev >= ndev) return fail("device_id out of range");
+    HIPOK(hipSetDevice(dev));
+    const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
+    {
+        const int rc = check_device_outputs(o, dev);
+        if (rc) return rc;
+    }
+    if (n_games == 0) return 0;
+    uint32_t maxlen = 0;
+    for (int g = 0; g < n_games; g++) {
+        if (move_off[g + 1] < move_off[g]) return fail("move_off not monotonic");
+        maxlen = std::max(maxlen, move_off[g + 1] - move_off[g]);
+    }
+    if (maxlen > 4000) return fail("move list too long");
+    const uint32_t total = move_off[n_games];
+    if (total && !moves) return fail("bad argument");
+    for (uint32_t p = 0; p < total; p++)
+        if (child_off[p + 1] < child_off[p] || child_off[p + 1] - child_off[p] > 224) return fail("child_off: more than 224 children or not monotonic");
+    if (child_off[total] && (!child_mv || !child_n)) return fail("bad argument");
+    return encode_device_core(dev, n_games, move_off, moves, child_mv, child_n, child_off, nullptr, apply_mirror, o,
+                              static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
+
 // ============================================================================================
 // self-play
 // ============================================================================================
@@ -636,6 +850,10 @@ struct sc_selfplay {
     // streaming drain (sc_selfplay_poll): per trace-ring row, the game id last reported to the host (+1; 0 = none)
     std::vector<uint64_t> reported;
     std::vector<int> to_release;     // rows handed out by the previous poll (trace_hold)
+    // sc_selfplay_encode_traces: recorded on the caller's stream behind the last encode that read ring rows; the next poll
+    // waits for it before it releases rows
+    hipEvent_t enc_ev = nullptr;
+    bool enc_pending = false;
     // search wave + tower in one launch (step_kernels.hip).  Chosen at creation: only with at most one game per compute
     // unit and a single group -- with more games than CUs the separate search launch runs all of them at once while the
     // fused workgroups (83 KB of LDS: one per CU) would take turns, and with several interleaved groups one group's search
@@ -855,6 +1073,10 @@ void sc_selfplay_destroy(sc_selfplay* sp) {
     for (hipEvent_t ev : sp->ev) (void)hipEventDestroy(ev);
     if (sp->ev_begin) (void)hipEventDestroy(sp->ev_begin);
     if (sp->ev_end) (void)hipEventDestroy(sp->ev_end);
+    if (sp->enc_ev) {
+        (void)hipEventSynchronize(sp->enc_ev);
+        (void)hipEventDestroy(sp->enc_ev);
+    }
     if (sp->own_stream && sp->stream) (void)hipStreamDestroy(sp->stream);
     delete sp;
 }
@@ -1204,6 +1426,11 @@ int sc_selfplay_poll(sc_selfplay* sp, int32_t* finished_games, int cap) {
         if (sp->poisoned) return sp_refuse(sp);   // nothing of this batch is reported: the games that "finished" are not real
     }
     const sc::SpParams& p = sp->p;
+    // an encode of held rows may still be reading them on its own stream
+    if (sp->enc_pending) {
+        HIPOK(hipEventSynchronize(sp->enc_ev));
+        sp->enc_pending = false;
+    }
     // rows handed out by the previous poll go back to the device (the stream is idle: no kernel reads them now)
     for (int row : sp->to_release) {
         const int32_t free_state = sc::TR_FREE;
@@ -1227,6 +1454,68 @@ int sc_selfplay_poll(sc_selfplay* sp, int32_t* finished_games, int cap) {
         if (p.trace_hold) sp->to_release.push_back(f.second);
     }
     return n;
+}
+
+int sc_selfplay_encode_traces(sc_selfplay* sp, int n, const int32_t* games, int apply_mirror, int layout, void* stream, uint32_t* ply_off,
+                              void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal,
+                              int32_t* status) {
+    if (!sp || n < 0 || (n > 0 && !games) || !ply_off) return fail("bad argument");
+    HIPOK(hipSetDevice(sp->device));
+    if (sp->poisoned) return sp_refuse(sp);
+    const sc::SpParams& p = sp->p;
+    std::vector<int32_t> rows((size_t)std::max(n, 1));
+    bool all_held = true;
+    for (int i = 0; i < n; i++) {
+        const int g = games[i];
+        if (g < 0 || g >= p.total_games) return fail("bad argument: game index out of range");
+        const int row = g % p.trace_cap;
+        rows[(size_t)i] = row;
+        const uint64_t want_id = p.first_game_id + (uint64_t)g;
+        // the readiness rules of sc_selfplay_get_trace: a row reported by sc_selfplay_poll and held (trace_hold) is final
+        all_held = all_held && p.trace_hold && sp->reported[(size_t)row] == want_id + 1 &&
+                   std::find(sp->to_release.begin(), sp->to_release.end(), row) != sp->to_release.end();
+    }
+    if (!all_held) {
+        sp_flush(sp);
+        HIPOK(hipStreamSynchronize(sp->stream));
+        const int lrc = sp_latch(sp);
+        if (lrc) return lrc;
+        if (sp->poisoned) return sp_refuse(sp);
+    }
+    std::vector<sc::TraceHdr> hdr((size_t)p.trace_cap);
+    HIPOK(hipMemcpy(hdr.data(), p.thdr, hdr.size() * sizeof(sc::TraceHdr), hipMemcpyDeviceToHost));
+    int not_finished = 0, gone = 0;
+    ply_off[0] = 0;
+    for (int i = 0; i < n; i++) {
+        const int row = rows[(size_t)i];
+        const uint64_t want_id = p.first_game_id + (uint64_t)games[i];
+        const sc::TraceHdr& h = hdr[(size_t)row];
+        if (h.state == sc::TR_FREE) (sp->reported[(size_t)row] > want_id ? gone : not_finished) = 1;
+        else if (h.game_id > want_id) gone = 1;
+        else if (h.game_id < want_id || h.state != sc::TR_DONE) not_finished = 1;
+        ply_off[i + 1] = ply_off[i] + (uint32_t)std::max(h.n_steps, 0);
+    }
+    if (gone) return fail("trace released or overwritten (trace_capacity ring)", 2);
+    if (not_finished) return fail("game not finished", 1);
+    if (!boards && !meta && !dist && !dist_legal && !legal_idx && !n_legal && !status) return 0;   // sizing call
+    if (!status) return fail("bad argument: status is required");
+    const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
+    {
+        const int rc = check_device_outputs(o, sp->device);
+        if (rc) return rc;
+    }
+    if (n == 0) return 0;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const RingSrc ring{rows.data(), &p};
+    const int rc = encode_device_core(sp->device, n, ply_off, nullptr, nullptr, nullptr, nullptr, &ring, apply_mirror, o, st);
+    if (rc) return rc;
+    // the rows are read on `st`: the next poll (held rows) waits for that before it releases them, and a row that is not held
+    // could be reused by a new game -- the handle's next steps then wait for the encode on the device
+    if (!sp->enc_ev) HIPOK(hipEventCreateWithFlags(&sp->enc_ev, hipEventDisableTiming));
+    HIPOK(hipEventRecord(sp->enc_ev, st));
+    sp->enc_pending = true;
+    if (!all_held) HIPOK(hipStreamWaitEvent(sp->stream, sp->enc_ev, 0));
+    return 0;
 }
 
 int sc_selfplay_debug_break_handoff(sc_selfplay* sp, int missing) {

@@ -1479,6 +1479,181 @@ __global__ __launch_bounds__(64) void k_steps_dist(int n, const uint16_t* legal_
         }
     }
 }
+
+// ------------------------------------------------------------------ device-resident training tensors
+// sc_encode_steps_device / sc_selfplay_encode_traces: the same per-ply work as k_encode_plies + k_steps_dist, written
+// straight into the caller's device buffers (no staging), in the reference layout or the trainer's (float32, channel-major),
+// with the status reduced on the device.
+
+// per ply q of the games [g0, g0 + ng) (plies ply_off[g0] + [0, n)): its game, its index in the game and the record offset of
+// its game in the group's history buffer (group-local: ng * hist_cap records).  From the trace ring (t_move != nullptr) also
+// the ply's move and its ring index row * num_steps + ply, so that the replay reads a packed move list.  One thread per ply.
+__global__ __launch_bounds__(256) void k_ply_index(int n, int g0, int ng, const uint32_t* ply_off, int hist_cap, uint32_t* hoff,
+                                                   uint32_t* plen, uint32_t* pgame, const int32_t* rows, int num_steps,
+                                                   const uint16_t* t_move, uint16_t* moves, uint32_t* src) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t q = ply_off[g0] + (uint32_t)i;
+    int lo = g0, hi = g0 + ng - 1;   // the last game whose first ply is <= q (a game without plies shares its offset with the next)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (ply_off[mid] <= q) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint32_t t = q - ply_off[lo];
+    hoff[q] = (uint32_t)(lo - g0) * (uint32_t)hist_cap;
+    plen[q] = t;
+    pgame[q] = (uint32_t)lo;
+    if (t_move) {
+        const uint32_t s = (uint32_t)rows[lo] * (uint32_t)num_steps + t;
+        moves[q] = t_move[s];
+        src[q] = s;
+    }
+}
+
+// k_encode_plies with optional outputs and two plane layouts.  LAYOUT 0: int8 [n][8][8][112] as encode_wave writes it;
+// LAYOUT 1: float32 [n][112][8][8] -- lane = square, one plane per store, so each of the 112 stores of a ply is one
+// contiguous 256-byte row.  meta (int32, stride 7), legal_mv and n_legal are the call's scratch (k_steps_dist_dev reads them);
+// boards and legal_idx are the caller's buffers or nullptr.
+template <int LAYOUT>
+__global__ __launch_bounds__(64) void k_encode_plies_dev(int n, const Position* hist_all, const uint32_t* hoff, const uint32_t* plen,
+                                                         void* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx,
+                                                         int32_t* n_legal) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n) return;
+    __shared__ __attribute__((aligned(16))) int8_t s_stage[7168];
+    __shared__ move_t s_moves[MAXC];
+    __shared__ int32_t s_meta[8];
+    __shared__ Position s_hist[8];
+    const HistChain hc{hist_all + hoff[g]};
+    const int played = (int)plen[g];
+    stage_history(hc, played, lane, s_hist);
+    __syncthreads();
+    const Position cur = s_hist[0];
+    int nl = 0;
+    gen_legal_wave(cur, s_moves, lane, nl);
+    __syncthreads();
+    for (int i = lane; i < MAXC; i += 64) {
+        legal_mv[(size_t)g * MAXC + i] = i < nl ? s_moves[i] : (move_t)0;
+        if (legal_idx) legal_idx[(size_t)g * MAXC + i] = i < nl ? (uint16_t)move_index(s_moves[i], cur.turn) : (uint16_t)0;
+    }
+    if (lane == 0) n_legal[g] = nl;
+    int8_t* out8 = (LAYOUT == 0 && boards) ? static_cast<int8_t*>(boards) + (size_t)g * 7168 : nullptr;
+    encode_wave(s_hist, played < 7 ? played + 1 : 8, lane, s_stage, out8, s_meta);
+    if (LAYOUT == 1 && boards) {
+        // this lane's own 112 plane bytes (written by this lane above), widened to float, plane by plane
+        const uint4* cell16 = reinterpret_cast<const uint4*>(s_stage + lane * 112);
+        uint32_t w[28];
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            const uint4 v = cell16[k];
+            w[4 * k] = v.x;
+            w[4 * k + 1] = v.y;
+            w[4 * k + 2] = v.z;
+            w[4 * k + 3] = v.w;
+        }
+        float* o = static_cast<float*>(boards) + (size_t)g * 7168 + lane;
+#pragma unroll
+        for (int c = 0; c < 112; c++) o[c * 64] = (float)(int8_t)((w[c >> 2] >> (8 * (c & 3))) & 0xffu);
+    }
+    __syncthreads();
+    if (lane < 7) meta[(size_t)g * 7 + lane] = s_meta[lane];
+}
+
+// k_steps_dist with optional outputs: the legal-set check, the u32 visit sum and the division are k_steps_dist's, line for
+// line.  Children come either as CSR (child_off[q] .. child_off[q+1] into child_mv / child_n) or, with src != nullptr, as the
+// trace ring's padded rows (ply q: row src[q] of MAXC entries, nchild[src[q]] of them).  Writes the (mirrored) meta in the
+// requested layout, the dense dist row, the legal-move row dist_legal[q][i] = share of legal move i (0 past n_legal), n_legal,
+// and folds the ply's failure into status[game] with an atomic min over the key 2 * ply + kind (kind 0: children are not the
+// legal moves, kind 1: the played move is illegal) -- the first failing ply wins, a children mismatch beats an illegal move
+// at the same ply; k_status_final turns the keys into sc_encode_steps's codes.
+__global__ __launch_bounds__(64) void k_steps_dist_dev(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv,
+                                                       const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off,
+                                                       const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
+                                                       const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout,
+                                                       void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out,
+                                                       int32_t* status) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= n) return;
+    __shared__ move_t s_lm[MAXC];
+    __shared__ int s_hit[MAXC];
+    __shared__ uint32_t s_cn[MAXC];
+    const int nl = n_legal_s[g];
+    size_t c0;
+    int nc;
+    if (src) {
+        const uint32_t s = src[g];
+        c0 = (size_t)s * MAXC;
+        nc = nchild[s];
+        nc = nc < 0 ? 0 : nc > MAXC ? MAXC : nc;
+    } else {
+        c0 = child_off[g];
+        nc = (int)(child_off[g + 1] - child_off[g]);
+    }
+    const int turn = meta_s[(size_t)g * 7];
+    if (dist) {
+        float4* dz = reinterpret_cast<float4*>(dist + (size_t)g * 4672);
+        for (int i = lane; i < 4672 / 4; i += 64) dz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int i = lane; i < MAXC; i += 64) {
+        s_lm[i] = i < nl ? legal_mv[(size_t)g * MAXC + i] : (move_t)0;
+        s_hit[i] = 0;
+        s_cn[i] = 0;
+    }
+    __syncthreads();
+    const move_t nx = next_mv[g];
+    int has_next = 0, bad = 0;
+    uint32_t sum = 0;
+    for (int i = lane; i < nl; i += 64) has_next |= (s_lm[i] == nx) ? 1 : 0;
+    for (int i = lane; i < nc; i += 64) {
+        const move_t m = child_mv[c0 + i];
+        int k = -1;
+        for (int j = 0; j < nl; j++)
+            if (s_lm[j] == m) k = j;
+        if (k < 0) bad = 1;
+        else {
+            s_hit[k] = 1;     // benign same-value race between duplicates
+            s_cn[k] = child_n[c0 + i];
+        }
+        sum += child_n[c0 + i];
+    }
+    __syncthreads();
+    for (int i = lane; i < nl; i += 64) bad |= s_hit[i] ? 0 : 1;   // with nc == nl this also catches duplicate children
+    bad |= (nc != nl) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);   // u32 wrap-around, as the reference's u32 sum in release mode
+    const float den = (float)sum + 1e-5f;
+    if (dist)
+        for (int i = lane; i < nc; i += 64) {
+            const int idx = move_index(child_mv[c0 + i], turn);
+            if (idx >= 0) dist[(size_t)g * 4672 + idx] = (float)child_n[c0 + i] / den;
+        }
+    if (dist_legal)
+        for (int i = lane; i < MAXC; i += 64) dist_legal[(size_t)g * MAXC + i] = (i < nl && s_hit[i]) ? (float)s_cn[i] / den : 0.f;
+    const bool any_bad = __ballot(bad) != 0, any_next = __ballot(has_next) != 0;
+    if (lane == 0) {
+        if (any_bad || !any_next) atomicMin(&status[pgame[g]], (int32_t)(2 * plen[g] + (any_bad ? 0 : 1)));
+        if (n_legal_out) n_legal_out[g] = nl;
+    }
+    if (meta_out && lane < 7) {
+        const int32_t* m = meta_s + (size_t)g * 7;
+        int32_t v = m[lane];
+        if (apply_mirror) {   // Board::rotate() (k_steps_dist)
+            const int32_t t = m[0];
+            v = lane == 0 ? 1 - t : lane == 1 ? m[1] + (t == 1 ? 1 : 0) : lane == 2 ? m[4] : lane == 3 ? m[5] : lane == 4 ? m[2] : lane == 5 ? m[3] : v;
+        }
+        if (layout == 1) static_cast<float*>(meta_out)[(size_t)g * 7 + lane] = (float)v;
+        else static_cast<int32_t*>(meta_out)[(size_t)g * 7 + lane] = v;
+    }
+}
+
+// status keys (2 * ply + kind, STATUS_NONE when no ply failed) -> 0 / 1000 + ply / -(ply + 1)
+constexpr int32_t STATUS_NONE = 0x7f7f7f7f;   // what a 0x7f byte fill leaves
+__global__ __launch_bounds__(256) void k_status_final(int n, int32_t* status) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t v = status[i];
+    status[i] = v == STATUS_NONE ? 0 : (v & 1) ? -((v >> 1) + 1) : 1000 + (v >> 1);
+}
 #endif
 
 }  // namespace sc

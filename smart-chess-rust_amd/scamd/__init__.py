@@ -9,11 +9,14 @@ reference's usage:
   SelfPlay                       <->  bin `selfplay` (src/main.rs:155-238): same flag names
   encode_positions               <->  BoardState + _encode (src/chess.rs:665-877)
   encode_steps                   <->  libsmartchess.chess_encode_steps (src/lib.rs:46-128), the trace -> training-tensor step
+  encode_steps_torch,            <->  the same, plus ChessDataset's _prepare (py/dataset.py:31-87), as torch tensors on the GPU
+  SelfPlay.training_tensors           (from recorded games, or from the self-play trace ring in place)
 
 There is NO CPU fallback: importing works anywhere (so the C ABI can be checked), but every
 compute entry point raises EngineError when the HIP library or a GPU is missing.
 """
 from .binding import (ChessHip, Engine, EngineError, Play, SelfPlay, encode_move, encode_positions, encode_steps, encode_steps_batch,  # noqa: F401
+                      encode_steps_torch, pack_steps, hip_runtime, hip_runtime_files,
                       enqueue_interleaved, elo, find_max, lib, lib_path, play_match, runtime_flags, search,
                       move_uci, uci_move, write_trace_json, TERMINATION)
 from . import binding  # noqa: F401

@@ -93,12 +93,15 @@ ABI = {
     "sc_selfplay_set_position": (_i, [_vp, _i, _vp, _i]),
     "sc_encode_steps_last_timing": (_i, [C.POINTER(_f), C.POINTER(_f)]),
     "sc_encode_steps": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_encode_steps_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_selfplay_encode_traces": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_trace_write_json": (_i, [C.c_char_p, C.POINTER(TraceInfo), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_move_uci": (_i, [C.c_uint16, C.c_char_p]),
     "sc_move_index": (_i, [C.c_uint16, _i]),
 }
 
 _lib = None
+_engine_hip = []   # libamdhip64 file(s) libsc_engine.so bound to when it was loaded
 
 
 def lib_path():
@@ -113,10 +116,15 @@ def lib():
     if not os.path.exists(_LIB_PATH):
         raise EngineError(f"{_LIB_PATH} is missing: build it with `python smart-chess-rust_amd/build.py` "
                           "(there is no CPU fallback)")
+    before = set(hip_runtime_files())
     try:
         L = C.CDLL(_LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise EngineError(f"cannot load {_LIB_PATH}: {e}") from e
+    # the HIP runtime the engine bound to: the one its loading mapped, or the one already there (a host that loaded torch first)
+    global _engine_hip
+    new = set(hip_runtime_files()) - before
+    _engine_hip = sorted(new or before)
     for name, (res, args) in ABI.items():
         fn = getattr(L, name)
         fn.restype = res
@@ -155,6 +163,7 @@ class Engine:
     def __init__(self, n_res_blocks=10, channels=256, seed=0, weights=None, device=0, precision="bf16"):
         self.L = lib()
         self.n_res_blocks, self.channels = n_res_blocks, channels
+        self.device = device
         cfg = NetConfig(n_res_blocks, channels, seed, {"bf16": 0, "fp8": 1}[precision], 0)
         h = C.c_void_p()
         _check(self.L.sc_engine_create(C.byref(cfg), weights.encode() if weights else None, device, C.byref(h)))
@@ -256,6 +265,130 @@ def encode_steps_batch(games, apply_mirror=False, device=0, engine=None):
                              int(bool(apply_mirror)), _p(boards), _p(meta), _p(dist), _p(li), _p(nl), _p(status)))
     return dict(boards=boards[:P], meta=meta[:P], dist=dist[:P], move_indices=[li[i, :nl[i]].astype(np.int32) for i in range(P)],
                 ply_off=off, status=status[:n])
+
+
+def pack_steps(games):
+    """The list form of encode_steps_batch -> the packed arrays (moves, move_off, child_mv, child_n, child_off) that
+    sc_encode_steps / sc_encode_steps_device take"""
+    mv = lambda m: uci_move(m) if isinstance(m, str) else int(m)
+    n = len(games)
+    off = np.zeros(n + 1, np.uint32)
+    off[1:] = np.cumsum([len(g) for g in games])
+    P = int(off[n])
+    flat = np.asarray([mv(s[0]) for g in games for s in g] or [0], np.uint16)
+    coff = np.zeros(P + 1, np.uint32)
+    coff[1:] = np.cumsum([len(s[1]) for g in games for s in g])
+    cm = np.asarray([mv(c[0]) for g in games for s in g for c in s[1]] or [0], np.uint16)
+    cn = np.asarray([int(c[1]) for g in games for s in g for c in s[1]] or [0], np.uint32)
+    return flat, off, cm, cn, coff
+
+
+def hip_runtime_files():
+    """the distinct libamdhip64 files mapped into this process (/proc/self/maps)"""
+    found = set()
+    with open("/proc/self/maps") as f:
+        for ln in f:
+            parts = ln.split(None, 5)
+            if len(parts) == 6 and os.path.basename(parts[5].strip()).startswith("libamdhip64"):
+                found.add(os.path.realpath(parts[5].strip()))
+    return sorted(found)
+
+
+def hip_runtime():
+    """ctypes handle of the HIP runtime libsc_engine.so uses (device buffers for the *_device entry points without torch)"""
+    lib()
+    if len(_engine_hip) != 1:
+        raise EngineError(f"cannot tell which HIP runtime libsc_engine.so uses: {_engine_hip}")
+    return C.CDLL(_engine_hip[0])
+
+
+_LAYOUTS = {"reference": 0, "trainer": 1}
+_DISTS = ("dense", "legal", "both")
+
+
+def _torch_for_device():
+    """torch, after checking that it shares the engine's HIP runtime: device pointers must not cross between two runtimes"""
+    L = lib()
+    if L.sc_device_count() <= 0:
+        raise EngineError("no HIP device available: libsc_engine has no CPU fallback")
+    import torch
+    files = hip_runtime_files()
+    if len(files) > 1:
+        raise EngineError(f"two HIP runtimes are loaded ({', '.join(files)}): torch was imported after scamd loaded "
+                          "libsc_engine.so -- import torch before scamd")
+    return torch
+
+
+def _device_outputs(torch, device, P, n, layout, dist):
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(_LAYOUTS)}")
+    if dist not in _DISTS:
+        raise ValueError(f"dist must be one of {_DISTS}")
+    lay = _LAYOUTS[layout]
+    dev = torch.device("cuda", device)
+    R = max(P, 1)
+    out = {}
+    if lay == 1:
+        out["boards"] = torch.empty((R, 112, 8, 8), dtype=torch.float32, device=dev)
+        out["meta"] = torch.empty((R, 7), dtype=torch.float32, device=dev)
+    else:
+        out["boards"] = torch.empty((R, 8, 8, 112), dtype=torch.int8, device=dev)
+        out["meta"] = torch.empty((R, 7), dtype=torch.int32, device=dev)
+    out["dist"] = torch.empty((R, 4672), dtype=torch.float32, device=dev) if dist in ("dense", "both") else None
+    out["dist_legal"] = torch.empty((R, MAX_MOVES), dtype=torch.float32, device=dev) if dist in ("legal", "both") else None
+    out["legal_idx"] = torch.empty((R, MAX_MOVES), dtype=torch.int16, device=dev)   # action indices < 4672: exact in int16
+    out["n_legal"] = torch.empty(R, dtype=torch.int32, device=dev)
+    out["status"] = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    args = [lay] + [ptr(out[k]) for k in ("boards", "meta", "dist", "dist_legal", "legal_idx", "n_legal", "status")]
+    return out, args
+
+
+def _finish_outputs(torch, out, ply_off, outcome_per_game, apply_mirror, device):
+    n = ply_off.size - 1
+    P = int(ply_off[n])
+    status = out.pop("status")[:n].cpu().numpy()   # the one host copy: waits for the work on the current stream
+    res = {k: (None if v is None else v[:P]) for k, v in out.items()}
+    oc = np.repeat(np.asarray(outcome_per_game, np.float32), np.diff(ply_off.astype(np.int64)))
+    if apply_mirror:
+        oc = -oc   # ChessDataset negates the outcome under the mirror (py/dataset.py)
+    res["outcome"] = torch.from_numpy(oc).to(torch.device("cuda", device))
+    res["ply_off"] = ply_off
+    res["status"] = status
+    return res
+
+
+def encode_steps_torch(games, apply_mirror=False, layout="trainer", dist="dense", engine=None, device=0, outcomes=None):
+    """Training tensors on the GPU, for a trainer there (sc_encode_steps_device): no copy through the host.
+    games: the list form of encode_steps_batch, or the packed arrays (moves, move_off, child_mv, child_n, child_off) as a
+    tuple or a dict with those keys (pack_steps).  layout "trainer": boards float32 [P,112,8,8] and meta float32 [P,7]
+    (py/dataset.py _prepare); "reference": int8 [P,8,8,112] and int32 [P,7] as encode_steps_batch.  dist "dense": dist
+    float32 [P,4672]; "legal": dist_legal float32 [P,224] aligned with legal_idx (rebuild the dense rows with
+    zeros(P, 4672).scatter_add_(1, legal_idx.long(), dist_legal) -- scatter_add_, not scatter_: padding entries point at action
+    0); "both".  outcomes: per game, White's result (1, -1, 0; None: 0) -> outcome float32 [P], negated under apply_mirror as
+    ChessDataset does.
+    -> dict of torch tensors on cuda:<device> (enqueued on torch.cuda.current_stream()): boards, meta, dist, dist_legal,
+    legal_idx (int16) [P,224], n_legal int32 [P], outcome; plus ply_off (numpy) and status (numpy, sc_encode_steps's codes)."""
+    L = lib()
+    if L.sc_device_count() <= 0:
+        raise EngineError("no HIP device available: libsc_engine has no CPU fallback")
+    if isinstance(games, dict):
+        packed = tuple(games[k] for k in ("moves", "move_off", "child_mv", "child_n", "child_off"))
+    elif isinstance(games, tuple) and len(games) == 5 and all(isinstance(a, np.ndarray) for a in games):
+        packed = games
+    else:
+        packed = pack_steps(games)
+    flat, off, cm, cn, coff = (np.ascontiguousarray(a, t) for a, t in zip(packed, (np.uint16, np.uint32, np.uint16, np.uint32, np.uint32)))
+    n = off.size - 1
+    torch = _torch_for_device()
+    dev = engine.device if engine is not None else device
+    out, args = _device_outputs(torch, dev, int(off[n]), n, layout, dist)
+    stream = torch.cuda.current_stream(dev)
+    _check(L.sc_encode_steps_device(engine.h if engine else None, dev, n, _p(flat if flat.size else np.zeros(1, np.uint16)), _p(off),
+                                    _p(cm if cm.size else np.zeros(1, np.uint16)), _p(cn if cn.size else np.zeros(1, np.uint32)),
+                                    _p(coff), int(bool(apply_mirror)), args[0], C.c_void_p(stream.cuda_stream), *args[1:]))
+    oc = np.zeros(n, np.float32) if outcomes is None else np.asarray(outcomes, np.float32)
+    return _finish_outputs(torch, out, off, oc, apply_mirror, dev)
 
 
 def encode_steps_last_timing():
@@ -485,6 +618,7 @@ class SelfPlay:
                  tie_random=False, trace_hold=False, rollout_factor=0.0):
         self.L = lib()
         self.engine = engine
+        self.device = engine.device if engine is not None else device
         cfg = SelfplayConfig(n_slots, n_games if n_games is not None else n_slots, rollout_num, num_steps, cpuct,
                              temperature, temperature_switch, epsilon, int(with_noise), outcome_gate,
                              EVALUATORS[evaluator], int(external_noise), seed, first_game_id, trace_capacity, int(own_stream),
@@ -567,6 +701,27 @@ class SelfPlay:
         if info.has_outcome:
             outcome = {"termination": TERMINATION[info.termination], "winner": _WINNER[info.winner]}
         return {"steps": steps, "outcome": outcome, "game_id": int(info.game_id)}
+
+    def training_tensors(self, games, apply_mirror=False, layout="trainer", dist="dense"):
+        """Training tensors of finished games straight from the trace ring (sc_selfplay_encode_traces), as torch tensors on
+        this handle's GPU -- see encode_steps_torch for the result.  outcome comes from the ring headers.  Raises EngineError
+        with .code 1 if a game has not finished, 2 if its ring row has been overwritten or released."""
+        games = np.ascontiguousarray(games, np.int32).reshape(-1)
+        n = games.size
+        torch = _torch_for_device()
+        ply_off = np.zeros(n + 1, np.uint32)
+        _check(self.L.sc_selfplay_encode_traces(self.h, n, _p(games), 0, 0, None, _p(ply_off), None, None, None, None, None,
+                                                None, None))
+        win = np.zeros(n, np.float32)
+        info = TraceInfo()
+        for i, g in enumerate(games):
+            _check(self.L.sc_selfplay_get_trace(self.h, int(g), C.byref(info), None, None, None, None, None, None, None))
+            win[i] = {1: 1.0, 0: -1.0}.get(info.winner, 0.0) if info.has_outcome else 0.0
+        out, args = _device_outputs(torch, self.device, int(ply_off[n]), n, layout, dist)
+        stream = torch.cuda.current_stream(self.device)
+        _check(self.L.sc_selfplay_encode_traces(self.h, n, _p(games), int(bool(apply_mirror)), args[0], C.c_void_p(stream.cuda_stream),
+                                                _p(ply_off), *args[1:]))
+        return _finish_outputs(torch, out, ply_off, win, apply_mirror, self.device)
 
     def write_trace(self, game, path):
         _check(self.L.sc_selfplay_write_trace_json(self.h, game, path.encode()))
