@@ -135,8 +135,10 @@ int sc_encode_steps(sc_engine* engine_or_null, int device_id, int n_games, const
                     const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror,
                     int8_t* boards, int32_t* meta, float* dist, uint16_t* legal_idx, int32_t* n_legal, int32_t* status);
 
-/* measurement aid (bench.py also_encode_steps): the last sc_encode_steps call of the calling thread -- HIP-event time of its
- * kernels (game walk, keys, repetition flags, planes + moves, dist: all chunks) and wall time of the whole call including the PCIe copies */
+/* measurement aid (bench.py also_encode_steps): the last sc_encode_steps call of the calling thread -- HIP-event time of the
+ * encoder work it enqueues, summed over its slices (per slice: the upload of the slice's moves, children and offsets, the ply
+ * index, game walk, keys, repetition flags, planes + moves, dist, status codes; not the copy-out) and wall time of the whole call
+ * including the PCIe copies */
 int sc_encode_steps_last_timing(float* kernels_ms, float* total_ms);
 
 /* Training tensors straight into DEVICE memory, for a trainer on the same GPU (no copy through the host).

@@ -265,15 +265,24 @@ SC_HD bool reduces_castling(const Position& p, move_t m) {
 // python-chess is_irreversible(move), evaluated on the position BEFORE the move
 SC_HD bool is_irreversible(const Position& p, move_t m) { return is_zeroing(p, m) || reduces_castling(p, m) || has_legal_ep(p); }
 
-// Plays m on p (flags' REP bits are cleared; IRREV and key are set). Pure function of (p, m); p.key must be
-// valid on entry (it is updated incrementally: <= 7 key terms instead of a 32-piece recompute).
+// Plays m on p.  make_move(p, m), WITH_KEY: flags' REP bits are cleared, IRREV and key are set; p.key must be valid on entry (it
+// is updated incrementally: <= 7 key terms instead of a 32-piece recompute).  Pure function of (p, m).
+// WITH_KEY = false (make_move_board) is the board half alone -- pieces, occupancy, castling rights, ep square, clocks, side to
+// move -- and leaves key and flags zero: no key terms, no irreversibility test and neither of the two has_legal_ep probes.  The
+// training-tensor encoder walks a game with it, one wave per game and a chain of dependent steps, at ~10 % of what a full
+// make_move + repetition scan per ply cost there (1.9 us per ply, 194 us for 100-ply games), and computes the keys, F_IRREV and
+// the repetition flags of all plies in parallel afterwards (mcts_kernels.hpp: k_replay_raw, k_ply_keys, k_ply_rep).
+// tests/test_engine_rules_host.py::test_make_move_board_matches_make_move compares the two instantiations field by field.
+// (make_move is the template itself and not a second name around it: one more level of inlining reorders operands in k_step and
+// k_mcts, and tools/isa_compare.py would no longer show their instruction streams unchanged.)
+template <bool WITH_KEY = true>
 SC_HD void make_move(Position& p, move_t m) {
     int from = mv_from(m), to = mv_to(m), promo = mv_promo(m);
     int us = p.turn, them = !us;
-    bool old_ep_legal = has_legal_ep(p);
+    bool old_ep_legal = WITH_KEY ? has_legal_ep(p) : false;
     bool zero = is_zeroing(p, m);
-    bool irrev = zero || reduces_castling(p, m) || old_ep_legal;  // python-chess is_irreversible
-    bb_t key = p.key ^ state_key(us, p.castling, old_ep_legal ? p.ep : -1);
+    bool irrev = WITH_KEY ? zero || reduces_castling(p, m) || old_ep_legal : false;  // python-chess is_irreversible
+    bb_t key = WITH_KEY ? p.key ^ state_key(us, p.castling, old_ep_legal ? p.ep : -1) : 0;
     int old_ep = p.ep;
     p.ep = -1;
     p.halfmove = zero ? 0 : (uint16_t)(p.halfmove + 1);
@@ -284,13 +293,13 @@ SC_HD void make_move(Position& p, move_t m) {
     // remove mover
     xor_pcs(p, pt, fb);
     xor_occ(p, us, fb);
-    key ^= psq_key(pt, us, from);
+    if constexpr (WITH_KEY) key ^= psq_key(pt, us, from);
     p.castling &= (uint8_t)~(castle_bit_for_sq(from) | castle_bit_for_sq(to));
     if (pt == KING) p.castling &= us ? (uint8_t)~3 : (uint8_t)~12;
     if (cap >= 0) {
         xor_pcs(p, cap, tb);
         xor_occ(p, them, tb);
-        key ^= psq_key(cap, them, to);
+        if constexpr (WITH_KEY) key ^= psq_key(cap, them, to);
     }
     if (pt == PAWN) {
         int diff = to - from;
@@ -301,7 +310,7 @@ SC_HD void make_move(Position& p, move_t m) {
             bb_t cb = bit(csq);
             p.pcs[PAWN] ^= cb;
             xor_occ(p, them, cb);
-            key ^= psq_key(PAWN, them, csq);
+            if constexpr (WITH_KEY) key ^= psq_key(PAWN, them, csq);
         }
     }
     int placed = pt;
@@ -313,64 +322,17 @@ SC_HD void make_move(Position& p, move_t m) {
         bb_t rf = bit(rfs), rt = bit(rts);
         p.pcs[ROOK] ^= rf | rt;
         xor_occ(p, us, rf | rt);
-        key ^= psq_key(ROOK, us, rfs) ^ psq_key(ROOK, us, rts);
+        if constexpr (WITH_KEY) key ^= psq_key(ROOK, us, rfs) ^ psq_key(ROOK, us, rts);
     }
     xor_pcs(p, placed, tb);  // the target square is empty at this point (a captured piece was removed above)
     xor_occ(p, us, tb);
-    key ^= psq_key(placed, us, to);
+    if constexpr (WITH_KEY) key ^= psq_key(placed, us, to);
     p.turn = (uint8_t)them;
     p.flags = irrev ? F_IRREV : 0;
-    p.key = key ^ state_key(them, p.castling, has_legal_ep(p) ? p.ep : -1);
+    if constexpr (WITH_KEY) key ^= state_key(them, p.castling, has_legal_ep(p) ? p.ep : -1);
+    p.key = key;
 }
-
-// The board half of make_move alone: pieces, occupancy, castling rights, ep square, clocks, side to move.  key and flags are left
-// zero: the training-tensor encoder walks a game with this (one wave per game, a chain of dependent steps) and computes the keys,
-// the irreversibility flag and the repetition flags of all plies in parallel afterwards (mcts_kernels.hpp: k_replay_raw,
-// k_ply_keys, k_ply_rep).  Must stay in step with make_move above: tests/test_engine_rules_host.py::test_make_move_board_matches_make_move
-// compares the two field by field on every legal move of ~10^5 positions, and tests/test_gpu_parity.py::test_encode_steps_* and
-// tests/test_gpu_rules.py::test_encode_steps_on_edge_lines compare the encoder's result with the oracle.
-SC_HD void make_move_board(Position& p, move_t m) {
-    int from = mv_from(m), to = mv_to(m), promo = mv_promo(m);
-    int us = p.turn, them = !us;
-    bool zero = is_zeroing(p, m);
-    int old_ep = p.ep;
-    p.ep = -1;
-    p.halfmove = zero ? 0 : (uint16_t)(p.halfmove + 1);
-    if (us == BLACK) p.fullmove++;
-    bb_t fb = bit(from), tb = bit(to);
-    int pt = piece_type_at(p, from);
-    int cap = (occ_c(p, them) & tb) ? piece_type_at(p, to) : -1;
-    xor_pcs(p, pt, fb);
-    xor_occ(p, us, fb);
-    p.castling &= (uint8_t)~(castle_bit_for_sq(from) | castle_bit_for_sq(to));
-    if (pt == KING) p.castling &= us ? (uint8_t)~3 : (uint8_t)~12;
-    if (cap >= 0) {
-        xor_pcs(p, cap, tb);
-        xor_occ(p, them, tb);
-    }
-    if (pt == PAWN) {
-        int diff = to - from;
-        if (diff == 16 && (from >> 3) == 1) p.ep = (int8_t)(from + 8);
-        else if (diff == -16 && (from >> 3) == 6) p.ep = (int8_t)(from - 8);
-        else if (to == old_ep && (diff == 7 || diff == 9 || diff == -7 || diff == -9) && cap < 0) {
-            bb_t cb = bit(old_ep + (us ? -8 : 8));
-            p.pcs[PAWN] ^= cb;
-            xor_occ(p, them, cb);
-        }
-    }
-    int placed = promo ? promo - 1 : pt;
-    if (pt == KING && (to - from == 2 || from - to == 2)) {
-        int base = from & 56;
-        bb_t rf = bit(to > from ? base + 7 : base + 0), rt = bit(to > from ? base + 5 : base + 3);
-        p.pcs[ROOK] ^= rf | rt;
-        xor_occ(p, us, rf | rt);
-    }
-    xor_pcs(p, placed, tb);
-    xor_occ(p, us, tb);
-    p.turn = (uint8_t)them;
-    p.flags = 0;
-    p.key = 0;
-}
+SC_HD void make_move_board(Position& p, move_t m) { make_move<false>(p, m); }
 
 // ------------------------------------------------------------------ legal move generation
 // python-chess _slider_blockers(king)

@@ -449,135 +449,13 @@ int sc_encode_positions(sc_engine* e, int device_id, int n, const uint16_t* move
     return rc;
 }
 
-// libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) for a batch of recorded games; see include/sc_engine.h
-int sc_encode_steps(sc_engine* e, int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off,
-                    const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int8_t* boards,
-                    int32_t* meta, float* dist, uint16_t* legal_idx, int32_t* n_legal, int32_t* status) {
-    if (n_games < 0 || !move_off || !child_off || !status) return fail("bad argument");
-    if (n_games == 0) return 0;
-    const auto t_call = std::chrono::steady_clock::now();
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
-    HIPOK(hipSetDevice(e ? e->device : device_id));
-    const uint32_t total = move_off[n_games];
-    uint32_t maxlen = 0;
-    for (int g = 0; g < n_games; g++) {
-        if (move_off[g + 1] < move_off[g]) return fail("move_off not monotonic");
-        maxlen = std::max(maxlen, move_off[g + 1] - move_off[g]);
-        status[g] = 0;
-    }
-    if (maxlen > 4000) return fail("move list too long");
-    for (uint32_t p = 0; p < total; p++)
-        if (child_off[p + 1] < child_off[p] || child_off[p + 1] - child_off[p] > 224) return fail("child_off: more than 224 children or not monotonic");
-    if (total == 0) return 0;
-    // one position per ply: (record index of its game's start position, number of moves already played)
-    const int hist_cap = (int)maxlen + 2;
-    std::vector<uint32_t> pstart(total), plen(total), pgame(total);
-    for (int g = 0; g < n_games; g++)
-        for (uint32_t t = move_off[g]; t < move_off[g + 1]; t++) {
-            pstart[t] = (uint32_t)g * (uint32_t)hist_cap;
-            plen[t] = t - move_off[g];
-            pgame[t] = (uint32_t)g;
-        }
-    if ((size_t)n_games * (size_t)hist_cap > (size_t)0xffffffffu) return fail("too many game records for one call");
-    const uint32_t CH = 8192;  // plies per launch of the per-ply kernels (bounds the output staging: CH * 26 KB)
-    const uint32_t nchild = child_off[total];
-    uint16_t *d_moves = nullptr, *d_cmv = nullptr, *d_lm = nullptr, *d_li = nullptr;
-    uint32_t *d_start = nullptr, *d_len = nullptr, *d_cn = nullptr, *d_coff = nullptr, *d_moff = nullptr;
-    sc::Position* d_hist = nullptr;
-    int8_t* d_boards = nullptr;
-    int32_t *d_meta = nullptr, *d_nl = nullptr, *d_flags = nullptr, *d_out = nullptr;
-    float* d_dist = nullptr;
-    const uint32_t cap = std::min(CH, total);
-    HIPOK(dalloc(&d_moves, total));
-    HIPOK(dalloc(&d_cmv, (size_t)nchild + 1));
-    HIPOK(dalloc(&d_cn, (size_t)nchild + 1));
-    HIPOK(dalloc(&d_coff, (size_t)cap + 1));
-    HIPOK(dalloc(&d_start, total));   // (all plies: the key / repetition kernels run over the whole batch at once)
-    HIPOK(dalloc(&d_len, total));
-    HIPOK(dalloc(&d_hist, (size_t)n_games * hist_cap));   // one 80-byte record per ply of every game (k_replay_games)
-    HIPOK(dalloc(&d_moff, (size_t)n_games + 1));
-    HIPOK(dalloc(&d_boards, (size_t)cap * 7168));
-    HIPOK(dalloc(&d_meta, (size_t)cap * 7));
-    HIPOK(dalloc(&d_nl, cap));
-    HIPOK(dalloc(&d_flags, cap));
-    HIPOK(dalloc(&d_out, (size_t)cap * 4));
-    HIPOK(dalloc(&d_lm, (size_t)cap * 224));
-    HIPOK(dalloc(&d_li, (size_t)cap * 224));
-    HIPOK(dalloc(&d_dist, (size_t)cap * 4672));
-    HIPOK(hipMemcpy(d_moves, moves, (size_t)total * 2, hipMemcpyHostToDevice));
-    HIPOK(hipMemcpy(d_moff, move_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice));
-    if (nchild) {
-        HIPOK(hipMemcpy(d_cmv, child_mv, (size_t)nchild * 2, hipMemcpyHostToDevice));
-        HIPOK(hipMemcpy(d_cn, child_n, (size_t)nchild * 4, hipMemcpyHostToDevice));
-    }
-    std::vector<int32_t> flags(cap), replay(4 * (size_t)cap);
-    std::vector<uint32_t> coff(cap + 1);
-    hipEvent_t evk[2] = {nullptr, nullptr};
-    HIPOK(hipEventCreate(&evk[0]));
-    HIPOK(hipEventCreate(&evk[1]));
-    float kernels_ms = 0.f;
-    // every game is walked once (board updates only: one record per ply), keys and repetition flags of all plies follow in parallel;
-    // then the plies are encoded from the records, 8 192 at a time
-    HIPOK(hipMemcpy(d_start, pstart.data(), (size_t)total * 4, hipMemcpyHostToDevice));
-    HIPOK(hipMemcpy(d_len, plen.data(), (size_t)total * 4, hipMemcpyHostToDevice));
-    HIPOK(hipEventRecord(evk[0], nullptr));
-    scl::replay_games(n_games, (int)total, d_moves, d_moff, d_hist, hist_cap, d_start, d_len, nullptr);
-    HIPOK(hipEventRecord(evk[1], nullptr));
-    HIPOK(hipGetLastError());
-    HIPOK(hipDeviceSynchronize());
-    HIPOK(hipEventElapsedTime(&kernels_ms, evk[0], evk[1]));
-    for (uint32_t p0 = 0; p0 < total; p0 += CH) {
-        const uint32_t n = std::min(CH, total - p0);
-        for (uint32_t i = 0; i <= n; i++) coff[i] = child_off[p0 + i];   // absolute offsets into d_cmv / d_cn
-        HIPOK(hipMemcpy(d_coff, coff.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice));
-        HIPOK(hipEventRecord(evk[0], nullptr));
-        scl::encode_plies((int)n, d_hist, d_start + p0, d_len + p0, d_boards, d_meta, d_lm, d_li, d_nl, nullptr);
-        // the ply's own move is moves[start + len] = d_moves + p0 + i
-        scl::steps_dist((int)n, d_lm, d_nl, d_moves + p0, d_cmv, d_cn, d_coff, apply_mirror, d_meta, d_dist, d_flags, nullptr);
-        HIPOK(hipEventRecord(evk[1], nullptr));
-        HIPOK(hipGetLastError());
-        HIPOK(hipDeviceSynchronize());
-        {
-            float ms = 0.f;
-            HIPOK(hipEventElapsedTime(&ms, evk[0], evk[1]));
-            kernels_ms += ms;
-        }
-        if (boards) HIPOK(hipMemcpy(boards + (size_t)p0 * 7168, d_boards, (size_t)n * 7168, hipMemcpyDeviceToHost));
-        if (meta) HIPOK(hipMemcpy(meta + (size_t)p0 * 7, d_meta, (size_t)n * 28, hipMemcpyDeviceToHost));
-        if (dist) HIPOK(hipMemcpy(dist + (size_t)p0 * 4672, d_dist, (size_t)n * 4672 * 4, hipMemcpyDeviceToHost));
-        if (legal_idx) HIPOK(hipMemcpy(legal_idx + (size_t)p0 * 224, d_li, (size_t)n * 224 * 2, hipMemcpyDeviceToHost));
-        if (n_legal) HIPOK(hipMemcpy(n_legal + p0, d_nl, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIPOK(hipMemcpy(flags.data(), d_flags, (size_t)n * 4, hipMemcpyDeviceToHost));
-        // first failing ply of each game, with the reference's precedence (children first, then the played move)
-        for (uint32_t i = 0; i < n; i++) {
-            const uint32_t g = pgame[p0 + i];
-            if (status[g] != 0) continue;
-            const int ply = (int)plen[p0 + i];
-            if (flags[i] & 1) status[g] = 1000 + ply;
-            else if (flags[i] & 2) status[g] = -(ply + 1);
-        }
-    }
-    dfree({d_moves, d_cmv, d_cn, d_coff, d_start, d_len, d_hist, d_moff});
-    dfree({d_boards, d_meta, d_nl, d_flags, d_out, d_lm, d_li, d_dist});
-    (void)hipEventDestroy(evk[0]);
-    (void)hipEventDestroy(evk[1]);
-    g_encode_ms[0] = kernels_ms;
-    g_encode_ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    return 0;
-}
-
-int sc_encode_steps_last_timing(float* kernels_ms, float* total_ms) {
-    if (kernels_ms) *kernels_ms = g_encode_ms[0];
-    if (total_ms) *total_ms = g_encode_ms[1];
-    return 0;
-}
-
 }  // extern "C"
 
-// ------------------------------------------------------------------ device-resident training tensors
-// sc_encode_steps_device / sc_selfplay_encode_traces (include/sc_engine.h): the kernels of sc_encode_steps, writing into the
-// caller's device buffers on the caller's stream.  Nothing is staged and nothing waits for the device in the steady state.
+// ------------------------------------------------------------------ training tensors
+// libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) for a batch of recorded games; see include/sc_engine.h.
+// One encoder, encode_device_core, writes device buffers on a stream.  sc_encode_steps_device / sc_selfplay_encode_traces hand
+// it the caller's buffers and stream: nothing is staged and nothing waits for the device in the steady state.  sc_encode_steps
+// runs it into staging buffers, slice by slice, and copies out to the caller's host arrays.
 // The scratch of a call lives in a per-device arena that the library keeps and reuses: an event recorded behind each call's
 // work orders the next call after it on the device (hipStreamWaitEvent, whatever its stream); only growing the arena waits
 // on the host, for that previous call, before the old buffer is freed.
@@ -735,22 +613,35 @@ static int encode_device_core(int dev, int n_games, const uint32_t* ply_off, con
         if (p1 == p0) continue;
         scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, d_rows, ring ? ring->p->num_steps : 0,
                        ring ? ring->p->t_move : nullptr, d_moves, d_src, st);
-        scl::replay_group(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st);
+        scl::replay_games(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st);
         for (uint32_t c0 = p0; c0 < p1; c0 += CH) {
             const uint32_t n = std::min(CH, p1 - c0);
-            scl::encode_plies_dev(o.layout, (int)n, d_hist, d_hoff + c0, d_plen + c0,
-                                  o.boards ? static_cast<char*>(o.boards) + (size_t)c0 * 7168 * bsz : nullptr, d_meta, d_lm,
-                                  o.legal_idx ? o.legal_idx + (size_t)c0 * 224 : nullptr, d_nl, st);
-            scl::steps_dist_dev((int)n, d_lm, d_nl, d_moves + c0, ring ? ring->p->t_cmove : d_cmv,
-                                ring ? reinterpret_cast<const uint32_t*>(ring->p->t_cn) : d_cn, ring ? nullptr : d_coff + c0,
-                                ring ? d_src + c0 : nullptr, ring ? ring->p->t_nchild : nullptr, d_pgame + c0, d_plen + c0, apply_mirror,
-                                d_meta, o.layout, o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr,
-                                o.dist ? o.dist + (size_t)c0 * 4672 : nullptr, o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr,
-                                o.n_legal ? o.n_legal + c0 : nullptr, o.status, st);
+            scl::encode_plies(o.layout, (int)n, d_hist, d_hoff + c0, d_plen + c0,
+                              o.boards ? static_cast<char*>(o.boards) + (size_t)c0 * 7168 * bsz : nullptr, d_meta, d_lm,
+                              o.legal_idx ? o.legal_idx + (size_t)c0 * 224 : nullptr, d_nl, st);
+            scl::steps_dist((int)n, d_lm, d_nl, d_moves + c0, ring ? ring->p->t_cmove : d_cmv,
+                            ring ? reinterpret_cast<const uint32_t*>(ring->p->t_cn) : d_cn, ring ? nullptr : d_coff + c0,
+                            ring ? d_src + c0 : nullptr, ring ? ring->p->t_nchild : nullptr, d_pgame + c0, d_plen + c0, apply_mirror,
+                            d_meta, o.layout, o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr,
+                            o.dist ? o.dist + (size_t)c0 * 4672 : nullptr, o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr,
+                            o.n_legal ? o.n_legal + c0 : nullptr, o.status, st);
         }
     }
     scl::status_final(n_games, o.status, st);
     HIPOK(hipGetLastError());
+    return 0;
+}
+
+// the host trace arrays of sc_encode_steps / sc_encode_steps_device
+static int check_traces(int n_games, const uint32_t* move_off, const uint32_t* child_off) {
+    uint32_t maxlen = 0;
+    for (int g = 0; g < n_games; g++) {
+        if (move_off[g + 1] < move_off[g]) return fail("move_off not monotonic");
+        maxlen = std::max(maxlen, move_off[g + 1] - move_off[g]);
+    }
+    if (maxlen > 4000) return fail("move list too long");
+    for (uint32_t p = 0; p < move_off[n_games]; p++)
+        if (child_off[p + 1] < child_off[p] || child_off[p + 1] - child_off[p] > 224) return fail("child_off: more than 224 children or not monotonic");
     return 0;
 }
 
@@ -772,19 +663,107 @@ int sc_encode_steps_device(sc_engine* e, int device_id, int n_games, const uint1
         if (rc) return rc;
     }
     if (n_games == 0) return 0;
-    uint32_t maxlen = 0;
-    for (int g = 0; g < n_games; g++) {
-        if (move_off[g + 1] < move_off[g]) return fail("move_off not monotonic");
-        maxlen = std::max(maxlen, move_off[g + 1] - move_off[g]);
+    {
+        const int rc = check_traces(n_games, move_off, child_off);
+        if (rc) return rc;
     }
-    if (maxlen > 4000) return fail("move list too long");
     const uint32_t total = move_off[n_games];
     if (total && !moves) return fail("bad argument");
-    for (uint32_t p = 0; p < total; p++)
-        if (child_off[p + 1] < child_off[p] || child_off[p + 1] - child_off[p] > 224) return fail("child_off: more than 224 children or not monotonic");
     if (child_off[total] && (!child_mv || !child_n)) return fail("bad argument");
     return encode_device_core(dev, n_games, move_off, moves, child_mv, child_n, child_off, nullptr, apply_mirror, o,
                               static_cast<hipStream_t>(stream));
+}
+
+namespace {
+struct EncStaging {   // sc_encode_steps's device staging and timing events: released on every path out of the call
+    char* base = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~EncStaging() {
+        dfree({base});
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+}  // namespace
+
+// the host-pointer form: encode_device_core (layout 0) into staging, slice by slice, and out through PCIe
+int sc_encode_steps(sc_engine* e, int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off,
+                    const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int8_t* boards,
+                    int32_t* meta, float* dist, uint16_t* legal_idx, int32_t* n_legal, int32_t* status) {
+    if (n_games < 0 || !move_off || !child_off || !status) return fail("bad argument");
+    if (n_games == 0) return 0;
+    const auto t_call = std::chrono::steady_clock::now();
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
+    const int dev = e ? e->device : device_id;
+    HIPOK(hipSetDevice(dev));
+    std::fill(status, status + n_games, 0);
+    {
+        const int rc = check_traces(n_games, move_off, child_off);
+        if (rc) return rc;
+    }
+    const uint32_t total = move_off[n_games];
+    if (total == 0) return 0;
+    // a slice: consecutive whole games of at most CH plies together (one game alone has at most 4000), which bounds the staging
+    // at CH * 26 KB when every output is asked for
+    const uint32_t CH = 8192, cap = std::min(CH, total);
+    size_t bytes = 0;
+    auto take = [&](const void* wanted, size_t n) {   // (an output the caller does not ask for is not staged)
+        const size_t o = bytes;
+        if (wanted) bytes += (n + 255) & ~(size_t)255;
+        return o;
+    };
+    const size_t o_status = take(status, (size_t)n_games * 4), o_boards = take(boards, (size_t)cap * 7168), o_meta = take(meta, (size_t)cap * 28);
+    const size_t o_dist = take(dist, (size_t)cap * 4672 * 4), o_li = take(legal_idx, (size_t)cap * 448), o_nl = take(n_legal, (size_t)cap * 4);
+    EncStaging S;
+    HIPOK(hipMalloc(reinterpret_cast<void**>(&S.base), bytes));
+    HIPOK(hipEventCreate(&S.ev[0]));
+    HIPOK(hipEventCreate(&S.ev[1]));
+    int32_t* d_status = reinterpret_cast<int32_t*>(S.base + o_status);
+    const hipStream_t st = e ? e->stream : nullptr;
+    std::vector<uint32_t> moff, coff;   // the slice's offsets, rebased; uploaded asynchronously: alive until the slice's synchronisation
+    float kernels_ms = 0.f;
+    for (int g0 = 0, g1; g0 < n_games; g0 = g1) {
+        const uint32_t p0 = move_off[g0], c0 = child_off[p0];
+        for (g1 = g0 + 1; g1 < n_games && move_off[g1 + 1] - p0 <= CH; g1++) {}
+        const uint32_t n = move_off[g1] - p0;
+        moff.assign(move_off + g0, move_off + g1 + 1);
+        coff.assign(child_off + p0, child_off + p0 + n + 1);
+        for (uint32_t& x : moff) x -= p0;
+        for (uint32_t& x : coff) x -= c0;
+        const DevEncodeOut o{0,
+                             boards ? S.base + o_boards : nullptr,
+                             meta ? S.base + o_meta : nullptr,
+                             dist ? reinterpret_cast<float*>(S.base + o_dist) : nullptr,
+                             nullptr,
+                             legal_idx ? reinterpret_cast<uint16_t*>(S.base + o_li) : nullptr,
+                             n_legal ? reinterpret_cast<int32_t*>(S.base + o_nl) : nullptr,
+                             d_status + g0};
+        HIPOK(hipEventRecord(S.ev[0], st));
+        const int rc = encode_device_core(dev, g1 - g0, moff.data(), moves + p0, child_mv + c0, child_n + c0, coff.data(), nullptr,
+                                          apply_mirror, o, st);
+        if (rc) return rc;
+        HIPOK(hipEventRecord(S.ev[1], st));
+        HIPOK(hipStreamSynchronize(st));
+        float ms = 0.f;
+        HIPOK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        kernels_ms += ms;
+        if (boards) HIPOK(hipMemcpy(boards + (size_t)p0 * 7168, o.boards, (size_t)n * 7168, hipMemcpyDeviceToHost));
+        if (meta) HIPOK(hipMemcpy(meta + (size_t)p0 * 7, o.meta, (size_t)n * 28, hipMemcpyDeviceToHost));
+        if (dist) HIPOK(hipMemcpy(dist + (size_t)p0 * 4672, o.dist, (size_t)n * 4672 * 4, hipMemcpyDeviceToHost));
+        if (legal_idx) HIPOK(hipMemcpy(legal_idx + (size_t)p0 * 224, o.legal_idx, (size_t)n * 448, hipMemcpyDeviceToHost));
+        if (n_legal) HIPOK(hipMemcpy(n_legal + p0, o.n_legal, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    HIPOK(hipMemcpy(status, d_status, (size_t)n_games * 4, hipMemcpyDeviceToHost));
+    g_encode_ms[0] = kernels_ms;
+    g_encode_ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return 0;
+}
+
+int sc_encode_steps_last_timing(float* kernels_ms, float* total_ms) {
+    if (kernels_ms) *kernels_ms = g_encode_ms[0];
+    if (total_ms) *total_ms = g_encode_ms[1];
+    return 0;
 }
 
 }  // extern "C"

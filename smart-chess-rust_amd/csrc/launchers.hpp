@@ -15,27 +15,20 @@ void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int 
 void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
                       int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
                       int32_t* outcome, hipStream_t s);
-// (all plies of all games: d_hoff / d_plen = record offset of the ply's game and moves played before the ply; d_moves[q] = ply q's move)
-void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
-                  const uint32_t* d_hoff, const uint32_t* d_plen, hipStream_t s);
-void encode_plies(int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, int8_t* boards, int32_t* meta,
-                  uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s);
-void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal, const uint16_t* next_mv, const uint16_t* child_mv,
-                const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int32_t* meta, float* dist, int32_t* flags,
-                hipStream_t s);
-// device-resident training tensors (sc_encode_steps_device / sc_selfplay_encode_traces): see mcts_kernels.hpp
+// training tensors (sc_encode_steps, sc_encode_steps_device, sc_selfplay_encode_traces): see mcts_kernels.hpp
 void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
                const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s);
-// replay_games for a group of games whose plies start at ply p0 of the batch: d_move_off holds absolute offsets into d_moves,
-// d_hoff / d_plen / d_ply_moves are the group's plies (d_ply_moves = d_moves + p0)
-void replay_group(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
+// the walk of a group of games whose plies start at ply p0 of the batch: d_move_off holds absolute offsets into d_moves,
+// d_hoff / d_plen / d_ply_moves are the group's plies (record offset of the ply's game, moves played before the ply, the ply's
+// move = d_moves + p0)
+void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
                   const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s);
-void encode_plies_dev(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
-                      int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s);
-void steps_dist_dev(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
-                    const uint32_t* child_n, const uint32_t* child_off, const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
-                    const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
-                    float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s);
+void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
+                  int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s);
+void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
+                const uint32_t* child_n, const uint32_t* child_off, const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
+                const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
+                float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s);
 void status_final(int n, int32_t* status, hipStream_t s);
 // nn_kernels.hip
 const char* nn_init();  // sets kernel attributes; returns error text or nullptr

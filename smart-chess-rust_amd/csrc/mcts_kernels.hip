@@ -20,52 +20,33 @@ void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move
     hipLaunchKernelGGL(sc::k_encode_positions, dim3(n_pos), dim3(64), 0, s, n_pos, d_moves, d_move_off, d_move_len, d_hist, hist_cap,
                        boards, meta, legal_mv, legal_idx, n_legal, outcome);
 }
-void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
-                  const uint32_t* d_hoff, const uint32_t* d_plen, hipStream_t s) {
-    if (n_games <= 0 || n_plies <= 0) return;
-    hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap);
-    hipLaunchKernelGGL(sc::k_ply_keys, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen, d_moves);
-    hipLaunchKernelGGL(sc::k_ply_rep, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen);
-}
-void encode_plies(int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, int8_t* boards, int32_t* meta,
-                  uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_encode_plies, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
-}
-void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal, const uint16_t* next_mv, const uint16_t* child_mv,
-                const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int32_t* meta, float* dist, int32_t* flags,
-                hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_steps_dist, dim3(n), dim3(64), 0, s, n, legal_mv, n_legal, next_mv, child_mv, child_n, child_off,
-                       apply_mirror, meta, dist, flags);
-}
 void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
                const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s) {
     if (n <= 0) return;
     hipLaunchKernelGGL(sc::k_ply_index, dim3((n + 255) / 256), dim3(256), 0, s, n, g0, ng, d_ply_off, hist_cap, d_hoff, d_plen, d_pgame,
                        d_rows, num_steps, t_move, d_moves, d_src);
 }
-void replay_group(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
+void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
                   const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s) {
     if (n_games <= 0 || n_plies <= 0) return;
     hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap);
     hipLaunchKernelGGL(sc::k_ply_keys, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen, d_ply_moves);
     hipLaunchKernelGGL(sc::k_ply_rep, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen);
 }
-void encode_plies_dev(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
-                      int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s) {
+void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
+                  int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s) {
     if (n <= 0) return;
     if (layout == 1)
-        hipLaunchKernelGGL(sc::k_encode_plies_dev<1>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
+        hipLaunchKernelGGL(sc::k_encode_plies<1>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
     else
-        hipLaunchKernelGGL(sc::k_encode_plies_dev<0>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
+        hipLaunchKernelGGL(sc::k_encode_plies<0>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
 }
-void steps_dist_dev(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
-                    const uint32_t* child_n, const uint32_t* child_off, const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
-                    const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
-                    float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s) {
+void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
+                const uint32_t* child_n, const uint32_t* child_off, const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
+                const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
+                float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_steps_dist_dev, dim3(n), dim3(64), 0, s, n, legal_mv, n_legal_s, next_mv, child_mv, child_n, child_off, src,
+    hipLaunchKernelGGL(sc::k_steps_dist, dim3(n), dim3(64), 0, s, n, legal_mv, n_legal_s, next_mv, child_mv, child_n, child_off, src,
                        nchild, pgame, plen, apply_mirror, meta_s, layout, meta_out, dist, dist_legal, n_legal_out, status);
 }
 void status_final(int n, int32_t* status, hipStream_t s) {

@@ -1383,108 +1383,23 @@ __global__ __launch_bounds__(64) void k_ply_rep(int n, Position* hist_all, const
     // (a byte store beside the F_IRREV bit other waves' scans read: that bit does not change here)
     if (lane == 0 && rf) hist[i].flags = (uint8_t)((hist[i].flags & F_IRREV) | rf);
 }
-
-// one wave per ply: the position BEFORE the ply's move from the game's records -- legal moves (python-chess order), action
-// indices, planes, meta.  hoff[p]: record index of the game's start position, plen[p]: moves played before the ply.
-__global__ __launch_bounds__(64) void k_encode_plies(int n, const Position* hist_all, const uint32_t* hoff, const uint32_t* plen, int8_t* boards,
-                                                     int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    if (g >= n) return;
-    __shared__ __attribute__((aligned(16))) int8_t s_stage[7168];
-    __shared__ move_t s_moves[MAXC];
-    __shared__ int32_t s_meta[8];
-    __shared__ Position s_hist[8];
-    const HistChain hc{hist_all + hoff[g]};
-    const int played = (int)plen[g];
-    stage_history(hc, played, lane, s_hist);
-    __syncthreads();
-    const Position cur = s_hist[0];
-    int nl = 0;
-    gen_legal_wave(cur, s_moves, lane, nl);
-    __syncthreads();
-    for (int i = lane; i < MAXC; i += 64) {   // whole rows: the entries past n_legal are zero (include/sc_engine.h)
-        legal_mv[(size_t)g * MAXC + i] = i < nl ? s_moves[i] : (move_t)0;
-        legal_idx[(size_t)g * MAXC + i] = i < nl ? (uint16_t)move_index(s_moves[i], cur.turn) : (uint16_t)0;
-    }
-    if (lane == 0) n_legal[g] = nl;
-    encode_wave(s_hist, played < 7 ? played + 1 : 8, lane, s_stage, boards + (size_t)g * 7168, s_meta);
-    __syncthreads();
-    if (lane < 7) meta[(size_t)g * 7 + lane] = s_meta[lane];
-}
 #endif
 
 // ------------------------------------------------------------------ training tensors
-// Per ply of a recorded game: libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) on top of
-// k_encode_positions (planes / meta / legal moves of the position BEFORE the ply's move):
-//   * checks the reference's two panics: the searched children must be exactly the legal moves, the played move
-//     must be legal -> flags[g] bit 0 / bit 1;
-//   * dist[index(move)] = count / (sum + 1e-5), index by the REAL mover (lib.rs:85-92, 105-113);
-//   * apply_mirror: the planes and dist do not change (the stored boards are rotated once at push and once more at
-//     view, lib.rs:80-98 + chess.rs:827-842 -- asserted on the oracle's literal restatement); meta becomes that of
-//     Board::rotate(): [!turn, fullmove + (turn==White), K(opp), Q(opp), K(mover), Q(mover), halfmove].
-// One wavefront per ply; HBM-bound writer (18.7 KB of dist per ply).
+// Per ply of a recorded game: libsmartchess.chess_encode_steps (reference src/lib.rs:46-128), for sc_encode_steps (through
+// staging), sc_encode_steps_device and sc_selfplay_encode_traces (straight into the caller's device buffers).  After the walk
+// above, one wavefront per ply, two kernels:
+//   k_encode_plies<LAYOUT>: legal moves (python-chess order), action indices, planes and meta of the position BEFORE the ply's
+//     move, from the game's records.  LAYOUT 0 is the reference's int8 [8][8][112], LAYOUT 1 the trainer's float32 [112][8][8];
+//   k_steps_dist: the reference's two panics -- the searched children must be exactly the legal moves, the played move must be
+//     legal -- and dist[index(move)] = count / (sum + 1e-5), index by the REAL mover (lib.rs:85-92, 105-113); HBM-bound
+//     writer (18.7 KB of dist per ply).  The children come as CSR arrays or as the trace ring's padded rows.
+//   apply_mirror: the planes and dist do not change (the stored boards are rotated once at push and once more at view,
+//     lib.rs:80-98 + chess.rs:827-842 -- asserted on the oracle's literal restatement); meta becomes that of Board::rotate():
+//     [!turn, fullmove + (turn==White), K(opp), Q(opp), K(mover), Q(mover), halfmove].
+// Every output but status is optional (nullptr).  A game's status is reduced on the device: k_steps_dist folds each failing
+// ply into status[game] by an atomic min, k_status_final turns the result into the codes of include/sc_engine.h.
 #ifndef SC_NO_KERNELS
-__global__ __launch_bounds__(64) void k_steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal, const uint16_t* next_mv,
-                                                   const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off,
-                                                   int apply_mirror, int32_t* meta, float* dist, int32_t* flags) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    if (g >= n) return;
-    __shared__ move_t s_lm[MAXC];
-    __shared__ int s_hit[MAXC];
-    const int nl = n_legal[g];
-    const uint32_t c0 = child_off[g];
-    const int nc = (int)(child_off[g + 1] - c0);
-    const int turn = meta[(size_t)g * 7];
-    float4* dz = reinterpret_cast<float4*>(dist + (size_t)g * 4672);
-    for (int i = lane; i < 4672 / 4; i += 64) dz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = lane; i < MAXC; i += 64) {
-        s_lm[i] = i < nl ? legal_mv[(size_t)g * MAXC + i] : (move_t)0;
-        s_hit[i] = 0;
-    }
-    __syncthreads();
-    const move_t nx = next_mv[g];
-    int has_next = 0, bad = 0;
-    uint32_t sum = 0;
-    for (int i = lane; i < nl; i += 64) has_next |= (s_lm[i] == nx) ? 1 : 0;
-    for (int i = lane; i < nc; i += 64) {
-        const move_t m = child_mv[c0 + i];
-        int k = -1;
-        for (int j = 0; j < nl; j++)
-            if (s_lm[j] == m) k = j;
-        if (k < 0) bad = 1;
-        else s_hit[k] = 1;     // benign same-value race between duplicates
-        sum += child_n[c0 + i];
-    }
-    __syncthreads();
-    for (int i = lane; i < nl; i += 64) bad |= s_hit[i] ? 0 : 1;   // with nc == nl this also catches duplicate children
-    bad |= (nc != nl) ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);   // u32 wrap-around, as the reference's u32 sum in release mode
-    const float den = (float)sum + 1e-5f;
-    for (int i = lane; i < nc; i += 64) {
-        const int idx = move_index(child_mv[c0 + i], turn);
-        if (idx >= 0) dist[(size_t)g * 4672 + idx] = (float)child_n[c0 + i] / den;
-    }
-    const bool any_bad = __ballot(bad) != 0, any_next = __ballot(has_next) != 0;
-    if (lane == 0) {
-        flags[g] = (any_bad ? 1 : 0) | (any_next ? 0 : 2);
-        if (apply_mirror) {
-            int32_t* m = meta + (size_t)g * 7;
-            const int32_t t = m[0], k0 = m[2], q0 = m[3], k1 = m[4], q1 = m[5];
-            m[0] = 1 - t;
-            m[1] = m[1] + (t == 1 ? 1 : 0);
-            m[2] = k1;
-            m[3] = q1;
-            m[4] = k0;
-            m[5] = q0;
-        }
-    }
-}
-
-// ------------------------------------------------------------------ device-resident training tensors
-// sc_encode_steps_device / sc_selfplay_encode_traces: the same per-ply work as k_encode_plies + k_steps_dist, written
-// straight into the caller's device buffers (no staging), in the reference layout or the trainer's (float32, channel-major),
-// with the status reduced on the device.
-
 // per ply q of the games [g0, g0 + ng) (plies ply_off[g0] + [0, n)): its game, its index in the game and the record offset of
 // its game in the group's history buffer (group-local: ng * hist_cap records).  From the trace ring (t_move != nullptr) also
 // the ply's move and its ring index row * num_steps + ply, so that the replay reads a packed move list.  One thread per ply.
@@ -1511,14 +1426,15 @@ __global__ __launch_bounds__(256) void k_ply_index(int n, int g0, int ng, const 
     }
 }
 
-// k_encode_plies with optional outputs and two plane layouts.  LAYOUT 0: int8 [n][8][8][112] as encode_wave writes it;
-// LAYOUT 1: float32 [n][112][8][8] -- lane = square, one plane per store, so each of the 112 stores of a ply is one
-// contiguous 256-byte row.  meta (int32, stride 7), legal_mv and n_legal are the call's scratch (k_steps_dist_dev reads them);
-// boards and legal_idx are the caller's buffers or nullptr.
+// hoff[p]: record index of the game's start position, plen[p]: moves played before the ply.  LAYOUT 0: int8 [n][8][8][112] as
+// encode_wave writes it; LAYOUT 1: float32 [n][112][8][8] -- lane = square, one plane per store, so each of the 112 stores of
+// a ply is one contiguous 256-byte row.  meta (int32, stride 7), legal_mv and n_legal are the call's scratch (k_steps_dist
+// reads them); boards and legal_idx are the caller's buffers or nullptr.  Whole rows are written: the entries past n_legal are
+// zero (include/sc_engine.h).
 template <int LAYOUT>
-__global__ __launch_bounds__(64) void k_encode_plies_dev(int n, const Position* hist_all, const uint32_t* hoff, const uint32_t* plen,
-                                                         void* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx,
-                                                         int32_t* n_legal) {
+__global__ __launch_bounds__(64) void k_encode_plies(int n, const Position* hist_all, const uint32_t* hoff, const uint32_t* plen,
+                                                     void* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx,
+                                                     int32_t* n_legal) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n) return;
     __shared__ __attribute__((aligned(16))) int8_t s_stage[7168];
@@ -1560,19 +1476,18 @@ __global__ __launch_bounds__(64) void k_encode_plies_dev(int n, const Position* 
     if (lane < 7) meta[(size_t)g * 7 + lane] = s_meta[lane];
 }
 
-// k_steps_dist with optional outputs: the legal-set check, the u32 visit sum and the division are k_steps_dist's, line for
-// line.  Children come either as CSR (child_off[q] .. child_off[q+1] into child_mv / child_n) or, with src != nullptr, as the
+// Children come either as CSR (child_off[q] .. child_off[q+1] into child_mv / child_n) or, with src != nullptr, as the
 // trace ring's padded rows (ply q: row src[q] of MAXC entries, nchild[src[q]] of them).  Writes the (mirrored) meta in the
 // requested layout, the dense dist row, the legal-move row dist_legal[q][i] = share of legal move i (0 past n_legal), n_legal,
 // and folds the ply's failure into status[game] with an atomic min over the key 2 * ply + kind (kind 0: children are not the
 // legal moves, kind 1: the played move is illegal) -- the first failing ply wins, a children mismatch beats an illegal move
-// at the same ply; k_status_final turns the keys into sc_encode_steps's codes.
-__global__ __launch_bounds__(64) void k_steps_dist_dev(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv,
-                                                       const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off,
-                                                       const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
-                                                       const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout,
-                                                       void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out,
-                                                       int32_t* status) {
+// at the same ply (the reference's precedence); k_status_final turns the keys into sc_encode_steps's codes.
+__global__ __launch_bounds__(64) void k_steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv,
+                                                   const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off,
+                                                   const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
+                                                   const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout,
+                                                   void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out,
+                                                   int32_t* status) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n) return;
     __shared__ move_t s_lm[MAXC];
@@ -1637,7 +1552,7 @@ __global__ __launch_bounds__(64) void k_steps_dist_dev(int n, const uint16_t* le
     if (meta_out && lane < 7) {
         const int32_t* m = meta_s + (size_t)g * 7;
         int32_t v = m[lane];
-        if (apply_mirror) {   // Board::rotate() (k_steps_dist)
+        if (apply_mirror) {   // Board::rotate()
             const int32_t t = m[0];
             v = lane == 0 ? 1 - t : lane == 1 ? m[1] + (t == 1 ? 1 : 0) : lane == 2 ? m[4] : lane == 3 ? m[5] : lane == 4 ? m[2] : lane == 5 ? m[3] : v;
         }

@@ -245,16 +245,8 @@ def encode_steps_batch(games, apply_mirror=False, device=0, engine=None):
     `steps` argument of libsmartchess.chess_encode_steps (reference src/lib.rs:46-50), one per game.
     -> dict(boards int8[P,8,8,112], meta int32[P,7], dist f32[P,4672], move_indices [P lists], ply_off[n+1], status[n])"""
     L = lib()
-    mv = lambda m: uci_move(m) if isinstance(m, str) else int(m)
-    n = len(games)
-    off = np.zeros(n + 1, np.uint32)
-    off[1:] = np.cumsum([len(g) for g in games])
-    P = int(off[n])
-    flat = np.asarray([mv(s[0]) for g in games for s in g] or [0], np.uint16)
-    coff = np.zeros(P + 1, np.uint32)
-    coff[1:] = np.cumsum([len(s[1]) for g in games for s in g])
-    cm = np.asarray([mv(c[0]) for g in games for s in g for c in s[1]] or [0], np.uint16)
-    cn = np.asarray([int(c[1]) for g in games for s in g for c in s[1]] or [0], np.uint32)
+    flat, off, cm, cn, coff = pack_steps(games)
+    n, P = len(games), int(off[-1])
     boards = np.zeros((max(P, 1), 8, 8, 112), np.int8)
     meta = np.zeros((max(P, 1), 7), np.int32)
     dist = np.zeros((max(P, 1), 4672), np.float32)

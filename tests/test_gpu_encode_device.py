@@ -1,6 +1,10 @@
-"""Device-resident training tensors on the GPU (-m gpu): sc_encode_steps_device and sc_selfplay_encode_traces against the
-host path (sc_encode_steps through encode_steps_batch), bit for bit.  Device buffers come from hipMalloc on the HIP runtime
-libsc_engine.so uses (ctypes): this file does not import torch -- the torch interop runs in a child process of its own."""
+"""Device-resident training tensors on the GPU (-m gpu): sc_encode_steps_device and sc_selfplay_encode_traces next to the host
+entry point (sc_encode_steps through encode_steps_batch), bit for bit.  The host entry point runs the same encoder into staging
+buffers, so that comparison checks what differs between the entry points -- the host path's slices, staging and copy-out, stream
+use, the ring as a source, the layouts, the grouping by history records -- and does not pin the kernels: the oracle does, on
+sampled games of the device result (assert_games_equal_oracle) and of the host result.  Device buffers come from hipMalloc on
+the HIP runtime libsc_engine.so uses (ctypes): this file does not import torch -- the torch interop runs in a child process of
+its own."""
 import ctypes as C
 import json
 import os
@@ -118,9 +122,23 @@ def _random_steps(orc, moves, rnd):
     return steps
 
 
+def assert_games_equal_oracle(orc, r, steps, sample, mirror=False):
+    """the games `sample` of r (a device result in the reference layout, or encode_steps_batch's) == orc.encode_steps, bit for bit"""
+    off = r["ply_off"]
+    for gi in sample:
+        rc, b, m, d, idx = orc.encode_steps(steps[gi], mirror)
+        a, e = int(off[gi]), int(off[gi + 1])
+        assert rc == 0 and e - a == len(steps[gi])
+        assert np.array_equal(r["boards"][a:e], b) and np.array_equal(r["meta"][a:e], m), gi
+        assert np.array_equal(r["dist"][a:e].view(np.uint32), d.view(np.uint32)), gi
+        for p in range(a, e):
+            got = r["move_indices"][p] if "move_indices" in r else r["legal_idx"][p, :int(r["n_legal"][p])]
+            assert np.array_equal(np.asarray(got, np.int32), idx[p - a]), (gi, p)
+
+
 def assert_same_as_host(d, h, skip=None):
-    """device result d (reference layout) == encode_steps_batch's h, bit for bit; skip[g] = first failing ply of game g
-    (outputs at and after it are unspecified, include/sc_engine.h)"""
+    """device result d (reference layout) == encode_steps_batch's h, bit for bit: the two entry points around the one encoder
+    agree.  skip[g] = first failing ply of game g (outputs at and after it are unspecified, include/sc_engine.h)"""
     assert np.array_equal(d["status"], h["status"])
     off = h["ply_off"]
     keep = np.ones(int(off[-1]), bool)
@@ -151,6 +169,7 @@ def test_device_matches_host_path(scamd, orc, dev, mirror):
     d = run_device(scamd, dev, steps, mirror)
     assert (h["status"] == 0).all()
     assert_same_as_host(d, h)
+    assert_games_equal_oracle(orc, d, steps, (0, len(steps) // 2, len(steps) - 1), mirror)
 
 
 def test_device_errors_like_the_host_path(scamd, orc, dev):
@@ -168,9 +187,7 @@ def test_device_errors_like_the_host_path(scamd, orc, dev):
         assert_same_as_host(d, scamd.encode_steps_batch(cases, mirror), skip=_first_bad_ply(h["status"]))
 
 
-def test_long_game_among_many_short_ones(scamd, orc, dev):
-    """a 700-ply game (repetition scan over > 64 plies) among 1 500 three-ply games: the game records exceed the per-call
-    budget (1 501 x 702 > 2^20 records), so the games are encoded in groups -- results equal the host path"""
+def _long_and_short(orc):
     cyc = ["g1f3", "g8f6", "f3g1", "f6g8", "b1c3", "b8c6", "c3b1", "c6b8"]
     games = []
     for moves in ([cyc[i % 8] for i in range(700)], ["e2e4", "e7e5", "g1f3"]):
@@ -180,13 +197,53 @@ def test_long_game_among_many_short_ones(scamd, orc, dev):
             steps.append((m, [(orc.uci(x), 1 + (k % 3)) for k, x in enumerate(st.legal_moves())]))
             st.push(m)
         games.append(steps)
+    return games
+
+
+def _slices(ply_off, cap=8192):
+    """the host path's slices (first game, one past the last): consecutive whole games of at most `cap` plies together"""
+    out, g0, n = [], 0, len(ply_off) - 1
+    while g0 < n:
+        g1 = g0 + 1
+        while g1 < n and int(ply_off[g1 + 1]) - int(ply_off[g0]) <= cap:
+            g1 += 1
+        out.append((g0, g1))
+        g0 = g1
+    return out
+
+
+def test_long_game_among_many_short_ones(scamd, orc, dev):
+    """a 700-ply game (repetition scan over > 64 plies) among 1 500 three-ply games: the game records exceed the per-call
+    budget (1 501 x 702 > 2^20 records), so the games are encoded in groups -- results equal the host path"""
+    games = _long_and_short(orc)
     batch = [games[1]] * 750 + [games[0]] + [games[1]] * 750
     h = scamd.encode_steps_batch(batch)
     d = run_device(scamd, dev, batch)
     assert (d["status"] == 0).all()
     assert_same_as_host(d, h)
+    assert_games_equal_oracle(orc, d, batch, (0, 750, 1500))
     p = int(h["ply_off"][750]) + 600
     assert d["boards"][p][:, :, 12].any() and d["boards"][p][:, :, 13].any()
+
+
+def test_host_slices_and_record_groups_differ(scamd, orc):
+    """the host path's slices (plies: staging) and the encoder's groups (history records) cut a batch in different places.
+    One slice of several groups: the 700-ply game first, 1 500 three-ply games behind it.  Several slices of one group each:
+    more than 8 192 plies with the 700-ply game in the middle.  The first and last game of every slice, the long game and a
+    middle game equal the oracle"""
+    long_game, short = _long_and_short(orc)
+    batch = [long_game] + [short] * 1500
+    r = scamd.encode_steps_batch(batch)
+    assert (r["status"] == 0).all() and len(_slices(r["ply_off"])) == 1 and 1501 * 702 > 1 << 20
+    assert_games_equal_oracle(orc, r, batch, (0, 1, 750, 1500))
+    rnd = random.Random(2)
+    base = [g for g, _ in random_games(orc, 30, 150, seed=5) if len(g) >= 40]
+    steps = [_random_steps(orc, g, rnd) for g in (base * 5)[:110]]
+    steps.insert(55, long_game)
+    r = scamd.encode_steps_batch(steps)
+    sl = _slices(r["ply_off"])
+    assert (r["status"] == 0).all() and int(r["ply_off"][-1]) > 8192 and len(sl) >= 2
+    assert_games_equal_oracle(orc, r, steps, sorted({55, 20} | {g for a, b in sl for g in (a, b - 1)}))
 
 
 def test_more_plies_than_one_host_chunk(scamd, orc, dev):

@@ -1,5 +1,6 @@
 """developer tool: the trace -> training-tensor path (sc_encode_steps) on 256 quick self-play games, for
-`rocprofv3 --kernel-trace --stats -- python3 tools/encode_steps_profile.py` (per-kernel time of k_encode_positions / k_steps_dist)"""
+`rocprofv3 --kernel-trace --stats -- python3 tools/encode_steps_profile.py` (per-kernel time of k_ply_index, k_replay_raw,
+k_ply_keys, k_ply_rep, k_encode_plies, k_steps_dist, k_status_final)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
