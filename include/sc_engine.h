@@ -167,6 +167,55 @@ int sc_encode_steps_device(sc_engine* engine_or_null, int device_id, int n_games
                            void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
                            int32_t* n_legal, int32_t* status);
 
+/* ------------------------------------------------------------------ network on device tensors: forward, losses, agreement */
+/* sc_forward_batch on DEVICE pointers: boards int8 [n][8][8][112] and meta int32 [n][7] as layout 0 of sc_encode_steps_device
+ * leaves them, logp float [n][4672] (may be NULL) and value float [n] in device memory of the engine's GPU.  The same kernels as
+ * sc_forward_batch: the outputs are bit-identical to it.  Every pointer is checked (hipPointerGetAttributes): host memory or
+ * memory of another GPU returns -1.
+ * Stream contract: `stream` is a hipStream_t (NULL: the default stream).  The call returns once the work is enqueued on it,
+ * ordered after the earlier work of `stream` and of the engine, and does not synchronise; read the outputs after the stream's
+ * work.  Only growing the engine's scratch (value-head features and split-K partials of up to 8 192 positions: longer inputs are
+ * processed in slices of that many) waits on the host, for the engine's earlier work.  Later calls on the engine wait on the device
+ * for this one.  As everywhere, one host thread drives an engine at a time. */
+int sc_forward_device(sc_engine*, int n, const int8_t* boards, const int32_t* meta, void* stream, float* logp, float* value);
+
+/* A network judged on recorded search results (the reference's scripts/train.py validation_step: compute_loss1, compute_loss2,
+ * and training_step's pi_entropy), on the tensors one sc_encode_steps_device / sc_selfplay_encode_traces call with layout 0
+ * leaves in device memory.  Inputs, device pointers (P = n positions): boards, meta as sc_forward_device; the visit shares in
+ * exactly ONE of two forms -- dist float [P][4672] (16-byte aligned), or dist_legal float [P][SC_MAX_MOVES] + legal_idx uint16
+ * [P][SC_MAX_MOVES] + n_legal int32 [P], of which only entries i < n_legal[p] are read (the padding points at action 0 with share
+ * 0; 0 * logp is never formed); outcome float [P]: White's result of the position's game.  The other form's pointers are NULL;
+ * both forms, or neither, return -1.
+ * Outputs, device pointers, each may be NULL, float [P]:
+ *   ce[p]    = -sum dist * logp over the entries with a non-zero share   (compute_loss1 before the division by the batch size)
+ *   se[p]    = (value[p] - outcome[p])^2                                 (compute_loss2 before the mean; both White-relative)
+ *   ent[p]   = -sum_a exp(logp[a]) * logp[a] over all 4672 actions       (pi_entropy before the mean)
+ *   value[p] = the network's value
+ *   summary  double [5]: [0] P, [1] mean ce (= loss1), [2] mean se (= loss2), [3] mean ent (= pi_entropy), [4] the number of
+ *            positions whose ce, se or ent is not finite.  Those positions are counted and left in: the means are then
+ *            non-finite too, as torch's would be.  P = 0: five zeros.
+ * n_legal[p] outside 0..218, or an action index >= 4672 among a position's legal moves, is found on the DEVICE (the call does not
+ * read device memory on the host): nothing is read through it, ce[p] is NaN and the position is counted in summary[4].
+ * Every sum over a row is a fixed tree 13 additions deep (score_kernels.hip); exp is expf.  A position's results depend on its
+ * own rows only, not on P or on its place among the positions; the summary is reduced in double precision in a fixed order, without
+ * atomics: identical calls give identical bits.
+ * Pointer checks and stream contract as sc_forward_device; the scratch adds the log-probability rows of one slice of 8 192
+ * positions (153 MB) and, for per-position outputs passed as NULL, 12 bytes per position. */
+int sc_score_positions(sc_engine*, int n, const int8_t* boards, const int32_t* meta, const float* dist, const float* dist_legal,
+                       const uint16_t* legal_idx, const int32_t* n_legal, const float* outcome, void* stream, float* ce, float* se,
+                       float* ent, float* value, double* summary);
+
+/* Agreement of two networks on the same positions (the reference's scripts/validate_model.py), any pairing of precisions, depths
+ * and widths; both engines on the GPU that holds boards / meta (engines on two devices: -1).  Outputs, device pointers, each may
+ * be NULL:
+ *   tv[p] = 1/2 sum_a |exp(logp_a[p][a]) - exp(logp_b[p][a])|     dv[p] = |value_a[p] - value_b[p]|
+ *   summary double [9]: [0] P, then mean, population standard deviation (numpy's default), max, min of tv: [1..4], and of dv:
+ *   [5..8] (a NaN among the values makes the four figures NaN).  P = 0: nine zeros.
+ * The same engine twice runs one forward pass and compares its rows with themselves.  Arithmetic, pointer checks and stream
+ * contract as sc_score_positions; both engines' later work waits on the device for the call. */
+int sc_compare_engines(sc_engine* a, sc_engine* b, int n, const int8_t* boards, const int32_t* meta, void* stream, float* tv,
+                       float* dv, double* summary);
+
 /* ------------------------------------------------------------------ self-play (L-search) */
 /* SYNTH: integer-hash evaluator for exact search-parity tests; SYNTH_COARSE: the same with 2-bit priors and values from
  * {-0.5, 0, 0.5} (exact PUCT ties between some siblings); SYNTH_UNIFORM: uniform priors, value 0 (every unvisited sibling

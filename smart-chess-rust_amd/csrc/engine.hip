@@ -100,20 +100,48 @@ struct sc_engine {
     // buffers per call cost more than a short search) and the rollout its node pools are sized for
     struct sc_selfplay* search_sp = nullptr;
     int search_rollout_cap = 0;
+    // d_hval / d_vpart have a capacity of their own (hv_cap): the device-pointer entry points (sc_forward_device, sc_score_positions,
+    // sc_compare_engines) run enqueue_forward on the caller's tensors and need only these two, for one slice.  Their other
+    // scratch: the slice's values and log-probability rows (scoring only), and per-position results the caller did not ask for but
+    // the summary needs.  dv_ev orders those calls (any stream) and the engine's stream after each other.
+    int hv_cap = 0;
+    size_t dv_cap = 0;        // capacities in floats
+    float* dv_value = nullptr;
+    size_t dv_logp_cap = 0;
+    float* dv_logp = nullptr;
+    size_t dv_pp_cap = 0;
+    float* dv_pp = nullptr;
+    hipEvent_t dv_ev = nullptr;
 };
 
 static void engine_free_scratch(sc_engine* e) {
     dfree({e->d_boards, e->d_meta, e->d_lidx, e->d_nlegal, e->d_prior});
-    dfree({e->d_value, e->d_logp, e->d_hval, e->d_vpart, e->d_dbg});
+    dfree({e->d_value, e->d_logp, e->d_dbg});
     e->d_boards = nullptr; e->d_meta = nullptr; e->d_lidx = nullptr; e->d_nlegal = nullptr; e->d_prior = nullptr;
-    e->d_value = nullptr; e->d_logp = nullptr; e->d_hval = nullptr; e->d_vpart = nullptr; e->d_dbg = nullptr;
+    e->d_value = nullptr; e->d_logp = nullptr; e->d_dbg = nullptr;
     e->cap = 0;
     dfree({e->d_enc});
     e->d_enc = nullptr;
     e->enc_cap = 0;
 }
+static void engine_free_hv(sc_engine* e) {
+    dfree({e->d_hval, e->d_vpart});
+    e->d_hval = nullptr;
+    e->d_vpart = nullptr;
+    e->hv_cap = 0;
+}
+// value-head features and split-K partials of n positions (enqueue_forward's scratch, whoever calls it)
+static int engine_reserve_hv(sc_engine* e, int n) {
+    if (n <= e->hv_cap) return 0;
+    HIPOK(hipStreamSynchronize(e->stream));
+    engine_free_hv(e);
+    HIPOK(dalloc(&e->d_hval, (size_t)n * 64 * 256));
+    HIPOK(dalloc(&e->d_vpart, (size_t)e->ksplit * n * 128));
+    e->hv_cap = n;
+    return 0;
+}
 static int engine_reserve(sc_engine* e, int n) {
-    if (n <= e->cap) return 0;
+    if (n <= e->cap) return engine_reserve_hv(e, n);
     HIPOK(hipStreamSynchronize(e->stream));
     engine_free_scratch(e);
     int cap = std::max(n, 64);
@@ -124,11 +152,9 @@ static int engine_reserve(sc_engine* e, int n) {
     HIPOK(dalloc(&e->d_prior, (size_t)cap * 224));
     HIPOK(dalloc(&e->d_value, (size_t)cap));
     HIPOK(dalloc(&e->d_logp, (size_t)cap * 4672));
-    HIPOK(dalloc(&e->d_hval, (size_t)cap * 64 * 256));
-    HIPOK(dalloc(&e->d_vpart, (size_t)e->ksplit * cap * 128));
     HIPOK(dalloc(&e->d_dbg, (size_t)cap * 64 * 256));
     e->cap = cap;
-    return 0;
+    return engine_reserve_hv(e, cap);
 }
 
 // enqueue the three network kernels for n positions (device pointers)
@@ -277,6 +303,9 @@ void sc_engine_destroy(sc_engine* e) {
     }
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     engine_free_scratch(e);
+    engine_free_hv(e);
+    dfree({e->dv_value, e->dv_logp, e->dv_pp});
+    if (e->dv_ev) (void)hipEventDestroy(e->dv_ev);
     dfree({e->d_wb});
     dfree({e->d_wf});
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -763,6 +792,239 @@ int sc_encode_steps(sc_engine* e, int device_id, int n_games, const uint16_t* mo
 int sc_encode_steps_last_timing(float* kernels_ms, float* total_ms) {
     if (kernels_ms) *kernels_ms = g_encode_ms[0];
     if (total_ms) *total_ms = g_encode_ms[1];
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ network on device tensors: forward, losses, agreement
+// sc_forward_device / sc_score_positions / sc_compare_engines (include/sc_engine.h).  The positions are cut into slices of
+// SCORE_SLICE (the figure sc_encode_steps uses), so the scratch of a call is bounded whatever its size: enqueue_forward's own
+// 256 MB of value-head features and 256 MB of split-K partials (d_hval / d_vpart, the buffers sc_forward_batch uses: one set per
+// engine) and -- scoring only -- 153 MB of log-probability rows, which the scoring
+// kernels read back while the slice is still in the Infinity Cache.  A position is one workgroup of the tower, one row of
+// value_fc1's tiles and one wavefront of the scoring kernels: its results do not depend on the slice it falls in.
+namespace {
+constexpr int SCORE_SLICE = 8192;
+
+// Work of these calls runs on the CALLER's stream.  begin: the stream waits for the engine's earlier work (host-pointer calls,
+// self-play steps, earlier device calls -- the engine's stream waits for each of those in end).  The scratch is therefore
+// never used by two calls at once, and growing it waits on the host for the engine's stream only.
+struct DevCall {
+    sc_engine* e;
+    hipStream_t st;
+    bool armed = false;
+    int begin() {
+        if (!e->dv_ev) HIPOK(hipEventCreateWithFlags(&e->dv_ev, hipEventDisableTiming));
+        if (st != e->stream) {
+            HIPOK(hipEventRecord(e->dv_ev, e->stream));
+            HIPOK(hipStreamWaitEvent(st, e->dv_ev, 0));
+        }
+        armed = true;
+        return 0;
+    }
+    ~DevCall() {   // on every path out of the call: later work of the engine waits for what was enqueued
+        if (armed && st != e->stream && hipEventRecord(e->dv_ev, st) == hipSuccess) (void)hipStreamWaitEvent(e->stream, e->dv_ev, 0);
+    }
+};
+}  // namespace
+
+static int dev_slice_cap(int n) {
+    int c = 64;
+    while (c < n && c < SCORE_SLICE) c *= 2;
+    return c;
+}
+// one scratch buffer of the device-pointer calls: growing it waits on the host for the engine's earlier work
+static int dev_grow(sc_engine* e, float** buf, size_t* cap, size_t want) {
+    if (want <= *cap) return 0;
+    HIPOK(hipStreamSynchronize(e->stream));
+    dfree({*buf});
+    *buf = nullptr;
+    *cap = 0;
+    HIPOK(dalloc(buf, want));
+    *cap = want;
+    return 0;
+}
+static int dev_reserve(sc_engine* e, int n, bool want_logp, size_t pp_floats) {
+    const size_t cap = (size_t)dev_slice_cap(n);
+    int rc = engine_reserve_hv(e, (int)cap);
+    if (!rc) rc = dev_grow(e, &e->dv_value, &e->dv_cap, cap);
+    if (!rc && want_logp) rc = dev_grow(e, &e->dv_logp, &e->dv_logp_cap, cap * 4672);
+    if (!rc && pp_floats) rc = dev_grow(e, &e->dv_pp, &e->dv_pp_cap, std::max<size_t>(pp_floats, 4 * SCORE_SLICE));
+    return rc;
+}
+
+// tower + value head of one slice on device tensors (reference layout: meta rows of 7): sc_forward_batch's three launches
+static void dev_forward_slice(sc_engine* e, int n, const int8_t* boards, const int32_t* meta, float* logp, float* value, hipStream_t st) {
+    enqueue_forward(e, n, boards, meta, 7, nullptr, nullptr, nullptr, value, logp, nullptr, -1, st);
+}
+
+static int check_device_ptrs(std::initializer_list<std::pair<const void*, const char*>> ptrs, int dev) {
+    for (const auto& x : ptrs) {
+        const int rc = check_device_ptr(x.first, dev, x.second);
+        if (rc) return rc;
+    }
+    return 0;
+}
+static int check_row_alignment(std::initializer_list<std::pair<const void*, const char*>> ptrs) {
+    for (const auto& x : ptrs)
+        if (reinterpret_cast<uintptr_t>(x.first) & 15) return fail(std::string(x.second) + ": rows are read 16 bytes at a time, the pointer must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" {
+
+int sc_forward_device(sc_engine* e, int n, const int8_t* boards, const int32_t* meta, void* stream, float* logp, float* value) {
+    if (!e || !boards || !meta || !value || n < 0) return fail("bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
+    HIPOK(hipSetDevice(e->device));
+    {
+        const int rc = check_device_ptrs({{boards, "boards"}, {meta, "meta"}, {logp, "logp"}, {value, "value"}}, e->device);
+        if (rc) return rc;
+    }
+    if (n == 0) return 0;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    {
+        const int rc = dev_reserve(e, n, false, 0);
+        if (rc) return rc;
+    }
+    DevCall call{e, st};
+    {
+        const int rc = call.begin();
+        if (rc) return rc;
+    }
+    for (int p0 = 0; p0 < n; p0 += SCORE_SLICE) {
+        const int m = std::min(SCORE_SLICE, n - p0);
+        dev_forward_slice(e, m, boards + (size_t)p0 * 7168, meta + (size_t)p0 * 7, logp ? logp + (size_t)p0 * 4672 : nullptr, value + p0, st);
+    }
+    HIPOK(hipGetLastError());
+    return 0;
+}
+
+int sc_score_positions(sc_engine* e, int n, const int8_t* boards, const int32_t* meta, const float* dist, const float* dist_legal,
+                       const uint16_t* legal_idx, const int32_t* n_legal, const float* outcome, void* stream, float* ce, float* se,
+                       float* ent, float* value, double* summary) {
+    if (!e || !boards || !meta || !outcome || n < 0) return fail("bad argument");
+    const bool sparse = dist_legal || legal_idx || n_legal;
+    if (dist && sparse) return fail("give the visit shares in ONE form: dist, or dist_legal + legal_idx + n_legal");
+    if (!dist && !(dist_legal && legal_idx && n_legal)) return fail("the visit shares are missing: dist, or dist_legal + legal_idx + n_legal");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
+    HIPOK(hipSetDevice(e->device));
+    {
+        int rc = check_device_ptrs({{boards, "boards"}, {meta, "meta"}, {dist, "dist"}, {dist_legal, "dist_legal"}, {legal_idx, "legal_idx"},
+                                    {n_legal, "n_legal"}, {outcome, "outcome"}, {ce, "ce"}, {se, "se"}, {ent, "ent"}, {value, "value"},
+                                    {summary, "summary"}}, e->device);
+        if (!rc) rc = check_row_alignment({{dist, "dist"}});
+        if (rc) return rc;
+    }
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {
+        if (summary) HIPOK(hipMemsetAsync(summary, 0, 5 * sizeof(double), st));
+        return 0;
+    }
+    {
+        const int rc = dev_reserve(e, n, true, (size_t)3 * n);
+        if (rc) return rc;
+    }
+    DevCall call{e, st};
+    {
+        const int rc = call.begin();
+        if (rc) return rc;
+    }
+    float* w_ce = ce ? ce : e->dv_pp;
+    float* w_se = se ? se : e->dv_pp + (size_t)n;
+    float* w_ent = ent ? ent : e->dv_pp + (size_t)2 * n;
+    for (int p0 = 0; p0 < n; p0 += SCORE_SLICE) {
+        const int m = std::min(SCORE_SLICE, n - p0);
+        dev_forward_slice(e, m, boards + (size_t)p0 * 7168, meta + (size_t)p0 * 7, e->dv_logp, e->dv_value, st);
+        scsc::ScoreArgs a{};
+        a.n = m;
+        a.logp = e->dv_logp;
+        a.value = e->dv_value;
+        a.dist = dist ? dist + (size_t)p0 * 4672 : nullptr;
+        a.dist_legal = dist ? nullptr : dist_legal + (size_t)p0 * 224;
+        a.legal_idx = dist ? nullptr : legal_idx + (size_t)p0 * 224;
+        a.n_legal = dist ? nullptr : n_legal + p0;
+        a.outcome = outcome + p0;
+        a.ce = w_ce + p0;
+        a.se = w_se + p0;
+        a.ent = w_ent + p0;
+        a.value_out = value ? value + p0 : nullptr;
+        scl::score_positions(a, st);
+    }
+    if (summary) {
+        scsc::SummaryArgs s{};
+        s.n = n;
+        s.mode = 0;
+        s.x0 = w_ce;
+        s.x1 = w_se;
+        s.x2 = w_ent;
+        s.out = summary;
+        scl::score_summary(s, st);
+    }
+    HIPOK(hipGetLastError());
+    return 0;
+}
+
+int sc_compare_engines(sc_engine* ea, sc_engine* eb, int n, const int8_t* boards, const int32_t* meta, void* stream, float* tv,
+                       float* dv, double* summary) {
+    if (!ea || !eb || !boards || !meta || n < 0) return fail("bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
+    if (ea->device != eb->device)
+        return fail("the two engines are on devices " + std::to_string(ea->device) + " and " + std::to_string(eb->device) +
+                    ": sc_compare_engines needs both on the GPU that holds the positions");
+    HIPOK(hipSetDevice(ea->device));
+    {
+        const int rc = check_device_ptrs({{boards, "boards"}, {meta, "meta"}, {tv, "tv"}, {dv, "dv"}, {summary, "summary"}}, ea->device);
+        if (rc) return rc;
+    }
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {
+        if (summary) HIPOK(hipMemsetAsync(summary, 0, 9 * sizeof(double), st));
+        return 0;
+    }
+    const bool same = ea == eb;   // one engine against itself: one forward pass, its rows on both sides
+    {
+        int rc = dev_reserve(ea, n, true, (size_t)2 * n);
+        if (!rc && !same) rc = dev_reserve(eb, n, true, 0);
+        if (rc) return rc;
+    }
+    DevCall call_a{ea, st}, call_b{eb, st};
+    {
+        int rc = call_a.begin();
+        if (!rc && !same) rc = call_b.begin();
+        if (rc) return rc;
+    }
+    float* w_tv = tv ? tv : ea->dv_pp;
+    float* w_dv = dv ? dv : ea->dv_pp + (size_t)n;
+    for (int p0 = 0; p0 < n; p0 += SCORE_SLICE) {
+        const int m = std::min(SCORE_SLICE, n - p0);
+        dev_forward_slice(ea, m, boards + (size_t)p0 * 7168, meta + (size_t)p0 * 7, ea->dv_logp, ea->dv_value, st);
+        if (!same) dev_forward_slice(eb, m, boards + (size_t)p0 * 7168, meta + (size_t)p0 * 7, eb->dv_logp, eb->dv_value, st);
+        scsc::CompareArgs a{};
+        a.n = m;
+        a.logp1 = ea->dv_logp;
+        a.logp2 = eb->dv_logp;
+        a.value1 = ea->dv_value;
+        a.value2 = eb->dv_value;
+        a.tv = w_tv + p0;
+        a.dv = w_dv + p0;
+        scl::compare_rows(a, st);
+    }
+    if (summary) {
+        scsc::SummaryArgs s{};
+        s.n = n;
+        s.mode = 1;
+        s.x0 = w_tv;
+        s.x1 = w_dv;
+        s.x2 = nullptr;
+        s.out = summary;
+        scl::score_summary(s, st);
+    }
+    HIPOK(hipGetLastError());
     return 0;
 }
 

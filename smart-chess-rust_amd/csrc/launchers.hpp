@@ -4,6 +4,7 @@
 
 #include "mcts_types.hpp"
 #include "nn_types.hpp"
+#include "score_types.hpp"
 
 namespace scl {
 // mcts_kernels.hip (compiled with -ffp-contract=off)
@@ -41,4 +42,9 @@ const char* step_init();
 int step_blocks_per_cu(const scnn::NetLayout& net);
 void step(const scnn::TowerArgs& a, const sc::SpParams& p, int do_expand, hipStream_t s);
 void value_finish(const scnn::VfinArgs& a, hipStream_t s);
+// score_kernels.hip (compiled with -ffp-contract=off): losses / agreement per position from the tower's log-probability rows,
+// and the [P] -> summary reduction (sc_score_positions, sc_compare_engines)
+void score_positions(const scsc::ScoreArgs& a, hipStream_t s);
+void compare_rows(const scsc::CompareArgs& a, hipStream_t s);
+void score_summary(const scsc::SummaryArgs& a, hipStream_t s);
 }  // namespace scl

@@ -95,6 +95,9 @@ ABI = {
     "sc_encode_steps": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_encode_steps_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_selfplay_encode_traces": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_forward_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sc_score_positions": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_compare_engines": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_trace_write_json": (_i, [C.c_char_p, C.POINTER(TraceInfo), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_move_uci": (_i, [C.c_uint16, C.c_char_p]),
     "sc_move_index": (_i, [C.c_uint16, _i]),
@@ -189,6 +192,20 @@ class Engine:
         logp = np.zeros((n, 4672), np.float32) if want_logp else None
         value = np.zeros(n, np.float32)
         _check(self.L.sc_forward_batch(self.h, n, _p(boards), _p(meta), _p(logp), _p(value)))
+        return logp, value
+
+    def forward_torch(self, boards, meta, want_logp=True):
+        """sc_forward_device: ChessModule.forward on torch tensors of this engine's GPU -- boards int8 [n,8,8,112], meta int32 [n,7]
+        (layout="reference") -> (logp float32 [n,4672] or None, value float32 [n]), enqueued on torch.cuda.current_stream();
+        bit-identical to forward()"""
+        torch = _torch_for_device()
+        _check_reference_tensors(torch, boards, meta, self.device)
+        n = boards.shape[0]
+        dev = torch.device("cuda", self.device)
+        logp = torch.empty((n, 4672), dtype=torch.float32, device=dev) if want_logp else None
+        value = torch.empty(n, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(self.device)
+        _check(self.L.sc_forward_device(self.h, n, _tp(boards), _tp(meta), C.c_void_p(stream.cuda_stream), _tp(logp), _tp(value)))
         return logp, value
 
     def debug(self, boards, meta, stage):
@@ -381,6 +398,90 @@ def encode_steps_torch(games, apply_mirror=False, layout="trainer", dist="dense"
                                     _p(coff), int(bool(apply_mirror)), args[0], C.c_void_p(stream.cuda_stream), *args[1:]))
     oc = np.zeros(n, np.float32) if outcomes is None else np.asarray(outcomes, np.float32)
     return _finish_outputs(torch, out, off, oc, apply_mirror, dev)
+
+
+def _tp(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _check_reference_tensors(torch, boards, meta, device):
+    """boards / meta of layout="reference" (int8 [n,8,8,112], int32 [n,7]) on cuda:<device>; the trainer layout is refused"""
+    if boards.dtype != torch.int8 or meta.dtype != torch.int32 or tuple(boards.shape[1:]) != (8, 8, 112) or tuple(meta.shape[1:]) != (7,):
+        raise ValueError('boards / meta are not in the reference layout (int8 [P,8,8,112], int32 [P,7]): encode them with '
+                         'layout="reference" -- the network kernels read the planes as the encoder writes them, not the '
+                         "trainer's float32 [P,112,8,8]")
+    for name, t in (("boards", boards), ("meta", meta)):
+        if not t.is_cuda or t.device.index != device or not t.is_contiguous():
+            raise ValueError(f"{name}: a contiguous tensor on cuda:{device} is needed")
+    if meta.shape[0] != boards.shape[0]:
+        raise ValueError("boards and meta differ in their number of positions")
+
+
+SCORE_SUMMARY = ("n", "loss1", "loss2", "pi_entropy", "n_nonfinite")
+COMPARE_SUMMARY = ("n", "tv_mean", "tv_std", "tv_max", "tv_min", "dv_mean", "dv_std", "dv_max", "dv_min")
+
+
+def score_torch(engine, tensors):
+    """A network judged on recorded search results (sc_score_positions; the reference's validation_step and pi_entropy).
+    tensors: the dict encode_steps_torch(..., layout="reference") / SelfPlay.training_tensors(..., layout="reference")
+    returns -- boards, meta, outcome and the visit shares as dist (dense) or dist_legal + legal_idx + n_legal (with
+    dist="both" the sparse form is used: 21 x fewer bytes).
+    -> dict: per-position torch tensors ce, se, ent, value (float32 [P], on the GPU), floats loss1 = mean ce, loss2 = mean se,
+    pi_entropy = mean ent, ints n and n_nonfinite (positions whose ce, se or ent is not finite; they stay in the means).
+    Enqueued on torch.cuda.current_stream(); the summary's copy to the host waits for it."""
+    torch = _torch_for_device()
+    boards, meta = tensors["boards"], tensors["meta"]
+    _check_reference_tensors(torch, boards, meta, engine.device)
+    n = boards.shape[0]
+    dist, dl, li, nl = (tensors.get(k) for k in ("dist", "dist_legal", "legal_idx", "n_legal"))
+    if dl is not None and li is not None and nl is not None:
+        dist = None
+        if dl.dtype != torch.float32 or li.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or nl.dtype != torch.int32:
+            raise ValueError("dist_legal float32, legal_idx int16 and n_legal int32 are needed")
+        sparse = (dl, li, nl)
+    elif dist is not None:
+        if dist.dtype != torch.float32:
+            raise ValueError("dist: float32 is needed")
+        sparse = (None, None, None)
+    else:
+        raise ValueError("the visit shares are missing: dist, or dist_legal + legal_idx + n_legal")
+    outcome = tensors["outcome"]
+    dev = torch.device("cuda", engine.device)
+    for name, t, rows in (("dist", dist, n), ("dist_legal", sparse[0], n), ("legal_idx", sparse[1], n), ("n_legal", sparse[2], n),
+                          ("outcome", outcome, n)):
+        if t is not None and (t.device != dev or not t.is_contiguous() or t.shape[0] != rows):
+            raise ValueError(f"{name}: a contiguous tensor of {rows} rows on cuda:{engine.device} is needed")
+    if outcome.dtype != torch.float32:
+        raise ValueError("outcome: float32 is needed")
+    out = {k: torch.empty(n, dtype=torch.float32, device=dev) for k in ("ce", "se", "ent", "value")}
+    summary = torch.empty(len(SCORE_SUMMARY), dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(engine.device)
+    _check(engine.L.sc_score_positions(engine.h, n, _tp(boards), _tp(meta), _tp(dist), _tp(sparse[0]), _tp(sparse[1]), _tp(sparse[2]),
+                                       _tp(outcome), C.c_void_p(stream.cuda_stream), _tp(out["ce"]), _tp(out["se"]), _tp(out["ent"]),
+                                       _tp(out["value"]), _tp(summary)))
+    s = summary.cpu().tolist()
+    out.update(n=int(s[0]), loss1=s[1], loss2=s[2], pi_entropy=s[3], n_nonfinite=int(s[4]))
+    return out
+
+
+def compare_torch(engine_a, engine_b, tensors):
+    """Agreement of two networks on the same positions (sc_compare_engines; the reference's scripts/validate_model.py).
+    tensors: a dict with boards and meta in layout="reference" on the engines' GPU.
+    -> dict: per-position torch tensors tv (total variation of the two policies) and dv (|value_a - value_b|), and the floats
+    tv_mean, tv_std, tv_max, tv_min, dv_mean, dv_std, dv_max, dv_min (population standard deviation), int n."""
+    torch = _torch_for_device()
+    boards, meta = tensors["boards"], tensors["meta"]
+    _check_reference_tensors(torch, boards, meta, engine_a.device)
+    n = boards.shape[0]
+    dev = torch.device("cuda", engine_a.device)
+    out = {k: torch.empty(n, dtype=torch.float32, device=dev) for k in ("tv", "dv")}
+    summary = torch.empty(len(COMPARE_SUMMARY), dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(engine_a.device)
+    _check(engine_a.L.sc_compare_engines(engine_a.h, engine_b.h, n, _tp(boards), _tp(meta), C.c_void_p(stream.cuda_stream),
+                                         _tp(out["tv"]), _tp(out["dv"]), _tp(summary)))
+    s = summary.cpu().tolist()
+    out.update({k: v for k, v in zip(COMPARE_SUMMARY[1:], s[1:])}, n=int(s[0]))
+    return out
 
 
 def encode_steps_last_timing():
