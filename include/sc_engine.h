@@ -216,6 +216,34 @@ int sc_score_positions(sc_engine*, int n, const int8_t* boards, const int32_t* m
 int sc_compare_engines(sc_engine* a, sc_engine* b, int n, const int8_t* boards, const int32_t* meta, void* stream, float* tv,
                        float* dv, double* summary);
 
+/* ------------------------------------------------------------------ training minibatches from the compact tensors */
+/* The per-sample work of the reference's DataLoader over ChessDataset (py/dataset.py _prepare; scripts/train.py:331-353), for
+ * positions already in device memory: sample b of the batch is built from row r = rows[b] of the tensors ONE
+ * sc_encode_steps_device / sc_selfplay_encode_traces call with layout 0 leaves behind (boards int8 [n_src][8][8][112], meta int32
+ * [n_src][7], dist_legal float [n_src][SC_MAX_MOVES], legal_idx uint16 [n_src][SC_MAX_MOVES], n_legal int32 [n_src]) plus outcome
+ * float [n_src] -- 8 548 B per ply instead of the trainer layout's 47 392.  rows int32 [n_batch] (a row may repeat); mirror uint8
+ * [n_batch] or NULL (none).  All array arguments are device pointers; boards, dist_legal, legal_idx, out_boards and out_dist
+ * 16-byte aligned.  Outputs, each may be NULL:
+ *   out_boards[b]  float [112][8][8] = (float) boards[r][square][plane]: signed, exact
+ *   out_meta[b]    float [7] = meta[r], exact; with mirror[b] != 0 Board::rotate()'s meta as apply_mirror forms it: with
+ *                  t = m[0], [1 - t, m[1] + (t == 1), m[4], m[5], m[2], m[3], m[6]].  Planes and dist do not change under the mirror
+ *   out_dist[b]    float [4672]: zeros, and dist_legal[r][i] at legal_idx[r][i] for i < n_legal[r] ONLY (the padding points at
+ *                  action 0, which can be a legal move) -- bit-identical to the dense dist the encoder writes for that ply
+ *   out_outcome[b] float = outcome[r], negated with mirror[b] != 0 (py/dataset.py:61-62)
+ *   n_bad          int32 [1], zeroed on the stream first: the number of samples with bad input, found on the DEVICE (the call
+ *                  does not read device memory on the host).  rows[b] outside [0, n_src): nothing is read through it, all four
+ *                  outputs of b are NaN.  n_legal[r] outside 0..218, or an action index >= 4672 among the first n_legal[r]:
+ *                  nothing is written through it, out_dist[b] is all NaN, the other three outputs are as normal.
+ * One kernel launch, one workgroup per sample (batch_kernels.hip); no global address is written twice: identical calls give
+ * identical bits.  Pointer checks as sc_forward_device (host memory or memory of another GPU than device_id's: -1); negative
+ * sizes: -1; n_batch == 0: nothing is enqueued or written.
+ * Stream contract: the work is enqueued on `stream` (NULL: the default stream); the call does not synchronise, has no scratch and
+ * keeps nothing after it returns.  Returns 0, or < 0 as every entry point (-3: no HIP device). */
+int sc_gather_batch(int device_id, int n_src, int n_batch, const int32_t* rows, const uint8_t* mirror, const int8_t* boards,
+                    const int32_t* meta, const float* dist_legal, const uint16_t* legal_idx, const int32_t* n_legal,
+                    const float* outcome, void* stream, float* out_boards, float* out_meta, float* out_dist, float* out_outcome,
+                    int32_t* n_bad);
+
 /* ------------------------------------------------------------------ self-play (L-search) */
 /* SYNTH: integer-hash evaluator for exact search-parity tests; SYNTH_COARSE: the same with 2-bit priors and values from
  * {-0.5, 0, 0.5} (exact PUCT ties between some siblings); SYNTH_UNIFORM: uniform priors, value 0 (every unvisited sibling

@@ -1028,6 +1028,50 @@ int sc_compare_engines(sc_engine* ea, sc_engine* eb, int n, const int8_t* boards
     return 0;
 }
 
+// Rows of the compact training tensors, chosen by index, as a trainer-layout minibatch (include/sc_engine.h): one launch of
+// k_gather_batch behind the zeroing of n_bad, on the caller's stream.  No engine, no scratch, nothing kept after the call.
+int sc_gather_batch(int device_id, int n_src, int n_batch, const int32_t* rows, const uint8_t* mirror, const int8_t* boards,
+                    const int32_t* meta, const float* dist_legal, const uint16_t* legal_idx, const int32_t* n_legal,
+                    const float* outcome, void* stream, float* out_boards, float* out_meta, float* out_dist, float* out_outcome,
+                    int32_t* n_bad) {
+    if (n_src < 0 || n_batch < 0 || !rows || !boards || !meta || !dist_legal || !legal_idx || !n_legal || !outcome) return fail("bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
+    if (device_id < 0 || device_id >= ndev) return fail("device_id out of range");
+    HIPOK(hipSetDevice(device_id));
+    {
+        int rc = check_device_ptrs({{rows, "rows"}, {mirror, "mirror"}, {boards, "boards"}, {meta, "meta"}, {dist_legal, "dist_legal"},
+                                    {legal_idx, "legal_idx"}, {n_legal, "n_legal"}, {outcome, "outcome"}, {out_boards, "out_boards"},
+                                    {out_meta, "out_meta"}, {out_dist, "out_dist"}, {out_outcome, "out_outcome"}, {n_bad, "n_bad"}},
+                                   device_id);
+        if (!rc) rc = check_row_alignment({{boards, "boards"}, {dist_legal, "dist_legal"}, {legal_idx, "legal_idx"},
+                                           {out_boards, "out_boards"}, {out_dist, "out_dist"}});
+        if (rc) return rc;
+    }
+    if (n_batch == 0) return 0;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n_bad) HIPOK(hipMemsetAsync(n_bad, 0, sizeof(int32_t), st));
+    scbt::GatherArgs a{};
+    a.n_src = n_src;
+    a.n_batch = n_batch;
+    a.rows = rows;
+    a.mirror = mirror;
+    a.boards = boards;
+    a.meta = meta;
+    a.dist_legal = dist_legal;
+    a.legal_idx = legal_idx;
+    a.n_legal = n_legal;
+    a.outcome = outcome;
+    a.out_boards = out_boards;
+    a.out_meta = out_meta;
+    a.out_dist = out_dist;
+    a.out_outcome = out_outcome;
+    a.n_bad = n_bad;
+    scl::gather_batch(a, st);
+    HIPOK(hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"
 
 // ============================================================================================

@@ -5,6 +5,7 @@
 #include "mcts_types.hpp"
 #include "nn_types.hpp"
 #include "score_types.hpp"
+#include "batch_types.hpp"
 
 namespace scl {
 // mcts_kernels.hip (compiled with -ffp-contract=off)
@@ -47,4 +48,6 @@ void value_finish(const scnn::VfinArgs& a, hipStream_t s);
 void score_positions(const scsc::ScoreArgs& a, hipStream_t s);
 void compare_rows(const scsc::CompareArgs& a, hipStream_t s);
 void score_summary(const scsc::SummaryArgs& a, hipStream_t s);
+// batch_kernels.hip: rows of the compact training tensors, chosen by index -> a trainer-layout minibatch (sc_gather_batch)
+void gather_batch(const scbt::GatherArgs& a, hipStream_t s);
 }  // namespace scl

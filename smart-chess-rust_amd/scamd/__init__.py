@@ -13,12 +13,14 @@ reference's usage:
   SelfPlay.training_tensors           (from recorded games, or from the self-play trace ring in place)
   score_torch, compare_torch,    <->  scripts/train.py validation_step (loss1, loss2, pi_entropy) and scripts/validate_model.py
   Engine.forward_torch                (total variation, |value1 - value2|) on those tensors, without leaving the GPU
+  gather_batch_torch,            <->  DataLoader(ConcatDataset([ChessDataset ...]), shuffle=True, drop_last=True) + _prepare
+  ReplayBuffer                        (scripts/train.py:331-353): shuffled trainer-layout minibatches from the compact tensors
 
 There is NO CPU fallback: importing works anywhere (so the C ABI can be checked), but every
 compute entry point raises EngineError when the HIP library or a GPU is missing.
 """
 from .binding import (ChessHip, Engine, EngineError, Play, SelfPlay, encode_move, encode_positions, encode_steps, encode_steps_batch,  # noqa: F401
-                      encode_steps_torch, score_torch, compare_torch, pack_steps, hip_runtime, hip_runtime_files,
+                      encode_steps_torch, score_torch, compare_torch, gather_batch_torch, ReplayBuffer, ReplayIndex, pack_steps, hip_runtime, hip_runtime_files,
                       enqueue_interleaved, elo, find_max, lib, lib_path, play_match, runtime_flags, search,
                       move_uci, uci_move, write_trace_json, TERMINATION)
 from . import binding  # noqa: F401
