@@ -391,6 +391,16 @@ int sc_search(sc_engine*, const uint16_t* moves, int n_moves, int rollout, float
  * caller-provided finite values: out[0] = the one-round form used for nodes with <= 64 children (-2 if n > 64),
  * out[1] = the four-round (value, index) form used for wider nodes. */
 int sc_debug_find_max(int device_id, const float* values, int n, int32_t* out2);
+/* test aid: the end-of-ply move choice (mcts::step, src/mcts.rs:298-317; with tie_random NNPlayer::bestmove, src/play.rs:268-277)
+ * on caller-provided visit counts, by the device function the self-play kernels call: one wave per case, all cases in one
+ * launch.  Case c: n_act[c * 224 .. + nc[c]) the children's counts (1 <= nc[c] <= 224, counts in [0, 60000]), temperature[c] >= 0
+ * the temperature already resolved for the ply (at most 64 distinct values per call), u[c] in [0, 1) the uniform draw.
+ * choice_out[c] = the chosen child; total_out[c] = the f32 sum of the weights N^(1/temperature) (0 at temperature 0).  The
+ * weights come from tables the host fills with its libm's powf, one per temperature, exactly as sc_selfplay_create does for a
+ * handle.  A total of 0 or infinity makes the reference panic; here an index is returned all the same (recorded behaviour,
+ * pinned by the tests). */
+int sc_debug_choose_child(int device_id, int n_cases, const int32_t* n_act, const int32_t* nc, const float* temperature,
+                          const float* u, int tie_random, int32_t* choice_out, float* total_out);
 /* test aid: makes the NEXT one-launch steps of the handle wait for arrivals that never come (the in-launch hand-off's target is
  * raised by `missing` arrivals per block), to show on hardware that the wait is bounded: every workgroup gives up after ~0.2 s,
  * the launch ends and error_flags carries bit 32.  The handle's results are invalid afterwards and it refuses further work

@@ -321,7 +321,10 @@ void orc_search_sim(orc_search* s, orc_eval_fn eval, void* user, float cpuct, fl
     }
 }
 
-int orc_choose_child(const int32_t* n_act, int n, float temp, float u01v) {
+int orc_choose_child(const int32_t* n_act, int n, float temp, float u01v) { return orc_choose_child_total(n_act, n, temp, u01v, NULL); }
+
+int orc_choose_child_total(const int32_t* n_act, int n, float temp, float u01v, float* total_out) {
+    if (total_out) *total_out = 0.0f;
     if (n == 0) return -1;
     if (temp == 0.0f) {
         int32_t mx = n_act[0];
@@ -338,6 +341,7 @@ int orc_choose_child(const int32_t* n_act, int n, float temp, float u01v) {
         total += w;
         cum[i] = total;
     }
+    if (total_out) *total_out = total;
     float x = u01v * total;
     int idx = 0;
     for (int i = 0; i < n - 1; i++)

@@ -117,6 +117,7 @@ def lib():
         "orc_search_last_path": (i32, [vp, vp]),
         "orc_search_set_rng": (None, [vp, u64]),
         "orc_choose_child": (i32, [vp, i32, C.c_float, C.c_float]),
+        "orc_choose_child_total": (i32, [vp, i32, C.c_float, C.c_float, C.POINTER(C.c_float)]),
         "orc_selfplay_game": (C.POINTER(Trace), [C.POINTER(SelfplayCfg), vp, vp]),
         "orc_match_game": (C.POINTER(Trace), [vp, vp, vp, vp, vp]),
         "orc_trace_free": (None, [C.POINTER(Trace)]),

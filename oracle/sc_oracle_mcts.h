@@ -43,6 +43,8 @@ void orc_search_set_rng(orc_search*, uint64_t seed);
 /* mcts::step (src/mcts.rs:292-328): temp==0 -> first max-N child; else sample ~ N^(1/temp) with
  * u01 (the build-defined uniform in [0,1) as float with 24 random bits). Returns child index or -1. */
 int orc_choose_child(const int32_t* n_act, int n, float temp, float u01);
+/* the same choice; *total_out (may be NULL) = the f32 sum of the weights WeightedIndex::new is given (0 at temp == 0) */
+int orc_choose_child_total(const int32_t* n_act, int n, float temp, float u01, float* total_out);
 
 typedef struct {
     int n_steps;

@@ -6,6 +6,7 @@
 // many concurrent games per GPU.  All compute runs on the GPU; there is no CPU fallback: every
 // entry point fails with an error code if HIP or the device is unavailable.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <string.h>
@@ -1194,6 +1195,17 @@ static void sp_flush(sc_selfplay* sp) {
     }
 }
 
+// The weights of the end-of-ply move choice (mcts::step, src/mcts.rs:313-315): w[n] = powf((float)n, 1.0f / temperature) for
+// n = 0..n_max, computed HERE, by the host libm -- the function the reference's f32::powf is.  The kernels read the table
+// instead of calling the device's powf, whose results differ from the host's in the last bit, because the sampled
+// index has to be the reference's bit for bit.
+static std::vector<float> choice_weights(float temperature, int n_max) {
+    const float power = 1.0f / temperature;
+    std::vector<float> w((size_t)n_max + 1);
+    for (int n = 0; n <= n_max; n++) w[(size_t)n] = powf((float)n, power);
+    return w;
+}
+
 template <class T>
 static int sp_alloc(sc_selfplay* sp, T** ptr, size_t n, bool zero = true) {
     HIPOK(dalloc(ptr, n));
@@ -1294,10 +1306,21 @@ int sc_selfplay_create(sc_engine* e, int device_id, const sc_selfplay_config* cf
     rc |= sp_alloc(sp, &p.t_cu, T * S * 224, false);
     rc |= sp_alloc(sp, &p.cnt, 1);
     rc |= sp_alloc(sp, &p.slot_cnt, (size_t)cfg->n_slots * 2);
+    // the temperature is fixed for the handle's life (sc_selfplay_set_players / sc_selfplay_set_search do not touch it), and no
+    // ply searches more than rollout_num simulations (the cap of --rollout-factor, 300, is rollout_num: checked above)
+    float* d_choice_w = nullptr;
+    if (cfg->temperature != 0.0f) rc |= sp_alloc(sp, &d_choice_w, (size_t)cfg->rollout_num + 1, false);
     if (rc) {
         std::string keep = g_err;
         sc_selfplay_destroy(sp);
         return fail("self-play allocation failed: " + keep, -2);
+    }
+    if (d_choice_w) {
+        const std::vector<float> w = choice_weights(cfg->temperature, cfg->rollout_num);
+        hipError_t he = hipMemcpy(d_choice_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (he != hipSuccess) return bail(he, "hipMemcpy(choice weights)");
+        p.choice_w = d_choice_w;
+        p.choice_w_max = cfg->rollout_num;
     }
     if (e) {
         rc = engine_reserve(e, cfg->n_slots);
@@ -1829,6 +1852,60 @@ int sc_debug_find_max(int device_id, const float* values, int n, int32_t* out2) 
     hipError_t e1 = hipGetLastError(), e2 = hipMemcpy(out2, d_o, 8, hipMemcpyDeviceToHost);
     dfree({d_u, d_o});
     if (e1 != hipSuccess || e2 != hipSuccess) return fail(hipGetErrorString(e1 != hipSuccess ? e1 : e2), -2);
+    return 0;
+}
+
+int sc_debug_choose_child(int device_id, int n_cases, const int32_t* n_act, const int32_t* nc, const float* temperature, const float* u,
+                          int tie_random, int32_t* choice_out, float* total_out) {
+    if (!n_act || !nc || !temperature || !u || !choice_out || !total_out || n_cases < 1 || n_cases > (1 << 20)) return fail("bad argument");
+    int w_max = 0;
+    for (int c = 0; c < n_cases; c++) {
+        if (nc[c] < 1 || nc[c] > sc::MAXC) return fail("sc_debug_choose_child: nc out of [1, 224]");
+        if (!(temperature[c] >= 0.0f) || !(u[c] >= 0.0f && u[c] < 1.0f)) return fail("sc_debug_choose_child: temperature < 0 or u outside [0, 1)");
+        for (int i = 0; i < nc[c]; i++) {
+            const int32_t n = n_act[(size_t)c * sc::MAXC + i];
+            if (n < 0 || n > 60000) return fail("sc_debug_choose_child: visit count out of [0, 60000]");
+            w_max = std::max(w_max, (int)n);
+        }
+    }
+    // one weight table per distinct temperature, made by the function that makes a self-play handle's
+    std::vector<float> w(1, 0.0f);
+    std::vector<int32_t> w_off((size_t)n_cases, 0);
+    std::map<uint32_t, int32_t> table_of;
+    for (int c = 0; c < n_cases; c++) {
+        if (temperature[c] == 0.0f) continue;
+        uint32_t bits;
+        memcpy(&bits, &temperature[c], 4);
+        auto it = table_of.find(bits);
+        if (it == table_of.end()) {
+            if (table_of.size() >= 64) return fail("sc_debug_choose_child: more than 64 distinct temperatures");
+            it = table_of.emplace(bits, (int32_t)w.size()).first;
+            const std::vector<float> t = choice_weights(temperature[c], w_max);
+            w.insert(w.end(), t.begin(), t.end());
+        }
+        w_off[(size_t)c] = it->second;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no HIP device available: libsc_engine has no CPU fallback", -3);
+    if (device_id < 0 || device_id >= ndev) return fail("device_id out of range");
+    HIPOK(hipSetDevice(device_id));
+    const size_t n = (size_t)n_cases;
+    int32_t *d_n = nullptr, *d_nc = nullptr, *d_ch = nullptr, *d_off = nullptr;
+    float *d_t = nullptr, *d_u = nullptr, *d_tot = nullptr, *d_w = nullptr;
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t r) { return e == hipSuccess && (e = r) == hipSuccess; };
+    if (ok(dalloc(&d_n, n * sc::MAXC)) && ok(dalloc(&d_nc, n)) && ok(dalloc(&d_ch, n)) && ok(dalloc(&d_off, n)) && ok(dalloc(&d_t, n)) &&
+        ok(dalloc(&d_u, n)) && ok(dalloc(&d_tot, n)) && ok(dalloc(&d_w, w.size())) &&
+        ok(hipMemcpy(d_n, n_act, n * sc::MAXC * 4, hipMemcpyHostToDevice)) && ok(hipMemcpy(d_nc, nc, n * 4, hipMemcpyHostToDevice)) &&
+        ok(hipMemcpy(d_t, temperature, n * 4, hipMemcpyHostToDevice)) && ok(hipMemcpy(d_u, u, n * 4, hipMemcpyHostToDevice)) &&
+        ok(hipMemcpy(d_off, w_off.data(), n * 4, hipMemcpyHostToDevice)) && ok(hipMemcpy(d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice))) {
+        scl::debug_choose_child(n_cases, d_n, d_nc, d_t, d_u, tie_random ? 1 : 0, d_w, d_off, w_max, d_ch, d_tot, nullptr);
+        ok(hipGetLastError());
+        ok(hipMemcpy(choice_out, d_ch, n * 4, hipMemcpyDeviceToHost));
+        ok(hipMemcpy(total_out, d_tot, n * 4, hipMemcpyDeviceToHost));
+    }
+    dfree({d_n, d_nc, d_ch, d_off, d_t, d_u, d_tot, d_w});
+    if (e != hipSuccess) return fail(hipGetErrorString(e), -2);
     return 0;
 }
 

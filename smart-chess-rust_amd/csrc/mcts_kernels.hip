@@ -11,6 +11,12 @@ void mcts(const sc::SpParams& p, int do_expand, int do_select, hipStream_t s) {
 }
 void synth_eval(const sc::SpParams& p, hipStream_t s) { hipLaunchKernelGGL(sc::k_synth_eval, dim3(p.n_slots), dim3(64), 0, s, p); }
 void debug_find_max(const float* d_u, int n, int* d_out, hipStream_t s) { hipLaunchKernelGGL(sc::k_debug_find_max, dim3(1), dim3(64), 0, s, d_u, n, d_out); }
+void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc, const float* d_temperature, const float* d_u, int tie_random,
+                        const float* d_w, const int32_t* d_w_off, int w_max, int32_t* d_choice, float* d_total, hipStream_t s) {
+    if (n_cases <= 0) return;
+    hipLaunchKernelGGL(sc::k_debug_choose_child, dim3(n_cases), dim3(64), 0, s, n_cases, d_n_act, d_nc, d_temperature, d_u, tie_random,
+                       d_w, d_w_off, w_max, d_choice, d_total);
+}
 void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s) {
     hipLaunchKernelGGL(sc::k_set_position, dim3(1), dim3(64), 0, s, p, slot, d_moves, n_moves);
 }

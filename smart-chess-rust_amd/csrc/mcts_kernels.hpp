@@ -832,6 +832,84 @@ __device__ inline void finish_game(SpParams& p, int g, int lane, int has_outcome
     start_new_game(p, g, lane);
 }
 
+// ------------------------------------------------------------------ the end-of-ply move choice
+// mcts::step (mcts.rs:298-317) on the visit counts n_act[0..nc) of the root's children (nc >= 1), called by the whole wave with
+// wave-uniform arguments: `temperature` already resolved for the ply, u in [0,1) the ply's uniform draw.  Returns the chosen
+// child; *total = the f32 sum of the weights of the weighted branch (0 at temperature 0).  The one implementation: the
+// self-play kernels and the test aid k_debug_choose_child (sc_debug_choose_child) both call it.
+// The weight N^(1/temperature) is READ from w[0..w_max], which the host filled with ITS libm's powf for this temperature
+// (engine.hip choice_weights): the reference's f32::powf is that function, and the index below must be the reference's bit for
+// bit -- the device's own powf is one ulp off it for a quarter of all (count, temperature) pairs.  Temperature 1
+// (the temperature-switch window) needs no table: powf(n, 1) == n.  A count never exceeds the ply's simulation budget, which
+// the table covers; the index is clamped all the same so that no read can leave the table.
+__device__ inline int choose_child(const int32_t* n_act, int nc, float temperature, float u, int tie_random, int lane, const float* w,
+                                   int w_max, float* total) {
+    *total = 0.0f;
+    if (temperature == 0.0f) {
+        int bn = -1, bi = 0x7fffffff;
+        for (int i = lane; i < nc; i += 64) {
+            int n = n_act[i];
+            if (n > bn) {  // first maximum within the lane (indices increase)
+                bn = n;
+                bi = i;
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            int on = __shfl_xor(bn, o, 64), oi = __shfl_xor(bi, o, 64);
+            if (on > bn || (on == bn && oi < bi)) {
+                bn = on;
+                bi = oi;
+            }
+        }
+        int choice = bi;
+        if (tie_random) {
+            // NNPlayer::bestmove (play.rs:268-277): uniform among the maxima; k = floor(u * count), in index order
+            int cnt = 0;
+            for (int i = 0; i < nc; i++) cnt += n_act[i] == bn;
+            int k = (int)(u * (float)cnt);
+            if (k >= cnt) k = cnt - 1;
+            for (int i = 0; i < nc; i++)
+                if (n_act[i] == bn && k-- == 0) {
+                    choice = i;
+                    break;
+                }
+        }
+        return choice;
+    }
+    // WeightedIndex over N^(1/temp): sequential f32 cumulative sums, x = u*total,
+    // index = number of cumulative weights (last excluded) <= x
+    const bool plain = 1.0f / temperature == 1.0f;
+    auto weight = [&](int n) { return plain ? (float)n : w[n < w_max ? n : w_max]; };
+    float sum = 0.0f;
+    for (int i = 0; i < nc; i++) sum += weight(n_act[i]);
+    *total = sum;
+    float x = u * sum;
+    float cum = 0.0f;
+    int idx = 0;
+    for (int i = 0; i < nc - 1; i++) {
+        cum += weight(n_act[i]);
+        if (cum <= x) idx++;
+    }
+    return idx;
+}
+
+// One wave per case (test aid, sc_debug_choose_child): case c reads n_act[c][0..nc[c]), temperature[c], u[c] and the weight
+// table of its temperature, w[w_off[c] .. + w_max].
+#ifndef SC_NO_KERNELS
+__global__ __launch_bounds__(64) void k_debug_choose_child(int n_cases, const int32_t* n_act, const int32_t* nc, const float* temperature,
+                                                           const float* u, int tie_random, const float* w, const int32_t* w_off, int w_max,
+                                                           int32_t* choice, float* total) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (c >= n_cases) return;
+    float tot;
+    const int ch = choose_child(n_act + (size_t)c * MAXC, uniform(nc[c]), temperature[c], u[c], tie_random, lane, w + uniform(w_off[c]), w_max, &tot);
+    if (lane == 0) {
+        choice[c] = ch;
+        total[c] = tot;
+    }
+}
+#endif
+
 // ------------------------------------------------------------------ expand + backward + mcts::step
 // mcts.rs:267-288 (expand, backward), then when the rollout count is reached the per-ply part of
 // src/main.rs:198-233: snapshot root/children into the trace, mcts::step (mcts.rs:292-328), outcome.
@@ -1038,58 +1116,10 @@ __device__ __forceinline__ void dev_expand(SpParams& p, int g, int lane, Positio
         p.t_cu[tstep * MAXC + i] = U[fc + i];
     }
     // mcts::step (mcts.rs:298-317)
-    float temperature = (ply - cs.start_ply) < p.temp_switch ? 1.0f : p.temperature;
-    int choice = 0;
-    if (temperature == 0.0f) {
-        int bn = -1, bi = 0x7fffffff;
-        for (int i = lane; i < nc; i += 64) {
-            int n = N[fc + i];
-            if (n > bn) {  // first maximum within the lane (indices increase)
-                bn = n;
-                bi = i;
-            }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            int on = __shfl_xor(bn, o, 64), oi = __shfl_xor(bi, o, 64);
-            if (on > bn || (on == bn && oi < bi)) {
-                bn = on;
-                bi = oi;
-            }
-        }
-        choice = bi;
-        if (p.tie_random) {
-            // NNPlayer::bestmove (play.rs:268-277): uniform among the maxima; k = floor(u * count), in index order
-            int cnt = 0;
-            for (int i = 0; i < nc; i++) cnt += N[fc + i] == bn;
-            float u = (float)(sc_rng(p.seed, cs.game_id, (uint64_t)ply, 1, 0) >> 40) / 16777216.0f;
-            int k = (int)(u * (float)cnt);
-            if (k >= cnt) k = cnt - 1;
-            for (int i = 0; i < nc; i++)
-                if (N[fc + i] == bn && k-- == 0) {
-                    choice = i;
-                    break;
-                }
-        }
-    } else {
-        // WeightedIndex over N^(1/temp): sequential f32 cumulative sums, x = u*total,
-        // index = number of cumulative weights (last excluded) <= x
-        float power = 1.0f / temperature;
-        float total = 0.0f;
-        for (int i = 0; i < nc; i++) {
-            float n = (float)N[fc + i];
-            total += power == 1.0f ? n : powf(n, power);
-        }
-        float u = (float)(sc_rng(p.seed, cs.game_id, (uint64_t)ply, 1, 0) >> 40) / 16777216.0f;
-        float x = u * total;
-        float cum = 0.0f;
-        int idx = 0;
-        for (int i = 0; i < nc - 1; i++) {
-            float n = (float)N[fc + i];
-            cum += power == 1.0f ? n : powf(n, power);
-            if (cum <= x) idx++;
-        }
-        choice = idx;
-    }
+    const float temperature = (ply - cs.start_ply) < p.temp_switch ? 1.0f : p.temperature;
+    const float u = (float)(sc_rng(p.seed, cs.game_id, (uint64_t)ply, 1, 0) >> 40) / 16777216.0f;
+    float w_total;
+    const int choice = choose_child(N + fc, nc, temperature, u, p.tie_random, lane, p.choice_w, p.choice_w_max, &w_total);
     move_t mv = MV[fc + choice];
     if (lane == 0) {
         p.t_move[tstep] = mv;

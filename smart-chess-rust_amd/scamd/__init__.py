@@ -21,6 +21,6 @@ compute entry point raises EngineError when the HIP library or a GPU is missing.
 """
 from .binding import (ChessHip, Engine, EngineError, Play, SelfPlay, encode_move, encode_positions, encode_steps, encode_steps_batch,  # noqa: F401
                       encode_steps_torch, score_torch, compare_torch, gather_batch_torch, ReplayBuffer, ReplayIndex, pack_steps, hip_runtime, hip_runtime_files,
-                      enqueue_interleaved, elo, find_max, lib, lib_path, play_match, runtime_flags, search,
+                      choose_child, enqueue_interleaved, elo, find_max, lib, lib_path, play_match, runtime_flags, search,
                       move_uci, uci_move, write_trace_json, TERMINATION)
 from . import binding  # noqa: F401

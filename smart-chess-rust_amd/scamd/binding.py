@@ -58,6 +58,7 @@ ABI = {
     "sc_last_warning": (C.c_char_p, []),
     "sc_selfplay_poll": (_i, [_vp, _vp, _i]),
     "sc_debug_find_max": (_i, [_i, _vp, _i, _vp]),
+    "sc_debug_choose_child": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "sc_selfplay_debug_break_handoff": (_i, [_vp, _i]),
     "sc_debug_clear_handoff_failure": (_i, [_i]),
     "sc_selfplay_debug_cycles": (_i, [_vp, _i, _vp]),
@@ -1113,6 +1114,22 @@ def find_max(values, device=0):
     out = np.zeros(2, np.int32)
     _check(lib().sc_debug_find_max(device, _p(v), v.size, _p(out)))
     return int(out[0]), int(out[1])
+
+
+def choose_child(n_act, nc, temperature, u, tie_random=False, device=0):
+    """sc_debug_choose_child: (choice [n] int32, total [n] float32) of the end-of-ply move choice on n cases;
+    n_act [n][224] visit counts, nc / temperature / u one value per case"""
+    nc = np.ascontiguousarray(nc, np.int32)
+    n = nc.size
+    n_act = np.ascontiguousarray(n_act, np.int32)
+    temperature = np.ascontiguousarray(temperature, np.float32)
+    u = np.ascontiguousarray(u, np.float32)
+    if n_act.shape != (n, MAX_MOVES) or temperature.shape != (n,) or u.shape != (n,):
+        raise ValueError("choose_child: n_act must be [n][224], nc / temperature / u [n]")
+    choice = np.zeros(n, np.int32)
+    total = np.zeros(n, np.float32)
+    _check(lib().sc_debug_choose_child(device, n, _p(n_act), _p(nc), _p(temperature), _p(u), int(tie_random), _p(choice), _p(total)))
+    return choice, total
 
 
 def runtime_flags():

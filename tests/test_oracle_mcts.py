@@ -107,6 +107,44 @@ def test_choose_child_rules(orc):
     assert L.orc_choose_child(n.ctypes.data, 0, 1.0, 0.5) == -1         # no children -> None
 
 
+def test_choose_child_equals_a_plain_restatement_on_host_powf(orc):
+    """orc_choose_child(_total) against a direct Python restatement of mcts.rs:298-317 whose weights are the host libm's powf
+    through ctypes (the function Rust's f32::powf lowers to) and whose sums are f32 scalars: index AND total bits, on the
+    inputs of tests/test_gpu_choice.py -- single weights for every count 0..1024 over the temperature grid, count vectors with
+    u on the lattice points around their cumulative boundaries, first-maximum ties, zero and infinite totals (where the
+    reference panics in WeightedIndex::new: recorded behaviour, not reference parity).  Fixes the oracle's side of the
+    device comparison independently of the device."""
+    import choice_cases as cc
+    f = np.float32
+    # single weights: nc = 1, total = powf((float)n, 1.0f / T)
+    cases = [([n], T, f(0.5)) for T in cc.TEMPS for n in range(1025)]
+    n_act, nc, temp, u = cc.pack(cases)
+    c, t = cc.oracle_choices(orc, n_act, nc, temp, u)
+    want = np.array([cc.host_powf(f(n[0]), f(1.0) / f(T)) for n, T, _ in cases], np.float32)
+    assert np.isfinite(want).all() and not c.any()
+    assert np.array_equal(t.view(np.uint32), want.view(np.uint32))
+    # decisions next to boundaries (a thinner slice of the GPU test's vectors: the restatement is a Python loop), ties, degenerate totals
+    cases = cc.boundary_cases(per_vector_temps=1, n_random_u=2, n_boundaries=4)
+    cases += [([7] * k, 0.0, f(0.5)) for k in cc.NCS] + [([1, 5, 2, 5, 5], 0.0, f(0.9)), ([0, 0, 0], 0.0, f(0.0))]
+    cases += cc.degenerate_cases()
+    n_act, nc, temp, u = cc.pack(cases)
+    c, t = cc.oracle_choices(orc, n_act, nc, temp, u)
+    exact = 0
+    for i, (n, T, uu) in enumerate(cases):
+        wc, wt = cc.choose_ref(n, T, uu)
+        assert c[i] == wc and t[i:i + 1].view(np.uint32)[0] == np.array([wt], np.float32).view(np.uint32)[0], (i, n, T, uu, c[i], wc, t[i], wt)
+        if T != 0.0 and np.isfinite(wt) and wt > 0:
+            cum, tot = cc.weights_ref(n, T)
+            exact += any(cm == f(f(uu) * tot) for cm in cum[:-1])
+    assert {float(x) for x in t} >= {0.0, float("inf")}
+    # the inputs bite: in many cases one cumulative sum EQUALS x (`<=` against `<`), so one ulp in a weight changes the index
+    assert exact > 200, exact
+    # orc_choose_child is the same function without the total
+    L = orc.lib()
+    for i in range(0, len(cases), 7):
+        assert L.orc_choose_child(n_act[i].ctypes.data, int(nc[i]), float(temp[i]), float(u[i])) == c[i]
+
+
 def test_selfplay_trace_semantics(orc):
     g = orc.selfplay_game(rollout_num=30, num_steps=150, with_noise=True, seed=4, game_id=2)
     assert g == orc.selfplay_game(rollout_num=30, num_steps=150, with_noise=True, seed=4, game_id=2)
