@@ -41,7 +41,8 @@ def build(force=False, verbose=False):
     objs = []
     for src, extra in (("mcts_kernels.hip", ["-ffp-contract=off"]), ("nn_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
                        ("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("score_kernels.hip", ["-ffp-contract=off"]),
-                       ("batch_kernels.hip", []), ("engine.hip", [])):
+                       ("batch_kernels.hip", []), ("engine.hip", []), ("encode_steps.hip", []), ("device_calls.hip", []),
+                       ("selfplay.hip", []), ("selfplay_io.hip", [])):
         s = os.path.join(CSRC, src)
         o = os.path.join(BUILD, src.replace(".hip", ".o"))
         if force or _newer(o, [s] + hdrs):

@@ -1,0 +1,275 @@
+// encode_steps.hip -- host side of libsc_engine.so: training tensors (sc_encode_steps, sc_encode_steps_device).
+//
+// libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) for a batch of recorded games; see include/sc_engine.h.
+// One encoder, encode_device_core, writes device buffers on a stream.  sc_encode_steps_device / sc_selfplay_encode_traces hand
+// it the caller's buffers and stream: nothing is staged and nothing waits for the device in the steady state.  sc_encode_steps
+// runs it into staging buffers, slice by slice, and copies out to the caller's host arrays.
+// The scratch of a call lives in a per-device arena that the library keeps and reuses: an event recorded behind each call's
+// work orders the next call after it on the device (hipStreamWaitEvent, whatever its stream); only growing the arena waits
+// on the host, for that previous call, before the old buffer is freed.
+#include <chrono>
+#include <map>
+#include <mutex>
+
+#include "host_common.hpp"
+
+static thread_local float g_encode_ms[2] = {0.f, 0.f};   // last sc_encode_steps of this thread: kernels (HIP events), whole call
+
+namespace {
+struct EncArena {
+    DevBuf<char> buf;
+    hipEvent_t ev = nullptr;   // behind the last call's work
+    bool used = false;
+};
+std::mutex g_enc_mu;   // held across a call's enqueue: calls on one device take the arena in turn
+std::map<int, EncArena> g_enc_arena;
+struct ArenaRelease {   // scope guard: on every path out of the call (failures included), later calls wait for what was enqueued
+    EncArena& a;
+    hipStream_t s;
+    bool armed = false;
+    ~ArenaRelease() {
+        if (armed && hipEventRecord(a.ev, s) == hipSuccess) a.used = true;
+    }
+};
+}  // namespace
+
+// output pointers must be device memory of `dev` (a host pointer, or memory of another GPU, would be written by kernels that
+// cannot reach it)
+static int check_device_ptr(const void* ptr, int dev, const char* name) {
+    if (!ptr) return 0;
+    hipPointerAttribute_t a{};
+    const hipError_t e = hipPointerGetAttributes(&a, ptr);
+    (void)hipGetLastError();   // (an unknown host pointer is an error of this query only)
+    if (e != hipSuccess || a.type != hipMemoryTypeDevice)
+        return fail(std::string(name) + ": not device memory (outputs of this call are device pointers, e.g. hipMalloc or a torch "
+                    "tensor on the handle's GPU)");
+    if (a.device != dev)
+        return fail(std::string(name) + ": memory of device " + std::to_string(a.device) + ", the call runs on device " + std::to_string(dev));
+    return 0;
+}
+
+int check_device_ptrs(std::initializer_list<std::pair<const void*, const char*>> ptrs, int dev) {
+    for (const auto& x : ptrs) TRY(check_device_ptr(x.first, dev, x.second));
+    return 0;
+}
+int check_device_outputs(const DevEncodeOut& o, int dev) {
+    if (o.layout != 0 && o.layout != 1) return fail("layout must be 0 (reference) or 1 (trainer)");
+    return check_device_ptrs({{o.boards, "boards"}, {o.meta, "meta"}, {o.dist, "dist"}, {o.dist_legal, "dist_legal"},
+                              {o.legal_idx, "legal_idx"}, {o.n_legal, "n_legal"}, {o.status, "status"}}, dev);
+}
+
+// ply_off: host, n_games + 1 (the plies of game g are [ply_off[g], ply_off[g+1])).  Host path: moves / child_mv / child_n /
+// child_off are host arrays as sc_encode_steps takes them; ring path (ring != nullptr): the moves and children are read from the
+// trace ring rows on the device.
+int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
+                       const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
+                       hipStream_t st) {
+    const uint32_t P = ply_off[n_games];
+    // the game records of one group of games: (games in the group) x (longest game of the group + 2) <= REC_BUDGET, so one long
+    // game among many short ones does not size the buffer for all of them (80 B per record: 80 MiB)
+    const size_t REC_BUDGET = (size_t)1 << 20;
+    const uint32_t CH = 32768;   // plies per launch of the per-ply kernels (bounds their legal-move / meta scratch: 15 MB)
+    struct Group {
+        int g0, ng, hist_cap;
+    };
+    std::vector<Group> groups;
+    size_t max_rec = 1;
+    for (int g0 = 0; g0 < n_games;) {
+        uint32_t mx = ply_off[g0 + 1] - ply_off[g0];
+        int g1 = g0 + 1;
+        while (g1 < n_games) {
+            const uint32_t m2 = std::max(mx, ply_off[g1 + 1] - ply_off[g1]);
+            if ((size_t)(g1 - g0 + 1) * (m2 + 2) > REC_BUDGET) break;
+            mx = m2;
+            g1++;
+        }
+        groups.push_back({g0, g1 - g0, (int)mx + 2});
+        max_rec = std::max(max_rec, (size_t)(g1 - g0) * (mx + 2));
+        g0 = g1;
+    }
+    const bool has_ring = ring != nullptr;
+    const uint32_t nchild = has_ring ? 0 : child_off[P];
+    const uint32_t cap = std::max<uint32_t>(std::min(CH, P), 1);
+    uint32_t *d_off, *d_hoff, *d_plen, *d_pgame, *d_src, *d_coff, *d_cn;
+    uint16_t *d_moves, *d_lm, *d_cmv;
+    sc::Position* d_hist;
+    int32_t *d_meta, *d_nl, *d_rows;
+    ArenaLayout L;
+    L.add(&d_off, (size_t)n_games + 1);
+    L.add(&d_moves, (size_t)P);
+    L.add(&d_hoff, (size_t)P);
+    L.add(&d_plen, (size_t)P);
+    L.add(&d_pgame, (size_t)P);
+    L.add(&d_hist, max_rec);
+    L.add(&d_lm, (size_t)cap * 224);
+    L.add(&d_meta, (size_t)cap * 7);
+    L.add(&d_nl, (size_t)cap);
+    L.add(&d_rows, (size_t)n_games, has_ring);
+    L.add(&d_src, (size_t)P, has_ring);
+    L.add(&d_coff, (size_t)P + 1, !has_ring);
+    L.add(&d_cmv, (size_t)nchild, !has_ring);
+    L.add(&d_cn, (size_t)nchild, !has_ring);
+    std::lock_guard<std::mutex> lk(g_enc_mu);
+    EncArena& A = g_enc_arena[dev];
+    if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
+    if (L.bytes > A.buf.cap) {
+        // the previous call's work still reads the old arena
+        TRY(A.buf.grow(L.bytes, [&A] { return A.used ? hipEventSynchronize(A.ev) : hipSuccess; }));
+        A.used = false;
+    } else if (A.used) {
+        HIPOK(hipStreamWaitEvent(st, A.ev, 0));   // ... possibly on another stream
+    }
+    ArenaRelease guard{A, st};
+    guard.armed = true;
+    L.bind(A.buf.p);
+    HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
+    if (ring) {
+        HIPOK(hipMemcpyAsync(d_rows, ring->rows, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
+    } else {
+        if (P) HIPOK(hipMemcpyAsync(d_moves, moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
+        HIPOK(hipMemcpyAsync(d_coff, child_off, ((size_t)P + 1) * 4, hipMemcpyHostToDevice, st));
+        if (nchild) {
+            HIPOK(hipMemcpyAsync(d_cmv, child_mv, (size_t)nchild * 2, hipMemcpyHostToDevice, st));
+            HIPOK(hipMemcpyAsync(d_cn, child_n, (size_t)nchild * 4, hipMemcpyHostToDevice, st));
+        }
+    }
+    HIPOK(hipMemsetAsync(o.status, 0x7f, (size_t)n_games * 4, st));   // sc::STATUS_NONE: no failing ply yet
+    const size_t bsz = o.layout == 1 ? 4 : 1, msz = 4;
+    for (const Group& gr : groups) {
+        const uint32_t p0 = ply_off[gr.g0], p1 = ply_off[gr.g0 + gr.ng];
+        if (p1 == p0) continue;
+        scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, d_rows, ring ? ring->p->num_steps : 0,
+                       ring ? ring->p->t_move : nullptr, d_moves, d_src, st);
+        scl::replay_games(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st);
+        for (uint32_t c0 = p0; c0 < p1; c0 += CH) {
+            const uint32_t n = std::min(CH, p1 - c0);
+            scl::encode_plies(o.layout, (int)n, d_hist, d_hoff + c0, d_plen + c0,
+                              o.boards ? static_cast<char*>(o.boards) + (size_t)c0 * 7168 * bsz : nullptr, d_meta, d_lm,
+                              o.legal_idx ? o.legal_idx + (size_t)c0 * 224 : nullptr, d_nl, st);
+            scl::steps_dist((int)n, d_lm, d_nl, d_moves + c0, ring ? ring->p->t_cmove : d_cmv,
+                            ring ? reinterpret_cast<const uint32_t*>(ring->p->t_cn) : d_cn, ring ? nullptr : d_coff + c0,
+                            ring ? d_src + c0 : nullptr, ring ? ring->p->t_nchild : nullptr, d_pgame + c0, d_plen + c0, apply_mirror,
+                            d_meta, o.layout, o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr,
+                            o.dist ? o.dist + (size_t)c0 * 4672 : nullptr, o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr,
+                            o.n_legal ? o.n_legal + c0 : nullptr, o.status, st);
+        }
+    }
+    scl::status_final(n_games, o.status, st);
+    HIPOK(hipGetLastError());
+    return 0;
+}
+
+// the host trace arrays of sc_encode_steps / sc_encode_steps_device
+static int check_traces(int n_games, const uint32_t* move_off, const uint32_t* child_off) {
+    uint32_t maxlen = 0;
+    for (int g = 0; g < n_games; g++) {
+        if (move_off[g + 1] < move_off[g]) return fail("move_off not monotonic");
+        maxlen = std::max(maxlen, move_off[g + 1] - move_off[g]);
+    }
+    if (maxlen > 4000) return fail("move list too long");
+    for (uint32_t p = 0; p < move_off[n_games]; p++)
+        if (child_off[p + 1] < child_off[p] || child_off[p + 1] - child_off[p] > 224) return fail("child_off: more than 224 children or not monotonic");
+    return 0;
+}
+
+extern "C" {
+
+int sc_encode_steps_device(sc_engine* e, int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off,
+                           const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int layout,
+                           void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
+                           int32_t* n_legal, int32_t* status) {
+    if (n_games < 0 || !move_off || !child_off || !status) return fail("bad argument");
+    TRY(use_device(e, device_id));
+    const int dev = e ? e->device : device_id;
+    const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
+    TRY(check_device_outputs(o, dev));
+    if (n_games == 0) return 0;
+    TRY(check_traces(n_games, move_off, child_off));
+    const uint32_t total = move_off[n_games];
+    if (total && !moves) return fail("bad argument");
+    if (child_off[total] && (!child_mv || !child_n)) return fail("bad argument");
+    return encode_device_core(dev, n_games, move_off, moves, child_mv, child_n, child_off, nullptr, apply_mirror, o,
+                              static_cast<hipStream_t>(stream));
+}
+
+namespace {
+struct EncStaging {   // sc_encode_steps's device staging and timing events: released on every path out of the call
+    ScopedDev<char> buf;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~EncStaging() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+}  // namespace
+
+// the host-pointer form: encode_device_core (layout 0) into staging, slice by slice, and out through PCIe
+int sc_encode_steps(sc_engine* e, int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off,
+                    const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int8_t* boards,
+                    int32_t* meta, float* dist, uint16_t* legal_idx, int32_t* n_legal, int32_t* status) {
+    if (n_games < 0 || !move_off || !child_off || !status) return fail("bad argument");
+    if (n_games == 0) return 0;
+    const auto t_call = std::chrono::steady_clock::now();
+    TRY(use_device(e, device_id));
+    const int dev = e ? e->device : device_id;
+    std::fill(status, status + n_games, 0);
+    TRY(check_traces(n_games, move_off, child_off));
+    const uint32_t total = move_off[n_games];
+    if (total == 0) return 0;
+    // a slice: consecutive whole games of at most CH plies together (one game alone has at most 4000), which bounds the staging
+    // at CH * 26 KB when every output is asked for
+    const uint32_t CH = 8192, cap = std::min(CH, total);
+    int32_t *d_status, *d_nl;
+    char *d_boards, *d_meta;
+    float* d_dist;
+    uint16_t* d_li;
+    ArenaLayout L;   // (an output the caller does not ask for is not staged)
+    L.add(&d_status, (size_t)n_games);
+    L.add(&d_boards, (size_t)cap * 7168, boards != nullptr);
+    L.add(&d_meta, (size_t)cap * 28, meta != nullptr);
+    L.add(&d_dist, (size_t)cap * 4672, dist != nullptr);
+    L.add(&d_li, (size_t)cap * 224, legal_idx != nullptr);
+    L.add(&d_nl, (size_t)cap, n_legal != nullptr);
+    EncStaging S;
+    HIPOK(S.buf.alloc(L.bytes));
+    HIPOK(hipEventCreate(&S.ev[0]));
+    HIPOK(hipEventCreate(&S.ev[1]));
+    L.bind(S.buf.p);
+    const hipStream_t st = e ? e->stream : nullptr;
+    std::vector<uint32_t> moff, coff;   // the slice's offsets, rebased; uploaded asynchronously: alive until the slice's synchronisation
+    float kernels_ms = 0.f;
+    for (int g0 = 0, g1; g0 < n_games; g0 = g1) {
+        const uint32_t p0 = move_off[g0], c0 = child_off[p0];
+        for (g1 = g0 + 1; g1 < n_games && move_off[g1 + 1] - p0 <= CH; g1++) {}
+        const uint32_t n = move_off[g1] - p0;
+        moff.assign(move_off + g0, move_off + g1 + 1);
+        coff.assign(child_off + p0, child_off + p0 + n + 1);
+        for (uint32_t& x : moff) x -= p0;
+        for (uint32_t& x : coff) x -= c0;
+        const DevEncodeOut o{0, d_boards, d_meta, d_dist, nullptr, d_li, d_nl, d_status + g0};
+        HIPOK(hipEventRecord(S.ev[0], st));
+        TRY(encode_device_core(dev, g1 - g0, moff.data(), moves + p0, child_mv + c0, child_n + c0, coff.data(), nullptr, apply_mirror, o, st));
+        HIPOK(hipEventRecord(S.ev[1], st));
+        HIPOK(hipStreamSynchronize(st));
+        float ms = 0.f;
+        HIPOK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        kernels_ms += ms;
+        if (boards) HIPOK(hipMemcpy(boards + (size_t)p0 * 7168, o.boards, (size_t)n * 7168, hipMemcpyDeviceToHost));
+        if (meta) HIPOK(hipMemcpy(meta + (size_t)p0 * 7, o.meta, (size_t)n * 28, hipMemcpyDeviceToHost));
+        if (dist) HIPOK(hipMemcpy(dist + (size_t)p0 * 4672, o.dist, (size_t)n * 4672 * 4, hipMemcpyDeviceToHost));
+        if (legal_idx) HIPOK(hipMemcpy(legal_idx + (size_t)p0 * 224, o.legal_idx, (size_t)n * 448, hipMemcpyDeviceToHost));
+        if (n_legal) HIPOK(hipMemcpy(n_legal + p0, o.n_legal, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    HIPOK(hipMemcpy(status, d_status, (size_t)n_games * 4, hipMemcpyDeviceToHost));
+    g_encode_ms[0] = kernels_ms;
+    g_encode_ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return 0;
+}
+
+int sc_encode_steps_last_timing(float* kernels_ms, float* total_ms) {
+    if (kernels_ms) *kernels_ms = g_encode_ms[0];
+    if (total_ms) *total_ms = g_encode_ms[1];
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,242 @@
+// host_common.hpp -- what the host units of libsc_engine.so share (engine.hip, encode_steps.hip, device_calls.hip, selfplay.hip,
+// selfplay_io.hip): error state, the handles' structs and one helper for each piece of plumbing.  Host only: no kernel unit
+// includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <assert.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <initializer_list>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/sc_engine.h"
+#include "launchers.hpp"
+
+#pragma GCC visibility push(hidden)   // internal to the library: only the C ABI is exported
+
+// ------------------------------------------------------------------ errors
+extern thread_local std::string g_err;   // sc_last_error() of this thread (engine.hip)
+int fail(const std::string& m, int code = -1);
+#define HIPOK(expr)                                                                                   \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_), -2);     \
+    } while (0)
+// a call that has already reported its failure (fail / HIPOK): pass its return code on
+#define TRY(expr)                    \
+    do {                             \
+        const int rc_ = (expr);      \
+        if (rc_) return rc_;         \
+    } while (0)
+
+// ------------------------------------------------------------------ device memory
+template <class T>
+static hipError_t dalloc(T** p, size_t n) {
+    return hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T));
+}
+// cleanup paths: free a list of device pointers, ignoring errors
+static inline void dfree(std::initializer_list<void*> ptrs) {
+    for (void* q : ptrs)
+        if (q) (void)hipFree(q);
+}
+
+// "no HIP device" (-3), "device_id out of range" (-1), hipSetDevice: the opening of every call that names its device, which is
+// the engine's if there is one, else device_id.  The engine is not looked at before a device has been found.
+int use_device(const sc_engine* e, int device_id);
+
+// a call-local device buffer, freed on every path out of the call
+template <class T>
+struct ScopedDev {
+    T* p = nullptr;
+    ScopedDev() = default;
+    ScopedDev(const ScopedDev&) = delete;
+    ScopedDev& operator=(const ScopedDev&) = delete;
+    ~ScopedDev() { dfree({p}); }
+    hipError_t alloc(size_t n) { return dalloc(&p, n); }
+};
+
+// a device buffer that is kept and grown on demand (cap in elements).  Growing frees the old buffer: wait() is called first and
+// returns once nothing on the device uses it any more.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    template <class Wait>
+    int grow(size_t want, Wait wait) {
+        if (want <= cap) return 0;
+        HIPOK(wait());
+        release();
+        HIPOK(dalloc(&p, want));
+        cap = want;
+        return 0;
+    }
+    void release() {
+        dfree({p});
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// The regions of one device allocation.  add() registers a pointer and the elements it needs, bytes is then the size to
+// allocate, bind() points every registered pointer into the block.  Regions start 256 bytes apart at least and hold one byte at
+// least; a region that is not wanted takes no room and its pointer stays null.
+struct ArenaLayout {
+    struct Region {
+        void* slot;
+        size_t off;
+        void (*set)(void* slot, char* at);
+    };
+    Region regions[16];
+    int n = 0;
+    size_t bytes = 0;
+    template <class T>
+    void add(T** slot, size_t count, bool wanted = true) {
+        *slot = nullptr;
+        if (!wanted) return;
+        assert(n < 16);
+        regions[n++] = {slot, bytes, [](void* s, char* at) { *static_cast<T**>(s) = reinterpret_cast<T*>(at); }};
+        bytes += (std::max<size_t>(count * sizeof(T), 1) + 255) & ~(size_t)255;
+    }
+    void bind(void* base) const {
+        for (int i = 0; i < n; i++) regions[i].set(regions[i].slot, static_cast<char*>(base) + regions[i].off);
+    }
+};
+
+// ------------------------------------------------------------------ the engine
+struct sc_engine {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    scnn::NetDev net{};
+    uint16_t* d_wb = nullptr;
+    float* d_wf = nullptr;
+    int n_cu = 256;    // compute units of the device
+    int step_blocks_per_cu = 1;   // resident fused step workgroups per CU for this network (1 or 2)
+    int ksplit = 64;   // split-K of value_head.ffn.0 (the search kernel's fused tail sums 32 or 64 partials)
+    // scratch of the host-pointer calls and of self-play, grown on demand (engine_reserve: all for the same number of positions)
+    DevBuf<int8_t> d_boards;
+    DevBuf<int32_t> d_meta;
+    DevBuf<uint16_t> d_lidx;
+    DevBuf<int32_t> d_nlegal;
+    DevBuf<float> d_prior;
+    DevBuf<float> d_value;
+    DevBuf<float> d_logp;
+    DevBuf<float> d_dbg;
+    // scratch arena of sc_encode_positions (Level-1 callers encode one position per call: no malloc/free per call)
+    DevBuf<char> d_enc;
+    // the one-slot handle sc_search keeps between calls (NNPlayer::bestmove calls it once per move: building and freeing ~35 device
+    // buffers per call cost more than a short search) and the rollout its node pools are sized for
+    struct sc_selfplay* search_sp = nullptr;
+    int search_rollout_cap = 0;
+    // d_hval / d_vpart grow by themselves (engine_reserve_hv): the device-pointer entry points (sc_forward_device,
+    // sc_score_positions, sc_compare_engines) run enqueue_forward on the caller's tensors and need only these two, for one slice.
+    // Their other scratch: the slice's values and log-probability rows (scoring only), and per-position results the caller did not
+    // ask for but the summary needs.  dv_ev orders those calls (any stream) and the engine's stream after each other.
+    DevBuf<scnn::bf16_t> d_hval;
+    DevBuf<float> d_vpart;
+    DevBuf<float> dv_value;
+    DevBuf<float> dv_logp;
+    DevBuf<float> dv_pp;
+    hipEvent_t dv_ev = nullptr;
+};
+
+// growing a scratch buffer of the engine waits on the host for the engine's stream: its earlier work may use the old buffer
+template <class T>
+static int engine_grow(sc_engine* e, DevBuf<T>& b, size_t want) {
+    return b.grow(want, [e] { return hipStreamSynchronize(e->stream); });
+}
+int engine_reserve(sc_engine* e, int n);      // all scratch of n positions (at least 64)
+int engine_reserve_hv(sc_engine* e, int n);   // value-head features and split-K partials of n positions (enqueue_forward's scratch)
+
+// the argument blocks of the tower and of value_head.ffn.0 for n positions of network e
+scnn::TowerArgs tower_args(const sc_engine* e, int n, const int8_t* boards, const int32_t* meta, int meta_stride, const uint16_t* lidx,
+                           const int32_t* nlegal, float* prior, float* logp, scnn::bf16_t* hval, float* dbg = nullptr, int dbg_stage = -1);
+scnn::Fc1Args fc1_args(const sc_engine* e, int n, const scnn::bf16_t* hval, float* vpart);
+// enqueue the three network kernels for n positions (device pointers)
+void enqueue_forward(sc_engine* e, int n, const int8_t* boards, const int32_t* meta, int meta_stride, const uint16_t* lidx,
+                     const int32_t* nlegal, float* prior, float* value, float* logp, float* dbg, int dbg_stage, hipStream_t s);
+
+// ------------------------------------------------------------------ training tensors on the device (encode_steps.hip)
+struct DevEncodeOut {
+    int layout;
+    void* boards;
+    void* meta;
+    float* dist;
+    float* dist_legal;
+    uint16_t* legal_idx;
+    int32_t* n_legal;
+    int32_t* status;
+};
+// the trace ring as the encoder's source (sc_selfplay_encode_traces)
+struct RingSrc {
+    const int32_t* rows;   // host: ring row of each requested game
+    const sc::SpParams* p;
+};
+// pointers the kernels of a call read or write must be device memory of `dev`; null entries are skipped
+int check_device_ptrs(std::initializer_list<std::pair<const void*, const char*>> ptrs, int dev);
+int check_device_outputs(const DevEncodeOut& o, int dev);
+int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
+                       const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
+                       hipStream_t st);
+
+// ------------------------------------------------------------------ self-play (selfplay.hip, selfplay_io.hip)
+struct sc_selfplay {
+    sc_engine* engine = nullptr;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    sc_selfplay_config cfg{};
+    sc::SpParams p{};
+    std::vector<void*> allocs;
+    int64_t sim_steps_enqueued = 0;
+    // timing
+    int timing_stride = 0;       // > 0: every n-th step runs as separate launches with the TOWER bracketed by an event pair
+    int step_stride = 0;         // > 0: every n-th step is bracketed as a whole, in the handle's own launch form
+    std::vector<hipEvent_t> ev;  // pairs
+    int ev_next = 0;
+    int64_t ev_recorded = 0;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    bool have_span = false;
+    int64_t nn_launches = 0;
+    bool pending_final = false;
+    // match play (sc_selfplay_set_players): player of even / odd plies
+    bool match = false;
+    sc_engine* player[2] = {nullptr, nullptr};
+    uint64_t salt[2] = {0, 0};
+    scnn::bf16_t* d_hval = nullptr;  // value-head features of the current leaves [n_slots][64][256]
+    float* d_vpart = nullptr;        // split-K partials of value_head.ffn.0 [ksplit][n_slots][128]
+    // streaming drain (sc_selfplay_poll): per trace-ring row, the game id last reported to the host (+1; 0 = none)
+    std::vector<uint64_t> reported;
+    std::vector<int> to_release;     // rows handed out by the previous poll (trace_hold)
+    // sc_selfplay_encode_traces: recorded on the caller's stream behind the last encode that read ring rows; the next poll
+    // waits for it before it releases rows
+    hipEvent_t enc_ev = nullptr;
+    bool enc_pending = false;
+    // search wave + tower in one launch (step_kernels.hip).  Chosen at creation: only with at most one game per compute
+    // unit and a single group -- with more games than CUs the separate search launch runs all of them at once while the
+    // fused workgroups (83 KB of LDS: one per CU) would take turns, and with several interleaved groups one group's search
+    // launch is what hides under another group's tower (measured: 512 games 3.48 M vs 3.02 M simulations/s at fp8, two
+    // groups of 256 2.65 M vs 2.38 M at bf16, in favour of the separate launches)
+    bool fused = false;
+    bool fc1_in_step = false;        // ... and value_head.ffn.0 runs inside that launch too (one launch per simulation step)
+    uint32_t* d_fc1_ctr = nullptr;   // its arrival counters, one per 64-position block, 128 B apart (monotonic)
+    uint32_t fc1_launches = 0;       // step launches that counted on them so far
+    uint32_t fc1_target_skew = 0;    // test aid (sc_selfplay_debug_break_handoff): arrivals that will never come
+    // An internal hand-off of a step launch timed out (error_flags & (16 | 32)): tiles were computed from stale rows, the
+    // values backed up since are wrong.  Latched when the host first sees the flag; from then on the handle refuses work.
+    bool poisoned = false;
+};
+
+int sp_refuse(const sc_selfplay* sp);   // the error of a poisoned handle
+// complete the last enqueued simulation (expand / backward / ply transition) so that host reads see a fully backed-up state; a
+// following enqueue would have done the same work in its first launch
+void sp_flush(sc_selfplay* sp);
+int sp_latch(sc_selfplay* sp);   // called with the stream idle: looks at the device's error word
+// the opening of a host read or write: set the device, sp_flush, wait for the stream; with `latch` also sp_latch, and refuse a
+// poisoned handle
+int sp_quiesce(sc_selfplay* sp, bool latch);
+
+#pragma GCC visibility pop

@@ -838,7 +838,7 @@ __device__ inline void finish_game(SpParams& p, int g, int lane, int has_outcome
 // child; *total = the f32 sum of the weights of the weighted branch (0 at temperature 0).  The one implementation: the
 // self-play kernels and the test aid k_debug_choose_child (sc_debug_choose_child) both call it.
 // The weight N^(1/temperature) is READ from w[0..w_max], which the host filled with ITS libm's powf for this temperature
-// (engine.hip choice_weights): the reference's f32::powf is that function, and the index below must be the reference's bit for
+// (selfplay.hip choice_weights): the reference's f32::powf is that function, and the index below must be the reference's bit for
 // bit -- the device's own powf is one ulp off it for a quarter of all (count, temperature) pairs.  Temperature 1
 // (the temperature-switch window) needs no table: powf(n, 1) == n.  A count never exceeds the ply's simulation budget, which
 // the table covers; the index is clamped all the same so that no read can leave the table.
@@ -929,7 +929,7 @@ __device__ __forceinline__ void value_tail_issue(const SpParams& p, int g, int l
     const int j = 2 * lane;
     const float* vp = p.vpart + (size_t)g * 128 + j;
     const size_t vstride = (size_t)p.n_slots * 128;
-    // split-K is 32 or 64 (engine.hip): two unconditional batches -- a per-partial bound check makes the compiler
+    // split-K is 32 or 64 (host_common.hpp): two unconditional batches -- a per-partial bound check makes the compiler
     // branch around (and wait for) every single load
 #pragma unroll
     for (int ks = 0; ks < 32; ks++) t.acc[ks] = *reinterpret_cast<const float2*>(vp + (size_t)ks * vstride);

@@ -4,7 +4,7 @@
 // Replaces, for positions already in device memory, the arithmetic of the reference's scripts/train.py validation_step
 // (compute_loss1 / compute_loss2, pi_entropy) and scripts/validate_model.py (total variation, |value1 - value2|).
 //
-// The tower, value_fc1 and value_finish are launched unchanged (engine.hip); these kernels only READ what they wrote.
+// The tower, value_fc1 and value_finish are launched unchanged (device_calls.hip); these kernels only READ what they wrote.
 //
 //   k_score / k_compare   one wavefront per position (four positions per workgroup).  A row is 4672 floats = 1168 16-byte
 //       loads: lane l takes chunks l, l + 64, ..., l + 64 * 18 (the last index clamped to the row and masked in the arithmetic, so

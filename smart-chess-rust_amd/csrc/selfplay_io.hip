@@ -1,0 +1,322 @@
+// selfplay_io.hip -- host side of libsc_engine.so: what the host reads from and writes to a self-play handle (drain, traces,
+// tree / slot / noise / position accessors) and sc_search, which drives a one-slot handle through them.
+#include <string.h>
+
+#include "host_common.hpp"
+
+// A row that sc_selfplay_poll has reported and holds (trace_hold) is final, and no kernel writes it until the next poll releases it
+static bool row_held(const sc_selfplay* sp, int row, uint64_t want_id) {
+    return sp->p.trace_hold && sp->reported[(size_t)row] == want_id + 1 &&
+           std::find(sp->to_release.begin(), sp->to_release.end(), row) != sp->to_release.end();
+}
+// the ring row may belong to an earlier game (the wanted one has not started), to a later one (overwritten) or be released
+enum RowState { ROW_READY, ROW_NOT_FINISHED, ROW_GONE };
+static RowState row_state(const sc_selfplay* sp, int row, uint64_t want_id, const sc::TraceHdr& h) {
+    if (h.state == sc::TR_FREE) return sp->reported[(size_t)row] > want_id ? ROW_GONE : ROW_NOT_FINISHED;
+    if (h.game_id > want_id) return ROW_GONE;
+    return h.game_id < want_id || h.state != sc::TR_DONE ? ROW_NOT_FINISHED : ROW_READY;
+}
+
+extern "C" {
+
+int sc_selfplay_get_trace(sc_selfplay* sp, int game, sc_trace_info* info, uint16_t* step_move, float* step_q,
+                          int32_t* child_off, uint16_t* child_move, int32_t* child_n, float* child_q, float* child_uct) {
+    if (!sp || !info || game < 0 || game >= sp->p.total_games) return fail("bad argument");
+    const uint64_t want_id = sp->p.first_game_id + (uint64_t)game;
+    game %= sp->p.trace_cap;
+    if (sp->poisoned) return sp_refuse(sp);
+    // A held row is read without waiting for the stream, so a consumer can enqueue the next simulation steps first and fetch /
+    // write the finished traces while they run (the copies below are on the NULL stream; the launch stream is non-blocking).
+    // Anything else is read from an idle stream.
+    if (row_held(sp, game, want_id)) HIPOK(hipSetDevice(sp->device));
+    else TRY(sp_quiesce(sp, true));
+    const sc::SpParams& p = sp->p;
+    sc::TraceHdr h;
+    HIPOK(hipMemcpy(&h, p.thdr + game, sizeof h, hipMemcpyDeviceToHost));
+    switch (row_state(sp, game, want_id, h)) {
+        case ROW_NOT_FINISHED: return fail("game not finished", 1);
+        case ROW_GONE: return fail(h.state == sc::TR_FREE ? "trace released or overwritten" : "trace overwritten by a later game (trace_capacity ring)", 2);
+        case ROW_READY: break;
+    }
+    const size_t S = (size_t)p.num_steps, base = (size_t)game * S;
+    int ns = h.n_steps;
+    std::vector<int32_t> nch((size_t)std::max(ns, 1));
+    if (ns) HIPOK(hipMemcpy(nch.data(), p.t_nchild + base, (size_t)ns * 4, hipMemcpyDeviceToHost));
+    int total = 0;
+    for (int i = 0; i < ns; i++) total += nch[(size_t)i];
+    info->n_steps = ns;
+    info->n_children_total = total;
+    info->has_outcome = h.has_outcome;
+    info->termination = h.termination;
+    info->winner = h.winner;
+    info->game_id = h.game_id;
+    if (step_move && ns) HIPOK(hipMemcpy(step_move, p.t_move + base, (size_t)ns * 2, hipMemcpyDeviceToHost));
+    if (step_q && ns) HIPOK(hipMemcpy(step_q, p.t_q + base, (size_t)ns * 4, hipMemcpyDeviceToHost));
+    if (child_off) {
+        int off = 0;
+        for (int i = 0; i < ns; i++) {
+            child_off[i] = off;
+            off += nch[(size_t)i];
+        }
+        child_off[ns] = off;
+    }
+    if ((child_move || child_n || child_q || child_uct) && ns) {
+        // one copy per array for the whole game (rows of 224 entries per ply), compacted on the host: a copy per ply and
+        // array cost more than the games themselves when many short games stream out
+        const size_t rows = (size_t)ns * 224, src = base * 224;
+        std::vector<uint16_t> mv(child_move ? rows : 0);
+        std::vector<int32_t> cn(child_n ? rows : 0);
+        std::vector<float> cq(child_q ? rows : 0), cu(child_uct ? rows : 0);
+        if (child_move) HIPOK(hipMemcpy(mv.data(), p.t_cmove + src, rows * 2, hipMemcpyDeviceToHost));
+        if (child_n) HIPOK(hipMemcpy(cn.data(), p.t_cn + src, rows * 4, hipMemcpyDeviceToHost));
+        if (child_q) HIPOK(hipMemcpy(cq.data(), p.t_cq + src, rows * 4, hipMemcpyDeviceToHost));
+        if (child_uct) HIPOK(hipMemcpy(cu.data(), p.t_cu + src, rows * 4, hipMemcpyDeviceToHost));
+        int off = 0;
+        for (int i = 0; i < ns; i++) {
+            const size_t n = (size_t)nch[(size_t)i], r0 = (size_t)i * 224;
+            if (child_move) memcpy(child_move + off, mv.data() + r0, n * 2);
+            if (child_n) memcpy(child_n + off, cn.data() + r0, n * 4);
+            if (child_q) memcpy(child_q + off, cq.data() + r0, n * 4);
+            if (child_uct) memcpy(child_uct + off, cu.data() + r0, n * 4);
+            off += (int)n;
+        }
+    }
+    return 0;
+}
+
+int sc_selfplay_poll(sc_selfplay* sp, int32_t* finished_games, int cap) {
+    if (!sp || cap < 0 || (cap > 0 && !finished_games)) return fail("bad argument");
+    if (sp->poisoned) return sp_refuse(sp);
+    TRY(sp_quiesce(sp, true));   // (poisoned by this batch: nothing of it is reported, the games that "finished" are not real)
+    const sc::SpParams& p = sp->p;
+    // an encode of held rows may still be reading them on its own stream
+    if (sp->enc_pending) {
+        HIPOK(hipEventSynchronize(sp->enc_ev));
+        sp->enc_pending = false;
+    }
+    // rows handed out by the previous poll go back to the device (the stream is idle: no kernel reads them now)
+    for (int row : sp->to_release) {
+        const int32_t free_state = sc::TR_FREE;
+        HIPOK(hipMemcpy(reinterpret_cast<char*>(p.thdr + row) + offsetof(sc::TraceHdr, state), &free_state, 4, hipMemcpyHostToDevice));
+    }
+    sp->to_release.clear();
+    std::vector<sc::TraceHdr> hdr((size_t)p.trace_cap);
+    HIPOK(hipMemcpy(hdr.data(), p.thdr, hdr.size() * sizeof(sc::TraceHdr), hipMemcpyDeviceToHost));
+    // oldest games first: a consumer that writes trace{N}.json sees them in the order the reference's jobs would finish
+    std::vector<std::pair<uint64_t, int>> fin;
+    for (int row = 0; row < p.trace_cap; row++) {
+        const sc::TraceHdr& h = hdr[(size_t)row];
+        if (h.state == sc::TR_DONE && sp->reported[(size_t)row] != h.game_id + 1) fin.emplace_back(h.game_id, row);
+    }
+    std::sort(fin.begin(), fin.end());
+    int n = 0;
+    for (auto& f : fin) {
+        if (n >= cap) break;
+        finished_games[n++] = (int32_t)(f.first - p.first_game_id);
+        sp->reported[(size_t)f.second] = f.first + 1;
+        if (p.trace_hold) sp->to_release.push_back(f.second);
+    }
+    return n;
+}
+
+int sc_selfplay_encode_traces(sc_selfplay* sp, int n, const int32_t* games, int apply_mirror, int layout, void* stream, uint32_t* ply_off,
+                              void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal,
+                              int32_t* status) {
+    if (!sp || n < 0 || (n > 0 && !games) || !ply_off) return fail("bad argument");
+    if (sp->poisoned) return sp_refuse(sp);
+    const sc::SpParams& p = sp->p;
+    std::vector<int32_t> rows((size_t)std::max(n, 1));
+    bool all_held = true;
+    for (int i = 0; i < n; i++) {
+        const int g = games[i];
+        if (g < 0 || g >= p.total_games) return fail("bad argument: game index out of range");
+        const int row = g % p.trace_cap;
+        rows[(size_t)i] = row;
+        all_held = all_held && row_held(sp, row, p.first_game_id + (uint64_t)g);   // the readiness rules of sc_selfplay_get_trace
+    }
+    if (all_held) HIPOK(hipSetDevice(sp->device));
+    else TRY(sp_quiesce(sp, true));
+    std::vector<sc::TraceHdr> hdr((size_t)p.trace_cap);
+    HIPOK(hipMemcpy(hdr.data(), p.thdr, hdr.size() * sizeof(sc::TraceHdr), hipMemcpyDeviceToHost));
+    int not_finished = 0, gone = 0;
+    ply_off[0] = 0;
+    for (int i = 0; i < n; i++) {
+        const sc::TraceHdr& h = hdr[(size_t)rows[(size_t)i]];
+        const RowState rs = row_state(sp, rows[(size_t)i], p.first_game_id + (uint64_t)games[i], h);
+        gone |= rs == ROW_GONE;
+        not_finished |= rs == ROW_NOT_FINISHED;
+        ply_off[i + 1] = ply_off[i] + (uint32_t)std::max(h.n_steps, 0);
+    }
+    if (gone) return fail("trace released or overwritten (trace_capacity ring)", 2);
+    if (not_finished) return fail("game not finished", 1);
+    if (!boards && !meta && !dist && !dist_legal && !legal_idx && !n_legal && !status) return 0;   // sizing call
+    if (!status) return fail("bad argument: status is required");
+    const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
+    TRY(check_device_outputs(o, sp->device));
+    if (n == 0) return 0;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const RingSrc ring{rows.data(), &p};
+    TRY(encode_device_core(sp->device, n, ply_off, nullptr, nullptr, nullptr, nullptr, &ring, apply_mirror, o, st));
+    // the rows are read on `st`: the next poll (held rows) waits for that before it releases them, and a row that is not held
+    // could be reused by a new game -- the handle's next steps then wait for the encode on the device
+    if (!sp->enc_ev) HIPOK(hipEventCreateWithFlags(&sp->enc_ev, hipEventDisableTiming));
+    HIPOK(hipEventRecord(sp->enc_ev, st));
+    sp->enc_pending = true;
+    if (!all_held) HIPOK(hipStreamWaitEvent(sp->stream, sp->enc_ev, 0));
+    return 0;
+}
+
+int sc_selfplay_write_trace_json(sc_selfplay* sp, int game, const char* path) {
+    sc_trace_info info;
+    TRY(sc_selfplay_get_trace(sp, game, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    std::vector<uint16_t> sm((size_t)info.n_steps + 1), cm((size_t)info.n_children_total + 1);
+    std::vector<float> sq((size_t)info.n_steps + 1), cq((size_t)info.n_children_total + 1), cu((size_t)info.n_children_total + 1);
+    std::vector<int32_t> co((size_t)info.n_steps + 2), cn((size_t)info.n_children_total + 1);
+    TRY(sc_selfplay_get_trace(sp, game, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data()));
+    return sc_trace_write_json(path, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data());
+}
+
+int sc_selfplay_get_tree(sc_selfplay* sp, int slot, int cap, int32_t* n, float* q, float* uct, float* prior, uint16_t* move,
+                         int32_t* first_child, int32_t* n_child) {
+    if (!sp || slot < 0 || slot >= sp->p.n_slots) return fail("bad argument");
+    TRY(sp_quiesce(sp, false));
+    const sc::SpParams& p = sp->p;
+    sc::GameCtl c;
+    HIPOK(hipMemcpy(&c, p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
+    int nn = std::min(c.n_nodes, cap);
+    size_t nb = (size_t)slot * p.node_cap;
+    if (nn > 0) {
+        if (n) HIPOK(hipMemcpy(n, p.N + nb, (size_t)nn * 4, hipMemcpyDeviceToHost));
+        if (q) HIPOK(hipMemcpy(q, p.W + nb, (size_t)nn * 4, hipMemcpyDeviceToHost));
+        if (uct) HIPOK(hipMemcpy(uct, p.U + nb, (size_t)nn * 4, hipMemcpyDeviceToHost));
+        if (prior) HIPOK(hipMemcpy(prior, p.P + nb, (size_t)nn * 4, hipMemcpyDeviceToHost));
+        if (move) HIPOK(hipMemcpy(move, p.MV + nb, (size_t)nn * 2, hipMemcpyDeviceToHost));
+        if (first_child || n_child) {
+            std::vector<sc::NodeHdr> t((size_t)nn);
+            HIPOK(hipMemcpy(t.data(), p.H + nb, (size_t)nn * sizeof(sc::NodeHdr), hipMemcpyDeviceToHost));
+            for (int i = 0; i < nn; i++) {
+                if (first_child) first_child[i] = t[(size_t)i].fc;
+                if (n_child) n_child[i] = t[(size_t)i].nc;
+            }
+        }
+    }
+    return c.n_nodes;
+}
+
+int sc_selfplay_get_slot(sc_selfplay* sp, int slot, int32_t* ply, int32_t* sim, int32_t* status, uint64_t* game_id,
+                         int32_t* last_path, int32_t* last_path_len) {
+    if (!sp || slot < 0 || slot >= sp->p.n_slots) return fail("bad argument");
+    TRY(sp_quiesce(sp, false));
+    sc::GameCtl c;
+    HIPOK(hipMemcpy(&c, sp->p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
+    if (ply) *ply = c.ply;
+    if (sim) *sim = c.sim;
+    if (status) *status = c.status;
+    if (game_id) *game_id = c.game_id;
+    if (last_path_len) *last_path_len = c.path_len;
+    if (last_path && c.path_len > 0)
+        HIPOK(hipMemcpy(last_path, sp->p.path + (size_t)slot * sp->p.max_depth, (size_t)std::min(c.path_len, 1024) * 4,
+                        hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sc_selfplay_set_noise(sc_selfplay* sp, int slot, const float* noise, int n) {
+    if (!sp || slot < 0 || slot >= sp->p.n_slots || n < 0 || n > 224) return fail("bad argument");
+    TRY(sp_quiesce(sp, false));
+    HIPOK(hipMemcpy(sp->p.noise + (size_t)slot * 224, noise, (size_t)n * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+int sc_selfplay_get_noise(sc_selfplay* sp, int slot, float* noise, int cap) {
+    if (!sp || slot < 0 || slot >= sp->p.n_slots) return fail("bad argument");
+    TRY(sp_quiesce(sp, false));
+    HIPOK(hipMemcpy(noise, sp->p.noise + (size_t)slot * 224, (size_t)std::min(cap, 224) * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sc_selfplay_set_position(sc_selfplay* sp, int slot, const uint16_t* moves, int n_moves) {
+    if (!sp || slot < 0 || slot >= sp->p.n_slots || n_moves < 0 || n_moves > 590) return fail("bad argument");
+    TRY(sp_quiesce(sp, false));
+    {
+        sc::GameCtl c;
+        HIPOK(hipMemcpy(&c, sp->p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
+        if (c.status == sc::ST_PENDING) return fail("slot is waiting for a trace-ring row: no game to reposition");
+    }
+    ScopedDev<uint16_t> d_moves;
+    HIPOK(d_moves.alloc((size_t)n_moves));
+    if (n_moves) HIPOK(hipMemcpy(d_moves.p, moves, (size_t)n_moves * 2, hipMemcpyHostToDevice));
+    scl::set_position(sp->p, slot, d_moves.p, n_moves, sp->stream);
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(sp->stream));
+    return 0;
+}
+
+// One search from a given position: the body of NNPlayer::bestmove (src/play.rs:241-252) / chess_play_mcts
+// (src/lib.rs:233-247) as a single call; see include/sc_engine.h
+int sc_search(sc_engine* e, const uint16_t* moves, int n_moves, int rollout, float cpuct, int with_noise, uint64_t seed,
+              int cap, uint16_t* child_move, int32_t* child_n, float* child_q, float* child_prior, float* root_q) {
+    if (!e || rollout < 1 || rollout >= 60000 || cap < 0) return fail("bad argument");
+    // one cached handle per engine, rebuilt only when a call asks for more simulations than its node pools hold; every call starts
+    // from a fresh one-node tree (sc_selfplay_set_position) with its own options and seed, so the result is that of a new handle
+    int rc = 0;
+    if (e->search_sp && (rollout + 1 > e->search_rollout_cap || e->search_sp->poisoned)) {
+        sc_selfplay_destroy(e->search_sp);
+        e->search_sp = nullptr;
+    }
+    if (!e->search_sp) {
+        sc_selfplay_config c{};
+        c.n_slots = 1;
+        c.n_games = 1;
+        c.rollout_num = std::max(rollout + 1, 512);   // sizes the node pool; more than any call runs, so no ply transition happens
+        c.num_steps = 4000;
+        c.cpuct = cpuct;
+        c.epsilon = 0.15f;         // mcts::mcts(.., 0.15, noise) at both call sites
+        c.with_noise = with_noise ? 1 : 0;
+        c.outcome_gate = 1 << 30;
+        c.evaluator = SC_EVAL_NET;
+        c.seed = seed;
+        rc = sc_selfplay_create(e, e->device, &c, &e->search_sp);
+        if (rc) {
+            e->search_sp = nullptr;
+            return rc;
+        }
+        e->search_rollout_cap = c.rollout_num;
+    }
+    sc_selfplay* sp = e->search_sp;
+    HIPOK(hipSetDevice(e->device));
+    HIPOK(hipStreamSynchronize(sp->stream));
+    sp->p.seed = seed;
+    sp->cfg.seed = seed;
+    rc = sc_selfplay_set_search(sp, cpuct, 0.15f, with_noise);
+    {   // an earlier call's error flags are not this call's
+        const int32_t zero = 0;
+        HIPOK(hipMemcpy(reinterpret_cast<char*>(sp->p.cnt) + offsetof(sc::Counters, err), &zero, 4, hipMemcpyHostToDevice));
+    }
+    if (rc) return rc;
+    rc = sc_selfplay_set_position(sp, 0, moves, n_moves);
+    if (!rc) rc = sc_selfplay_enqueue_sims(sp, rollout);
+    int n_children = 0;
+    if (!rc) {
+        std::vector<int32_t> n(1 + 224), fc(1 + 224), nc(1 + 224);
+        std::vector<float> q(1 + 224), pr(1 + 224);
+        std::vector<uint16_t> mv(1 + 224);
+        int nn = sc_selfplay_get_tree(sp, 0, 1 + 224, n.data(), q.data(), nullptr, pr.data(), mv.data(), fc.data(), nc.data());
+        if (nn < 0) {
+            rc = nn;
+        } else {
+            sc_selfplay_stats st{};
+            rc = sc_selfplay_get_stats(sp, &st);
+            if (!rc && st.error_flags) rc = fail("search error flags set (non-finite PUCT value or pool overflow)", -4);
+            if (root_q) *root_q = nn > 0 ? q[0] : 0.f;
+            n_children = nn > 0 && fc[0] == 1 ? nc[0] : 0;   // the root's children are nodes 1..nc
+            for (int i = 0; i < n_children && i < cap; i++) {
+                if (child_move) child_move[i] = mv[(size_t)1 + i];
+                if (child_n) child_n[i] = n[(size_t)1 + i];
+                if (child_q) child_q[i] = q[(size_t)1 + i];
+                if (child_prior) child_prior[i] = pr[(size_t)1 + i];
+            }
+        }
+    }
+    return rc ? rc : n_children;
+}
+
+}  // extern "C"

@@ -37,7 +37,7 @@ __device__ __forceinline__ float wave_sum_fixed(float v) {
     return (rl(0) + rl(16)) + (rl(32) + rl(48));
 }
 
-// ksplit is 32 or 64 (engine.hip).  Wave-uniform result.
+// ksplit is 32 or 64 (host_common.hpp).  Wave-uniform result.
 __device__ __forceinline__ float value_tail_compute(const ValueTail& t, const int ksplit) {
 #pragma clang fp contract(off)
     float m[7];
