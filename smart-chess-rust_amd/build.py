@@ -39,8 +39,9 @@ def build(force=False, verbose=False):
     hdrs.append(os.path.join(HERE, "..", "include", "sc_engine.h"))
     common = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
     objs = []
-    for src, extra in (("mcts_kernels.hip", ["-ffp-contract=off"]), ("nn_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
-                       ("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("score_kernels.hip", ["-ffp-contract=off"]),
+    for src, extra in (("mcts_kernels.hip", ["-ffp-contract=off"]), ("encode_kernels.hip", ["-ffp-contract=off"]),
+                       ("nn_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
+                       ("score_kernels.hip", ["-ffp-contract=off"]),
                        ("batch_kernels.hip", []), ("engine.hip", []), ("encode_steps.hip", []), ("device_calls.hip", []),
                        ("selfplay.hip", []), ("selfplay_io.hip", [])):
         s = os.path.join(CSRC, src)

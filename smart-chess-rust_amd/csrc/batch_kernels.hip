@@ -16,7 +16,7 @@
 //       dist: the row is built in LDS (zero, barrier, <= 218 stores by wave 3, barrier) and streamed out, 1 168 16-byte stores:
 //       no global address is written twice by a launch.  Only entries i < n_legal are looked at: the padding points at action 0,
 //       which can be a legal move.
-//       The mirror changes meta and the outcome only (mcts_kernels.hpp, k_steps_dist: Board::rotate()'s meta).
+//       The mirror changes meta and the outcome only (encode_kernels.hip, k_steps_dist: Board::rotate()'s meta).
 //   Bad input is contained on the device: a row index outside [0, n_src) reads nothing and leaves NaN in all four outputs of
 //   the sample; n_legal outside 0..218 or an action index >= 4672 among the legal ones stores nothing through it and leaves NaN
 //   in the sample's dist row.  Each adds 1 to n_bad[0] (one integer atomic per bad sample).

@@ -271,7 +271,7 @@ SC_HD bool is_irreversible(const Position& p, move_t m) { return is_zeroing(p, m
 // move -- and leaves key and flags zero: no key terms, no irreversibility test and neither of the two has_legal_ep probes.  The
 // training-tensor encoder walks a game with it, one wave per game and a chain of dependent steps, at ~10 % of what a full
 // make_move + repetition scan per ply cost there (1.9 us per ply, 194 us for 100-ply games), and computes the keys, F_IRREV and
-// the repetition flags of all plies in parallel afterwards (mcts_kernels.hpp: k_replay_raw, k_ply_keys, k_ply_rep).
+// the repetition flags of all plies in parallel afterwards (encode_kernels.hip: k_replay_raw, k_ply_keys, k_ply_rep).
 // tests/test_engine_rules_host.py::test_make_move_board_matches_make_move compares the two instantiations field by field.
 // (make_move is the template itself and not a second name around it: one more level of inlining reorders operands in k_step and
 // k_mcts, and tools/isa_compare.py would no longer show their instruction streams unchanged.)

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "chess_rules.hpp"
+#include "wave_util.hpp"
 
 namespace sc {
 
@@ -21,7 +22,7 @@ namespace sc {
 // scalar work; the xor / shift shuffles they replace were 6-12 dependent trips through the LDS crossbar per call.
 template <int CTRL>
 __device__ __forceinline__ unsigned dpp_u(unsigned x) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);   // lanes without a source read 0
+    return (unsigned)scw::dpp_i<CTRL>((int)x);   // lanes without a source read 0
 }
 __device__ __forceinline__ unsigned wave_or32(unsigned v) {
     v |= dpp_u<0xB1>(v);    // quad_perm [1,0,3,2]
@@ -33,11 +34,6 @@ __device__ __forceinline__ unsigned wave_or32(unsigned v) {
 }
 // OR over the wave; the result is wave-uniform (SGPRs)
 __device__ __forceinline__ bb_t wave_or64(bb_t v) { return ((bb_t)wave_or32((unsigned)(v >> 32)) << 32) | wave_or32((unsigned)v); }
-__device__ __forceinline__ bb_t uniform64(bb_t v) {
-    unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-    unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-    return ((bb_t)hi << 32) | lo;
-}
 // sum of x over the lanes ABOVE this one (lane 63 gets 0), and the wave total in `total`: inclusive suffix scan inside
 // each row (row_shl:n -- lane i reads lane i+n of its row, 0 past the row's end), then the totals of the rows above
 __device__ __forceinline__ unsigned wave_suffix_excl(unsigned x, int lane, unsigned& total) {
@@ -212,7 +208,7 @@ __device__ inline bool gen_legal_wave(const Position& p, move_t* s_moves, int la
     g.blockers = slider_blockers(p, g.king);
     // a slider's x-ray through the king adds squares BEHIND the king only, so "attacks the king" is unchanged
     const bool checks = enemy && (att & kbb) != 0;
-    g.danger = uniform64(wave_or64(enemy ? att : 0));
+    g.danger = scw::uniform(wave_or64(enemy ? att : 0));
     const bb_t checkers = (bb_t)__ballot(checks);
     if (!checkers) {
         n_out = gen_pseudo_wave(p, g, t, att, BB_ALL, BB_ALL, s_moves, 0, lane);

@@ -1,4 +1,4 @@
-// launchers.hpp -- host entry points of the two kernel translation units.
+// launchers.hpp -- host entry points of the kernel translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,10 +16,11 @@ void debug_find_max(const float* d_u, int n, int* d_out, hipStream_t s);
 void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc, const float* d_temperature, const float* d_u, int tie_random,
                         const float* d_w, const int32_t* d_w_off, int w_max, int32_t* d_choice, float* d_total, hipStream_t s);
 void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s);
+// encode_kernels.hip (compiled with -ffp-contract=off)
 void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
                       int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
                       int32_t* outcome, hipStream_t s);
-// training tensors (sc_encode_steps, sc_encode_steps_device, sc_selfplay_encode_traces): see mcts_kernels.hpp
+// training tensors (sc_encode_steps, sc_encode_steps_device, sc_selfplay_encode_traces): see encode_kernels.hip
 void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
                const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s);
 // the walk of a group of games whose plies start at ply p0 of the batch: d_move_off holds absolute offsets into d_moves,

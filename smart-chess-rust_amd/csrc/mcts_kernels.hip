@@ -1,8 +1,160 @@
-// mcts_kernels.hip -- translation unit of the search kernels.  Build with -ffp-contract=off
-// (exact f32 PUCT arithmetic, see mcts_kernels.hpp).
-#include "mcts_kernels.hpp"
+// mcts_kernels.hip -- the unfused search kernel k_mcts, slot setup and the test aids, with their launchers.  Built with
+// -ffp-contract=off (search_select.hpp).
+#include "search_expand.hpp"
 
 #include "launchers.hpp"
+
+namespace sc {
+// ------------------------------------------------------------------ find_max on given values (test aid, sc_debug_find_max)
+// The two argmax forms of the descent on caller-provided PUCT values: out[0] = one-round form (n <= 64, lane = child),
+// out[1] = four-round (value, index) pair form (n <= 256, lane owns children lane, lane+64, ...), exactly as `level`
+// of dev_select combines them.  Lets a test place exact ties, -0.0 / +0.0 pairs and maxima in any lane and round.
+__global__ __launch_bounds__(64) void k_debug_find_max(const float* u, int n, int* out) {
+    const int lane = threadIdx.x;
+    if (n <= 64) {
+        const int r = wave_argmax_last_lane(lane < n ? u[lane] : 0.f, lane < n);
+        if (lane == 0) out[0] = r;
+    } else if (lane == 0) {
+        out[0] = -2;
+    }
+    float best_u = 0.f;
+    int best_i = -1;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int i = lane + 64 * r;
+        if (i < n) {
+            const float v = u[i];
+            if (best_i < 0 || v >= best_u) {
+                best_u = v;
+                best_i = i;
+            }
+        }
+    }
+    const int r4 = wave_argmax_last(best_u, best_i);
+    if (lane == 0) out[1] = r4;
+}
+
+// ------------------------------------------------------------------ synthetic evaluator (tests)
+__global__ __launch_bounds__(64) void k_synth_eval(SpParams p) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    GameCtl& c = p.ctl[g];
+    if (c.status != ST_ACTIVE || c.leaf_kind != LK_EVAL) return;
+    const Position& pos = p.tpos[(size_t)g * p.tpos_cap + c.n_exp];
+    uint64_t h = synth_pos_hash(pos) ^ p.synth_salt;
+    int n = c.n_legal;
+    const uint16_t* lm = p.legal_mv + (size_t)g * MAXC;
+    if (p.evaluator == SYNTH_UNIFORM) {
+        // tie tests: every sibling has the same prior and every leaf the value 0, so all unvisited children of a node tie
+        // exactly and find_max's LAST-maximum rule (src/mcts.rs:78-88) decides every descent
+        for (int i = lane; i < n; i += 64) p.prior[(size_t)g * MAXC + i] = 1.0f / (float)n;
+        if (lane == 0) p.value[g] = 0.0f;
+        return;
+    }
+    // SYNTH_COARSE: 2-bit weights and values from {-0.5, 0, 0, 0.5}: exact PUCT ties between SOME siblings, next to
+    // non-zero value sums (the hash evaluator's 24-bit priors never collide)
+    const bool coarse = p.evaluator == SYNTH_COARSE;
+    unsigned long long sum = 0;
+    for (int i = lane; i < n; i += 64) sum += coarse ? 1u + (synth_weight(h, lm[i]) >> 22) : synth_weight(h, lm[i]);
+    sum = scw::wave_sum_u64(sum);
+    float fs = (float)sum;
+    for (int i = lane; i < n; i += 64)
+        p.prior[(size_t)g * MAXC + i] = (float)(coarse ? 1u + (synth_weight(h, lm[i]) >> 22) : synth_weight(h, lm[i])) / fs;
+    if (lane == 0) {
+        const float v = synth_value(h);
+        p.value[g] = coarse ? (v < -0.5f ? -0.5f : v >= 0.5f ? 0.5f : 0.0f) : v;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_init_slots(SpParams p) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    uint4* b = reinterpret_cast<uint4*>(p.boards + (size_t)g * 7168);
+    for (int i = lane; i < 448; i += 64) b[i] = make_uint4(0, 0, 0, 0);
+    if (lane < 8) p.meta[(size_t)g * 8 + lane] = 0;
+    if (lane == 0) p.n_legal[g] = 0;
+    // slot g starts with game g (a deterministic slot <-> game map at start; later games are drawn from the counter as
+    // slots free up); no game has finished yet, so nothing else touches the counter during this launch
+    if (g == 0 && lane == 0)
+        atomicAdd(&p.cnt->next_game, (unsigned long long)(p.n_slots < p.total_games ? p.n_slots : p.total_games));
+    if (g >= p.total_games) {
+        if (lane == 0) {
+            p.ctl[g].status = ST_IDLE;
+            p.ctl[g].leaf_kind = LK_NONE;
+        }
+        return;
+    }
+    try_start_game(p, g, lane, (unsigned long long)g);
+}
+
+// One wave per case (test aid, sc_debug_choose_child): case c reads n_act[c][0..nc[c]), temperature[c], u[c] and the weight
+// table of its temperature, w[w_off[c] .. + w_max].
+__global__ __launch_bounds__(64) void k_debug_choose_child(int n_cases, const int32_t* n_act, const int32_t* nc, const float* temperature,
+                                                           const float* u, int tie_random, const float* w, const int32_t* w_off, int w_max,
+                                                           int32_t* choice, float* total) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (c >= n_cases) return;
+    float tot;
+    const int ch = choose_child(n_act + (size_t)c * MAXC, uniform(nc[c]), temperature[c], u[c], tie_random, lane, w + uniform(w_off[c]), w_max, &tot);
+    if (lane == 0) {
+        choice[c] = ch;
+        total[c] = tot;
+    }
+}
+
+// One launch per simulation step: finish the previous simulation of every game (value head tail, expand,
+// backward, and at the end of a ply mcts::step + trace + outcome), then select the next leaf and encode it.
+__global__ __launch_bounds__(64) void k_mcts(SpParams p, int do_expand, int do_select) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    __shared__ __attribute__((aligned(16))) int8_t s_stage[7168];
+    __shared__ move_t s_moves[MAXC];
+    __shared__ Position s_pos;
+    __shared__ Position s_hist[8];
+    __shared__ uint16_t s_ps[DEPTH_LDS];
+    constexpr bool SC_ST = true;   // (k_mcts runs the flush, the timed samples and the synthetic evaluators: never the hot loop)
+    SC_STAMP(0);
+    GameCtl cs_pre{};
+    bool cs_pre_valid = false;
+    if (do_expand) {
+        // No fence between the two halves: the block is ONE wavefront, whose vector-memory operations reach the cache
+        // hierarchy in program order, so the selection below reads what the expansion above stored (statistics of the
+        // path, control block, tree headers) without first waiting for every store to be acknowledged (~4 k cycles).
+        dev_expand(p, g, lane, &s_pos, cs_pre, cs_pre_valid);
+        __builtin_amdgcn_wave_barrier();
+    }
+    SC_STAMP(1);
+    if (do_select) dev_select(p, g, lane, s_stage, s_moves, &s_pos, s_ps, s_hist, cs_pre, cs_pre_valid);
+}
+
+// ------------------------------------------------------------------ sc_selfplay_set_position
+__global__ __launch_bounds__(64) void k_set_position(SpParams p, int g, const uint16_t* moves, int n_moves) {
+    const int lane = threadIdx.x;
+    GameCtl& c = p.ctl[g];
+    Position* hist = p.hist + (size_t)g * p.hist_cap;
+    Position* tpos = p.tpos + (size_t)g * p.tpos_cap;
+    __shared__ Position s_np;
+    Position cur;
+    set_startpos(cur);
+    cur.key = position_key(cur);
+    if (lane == 0) hist[0] = cur;
+    __syncthreads();
+    for (int i = 0; i < n_moves && i + 1 < p.hist_cap; i++) replay_step(cur, moves[i], i, hist, tpos, &s_np, lane);
+    if (lane == 0) {
+        const size_t nb = (size_t)g * p.node_cap;
+        tpos[0] = cur;
+        p.N[nb] = 0;
+        p.W[nb] = 0.0f;
+        p.H[nb] = NodeHdr{-1, 0, 0};
+        c.ply = n_moves;
+        c.start_ply = n_moves;
+        c.sim = 0;
+        c.n_nodes = 1;
+        c.n_exp = 1;
+        c.leaf_kind = LK_NONE;
+        c.rollout_cur = p.rollout;
+        c.status = ST_ACTIVE;
+    }
+}
+
+}  // namespace sc
 
 namespace scl {
 void init_slots(const sc::SpParams& p, hipStream_t s) { hipLaunchKernelGGL(sc::k_init_slots, dim3(p.n_slots), dim3(64), 0, s, p); }
@@ -19,44 +171,5 @@ void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc
 }
 void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s) {
     hipLaunchKernelGGL(sc::k_set_position, dim3(1), dim3(64), 0, s, p, slot, d_moves, n_moves);
-}
-void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
-                      int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
-                      int32_t* outcome, hipStream_t s) {
-    hipLaunchKernelGGL(sc::k_encode_positions, dim3(n_pos), dim3(64), 0, s, n_pos, d_moves, d_move_off, d_move_len, d_hist, hist_cap,
-                       boards, meta, legal_mv, legal_idx, n_legal, outcome);
-}
-void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
-               const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_ply_index, dim3((n + 255) / 256), dim3(256), 0, s, n, g0, ng, d_ply_off, hist_cap, d_hoff, d_plen, d_pgame,
-                       d_rows, num_steps, t_move, d_moves, d_src);
-}
-void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
-                  const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s) {
-    if (n_games <= 0 || n_plies <= 0) return;
-    hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap);
-    hipLaunchKernelGGL(sc::k_ply_keys, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen, d_ply_moves);
-    hipLaunchKernelGGL(sc::k_ply_rep, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen);
-}
-void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
-                  int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s) {
-    if (n <= 0) return;
-    if (layout == 1)
-        hipLaunchKernelGGL(sc::k_encode_plies<1>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
-    else
-        hipLaunchKernelGGL(sc::k_encode_plies<0>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
-}
-void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
-                const uint32_t* child_n, const uint32_t* child_off, const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
-                const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
-                float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_steps_dist, dim3(n), dim3(64), 0, s, n, legal_mv, n_legal_s, next_mv, child_mv, child_n, child_off, src,
-                       nchild, pgame, plen, apply_mirror, meta_s, layout, meta_out, dist, dist_legal, n_legal_out, status);
-}
-void status_final(int n, int32_t* status, hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_status_final, dim3((n + 255) / 256), dim3(256), 0, s, n, status);
 }
 }  // namespace scl

@@ -1,5 +1,5 @@
-// nn_kernels.hpp -- policy/value network forward for gfx950 (MI355X): shared device helpers and the value head's
-// batched kernels.  The tower itself lives in nn_tower32.hpp.
+// nn_kernels.hpp -- policy/value network forward for gfx950 (MI355X): shared device helpers and the tiles of
+// the value head's batched layer (its kernels: nn_kernels.hip).  The tower itself lives in nn_tower32.hpp.
 //
 // Reproduces ChessModule.forward (reference py/module.py:135-154; ResBlockSE :14-46, PolicyHead
 // :65-80, ValueHead :83-106) with the numerics of the exported bf16 graph the Rust backends load
@@ -26,6 +26,7 @@
 
 #include "nn_types.hpp"
 #include "value_tail.hpp"
+#include "wave_util.hpp"
 
 namespace scnn {
 
@@ -38,28 +39,7 @@ __device__ inline bf16_t f2bf(float x) {
 }
 __device__ inline float bf2f(bf16_t u) { return __builtin_bit_cast(float, (uint32_t)u << 16); }
 
-// Wave-wide sum / max with the result in every lane: four DPP steps inside each row of 16 lanes (quad_perm,
-// row_half_mirror, row_mirror -- plain VALU moves) and four readlanes, instead of six dependent trips through the LDS
-// crossbar (ds_bpermute).  Fixed order, so results are reproducible.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float readlane_f(float x, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l)); }
-__device__ __forceinline__ float wave_sum64(float v) {
-    v += dpp_f<0xB1>(v);
-    v += dpp_f<0x4E>(v);
-    v += dpp_f<0x141>(v);
-    v += dpp_f<0x140>(v);
-    return (readlane_f(v, 0) + readlane_f(v, 16)) + (readlane_f(v, 32) + readlane_f(v, 48));
-}
-__device__ __forceinline__ float wave_max64(float v) {
-    v = fmaxf(v, dpp_f<0xB1>(v));
-    v = fmaxf(v, dpp_f<0x4E>(v));
-    v = fmaxf(v, dpp_f<0x141>(v));
-    v = fmaxf(v, dpp_f<0x140>(v));
-    return fmaxf(fmaxf(readlane_f(v, 0), readlane_f(v, 16)), fmaxf(readlane_f(v, 32), readlane_f(v, 48)));
-}
+using scw::dpp_f, scw::wave_max_fixed, scw::wave_sum_fixed;
 
 // The kernel arguments live in memory that is fresh at every launch, and the compiler reads them piece by piece where they are
 // first needed, each piece behind its own wait: a chain of scalar-cache misses at the top of every kernel (stamped in the fused
@@ -248,51 +228,5 @@ __device__ __forceinline__ void fc1_mma_store(const Fc1W& w, const bf16_t* s_a, 
             }
         }
 }
-
-#ifndef SC_NO_KERNELS
-// grid = (ceil(n/64), KSPLIT)
-__global__ __launch_bounds__(256) void k_value_fc1(Fc1Args A) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int mb = blockIdx.x, ks = blockIdx.y;
-    __shared__ __attribute__((aligned(16))) bf16_t s_a[FC1_TILE_LDS / 2];
-    Fc1W w;
-    fc1_wload(w, A.net, ks, A.ksplit, wave, lane);
-    fc1_stage_a(s_a, A.hval, A.n_pos, mb, ks, A.ksplit, tid);
-    __syncthreads();   // A tile staged
-    fc1_mma_store(w, s_a, A.vpart, A.n_pos, mb, ks, A.ksplit, wave, lane);
-}
-
-// value head tail (py/module.py:95-106,147-149), one wave per position: the arithmetic is value_tail.hpp's, shared with the
-// search kernel's fused tail (mcts_kernels.hpp: value_tail_issue / value_tail_finish), so `predict` and the value the
-// search backs up are the same bits.
-__global__ __launch_bounds__(64) void k_value_finish(VfinArgs A) {
-    const int pos = blockIdx.x, lane = threadIdx.x;
-    if (pos >= A.n_pos) return;
-    const float* wf = A.net.wf;
-    scvt::ValueTail t;
-#pragma unroll
-    for (int k = 0; k < 7; k++) t.meta[k] = A.meta[(size_t)pos * A.meta_stride + k];
-    const int j = 2 * lane;   // lane owns output columns 2*lane, 2*lane+1
-    const float* vp = A.vpart + (size_t)pos * FC1_N + j;
-    const size_t vstride = (size_t)A.n_pos * FC1_N;
-#pragma unroll
-    for (int ks = 0; ks < 32; ks++) t.acc[ks] = *reinterpret_cast<const float2*>(vp + (size_t)ks * vstride);
-    if (A.ksplit > 32) {
-#pragma unroll
-        for (int ks = 32; ks < 64; ks++) t.acc[ks] = *reinterpret_cast<const float2*>(vp + (size_t)ks * vstride);
-    } else {
-#pragma unroll
-        for (int ks = 32; ks < 64; ks++) t.acc[ks] = make_float2(0.f, 0.f);
-    }
-    t.bias = *reinterpret_cast<const float2*>(wf + A.net.f_fc1b + j);
-    t.w2 = *reinterpret_cast<const float2*>(wf + A.net.f_fc2w + j);
-#pragma unroll
-    for (int k = 0; k < 7; k++) t.wm[k] = *reinterpret_cast<const float2*>(wf + A.net.f_fc1m + k * FC1_N + j);
-    t.fc2b = wf[A.net.f_fc2b];
-    const float v = scvt::value_tail_compute(t, A.ksplit);
-    if (lane == 0) A.value[pos] = v;
-}
-
-#endif  // SC_NO_KERNELS
 
 }  // namespace scnn

@@ -980,11 +980,11 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
     float mw = zv[0];
 #pragma unroll
     for (int j = 1; j < 19; j++) mw = fmaxf(mw, zv[j]);
-    mw = wave_max64(mw);
+    mw = wave_max_fixed(mw);
     float sw = 0.f;
 #pragma unroll
     for (int j = 0; j < 19; j++) sw += __expf(zv[j] - mw);
-    sw = wave_sum64(sw);
+    sw = wave_sum_fixed(sw);
     if (lane == 0) {
         s_red[wave] = mw;
         s_red[4 + wave] = sw;
@@ -1012,7 +1012,7 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         float e = 0.f;
         if (tid < n) e = __expf(s_z[li[tid]] - lse);  // n <= 218 < 256 threads
         float s = e;
-        s = wave_sum64(s);
+        s = wave_sum_fixed(s);
         __syncthreads();
         if (lane == 0) s_red[wave] = s;
         __syncthreads();
@@ -1030,16 +1030,6 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
     }
 #endif
     return true;
-}
-
-#ifndef SC_T32_OCC
-#define SC_T32_OCC 1
-#endif
-template <class P, int C, int RS, int TPI, int AB = SC_T32_AB>
-__global__ __launch_bounds__(256, SC_T32_OCC) void k_tower32(TowerArgs A) {
-    if ((int)blockIdx.x >= A.n_pos) return;
-    NoHand nh;
-    tower_body<P, C, RS, TPI, AB>(A, (int)blockIdx.x, nullptr, NoPre(), nh);
 }
 
 }  // namespace scnn

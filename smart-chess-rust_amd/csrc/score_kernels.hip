@@ -10,7 +10,7 @@
 //       loads: lane l takes chunks l, l + 64, ..., l + 64 * 18 (the last index clamped to the row and masked in the arithmetic, so
 //       no load is guarded), all issued before the first use (rows_landed() below; checked in the ISA: 38 global_load_dwordx4, then
 //       the first s_waitcnt vmcnt, in k_score and in k_compare).  Every sum over the row is the same tree: the four floats of a
-//       chunk pairwise (2 levels), the lane's 19 chunks pairwise (5 levels), wave_sum64 (4 DPP levels + 2) -- 13 additions deep,
+//       chunk pairwise (2 levels), the lane's 19 chunks pairwise (5 levels), wave_sum_fixed (4 DPP levels + 2) -- 13 additions deep,
 //       in a fixed order, so a position's result depends on nothing but its own rows.  The exponential is expf (HIP's
 //       math-function table: 1 ulp), the translation unit is compiled with -ffp-contract=off: products are rounded before they are
 //       added.  The sparse form of ce is one gather of <= 218 log-probabilities (lane = legal move, four rounds).
@@ -19,14 +19,13 @@
 //   k_summary             one workgroup reduces the [P] per-position floats to the summary in double precision: thread t adds
 //       entries t, t + 1024, ... in order, then a tree over the 1024 partials in LDS.  No atomics anywhere: two identical calls
 //       give bit-identical summaries.
-#define SC_NO_KERNELS
-#include "nn_kernels.hpp"   // wave_sum64 (DPP + readlane, fixed order)
+#include "wave_util.hpp"   // wave_sum_fixed (DPP + readlane, fixed order)
 #include "launchers.hpp"
 #include "score_types.hpp"
 
 namespace scsc {
 
-using scnn::wave_sum64;
+using scw::wave_sum_fixed;
 
 __device__ __forceinline__ float sum4(float4 t) { return (t.x + t.y) + (t.z + t.w); }
 // pairwise over the lane's 19 chunk sums: ((0..4) + (5..9)) + ((10..14) + (15..18)), 5 levels
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             t[j] = sum4(q);
         }
         if (!last) t[18] = 0.f;
-        ce = -wave_sum64(tree<19>(t));
+        ce = -wave_sum_fixed(tree<19>(t));
     } else {
         // lane = legal move i (+ 64 per round); entries at and past n_legal are padding (action 0, share 0) and are not read
         const int nl = A.n_legal[pos];
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             oob |= !in;
             t[r] = (on && in && d != 0.f) ? d * lrow[idx] : 0.f;
         }
-        ce = -wave_sum64((t[0] + t[1]) + (t[2] + t[3]));
+        ce = -wave_sum_fixed((t[0] + t[1]) + (t[2] + t[3]));
         // n_legal outside 0..218 or an action index outside the row: nothing was read through them, the position counts as non-finite
         if (bad || __builtin_amdgcn_ballot_w64(oob) != 0) ce = quiet_nan();
     }
@@ -126,7 +125,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         t[j] = sum4(q);
     }
     if (!last) t[18] = 0.f;
-    const float ent = -wave_sum64(tree<19>(t));
+    const float ent = -wave_sum_fixed(tree<19>(t));
     if (lane == 0) {
         const float v = A.value[pos];
         const float dv = v - A.outcome[pos];
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         t[j] = sum4(q);
     }
     if (!last) t[18] = 0.f;
-    const float tv = 0.5f * wave_sum64(tree<19>(t));
+    const float tv = 0.5f * wave_sum_fixed(tree<19>(t));
     if (lane == 0) {
         A.tv[pos] = tv;
         A.dv[pos] = fabsf(A.value1[pos] - A.value2[pos]);

@@ -155,7 +155,7 @@ int sc_selfplay_create(sc_engine* e, int device_id, const sc_selfplay_config* cf
     p.seed = cfg->seed;
     p.first_game_id = cfg->first_game_id;
     p.node_cap = 1 + cfg->rollout_num * 218;         // worst case: every expansion adds 218 children
-    p.max_depth = std::min(cfg->rollout_num + 2, 1024);  // the path is tracked in LDS (mcts_kernels.hpp DEPTH_LDS)
+    p.max_depth = std::min(cfg->rollout_num + 2, 1024);  // the path is tracked in LDS (search_select.hpp DEPTH_LDS)
     p.hist_cap = cfg->num_steps + 2 + 600;           // room for sc_selfplay_set_position prefixes
     p.tpos_cap = cfg->rollout_num + 2;
     p.trace_cap = cfg->trace_capacity > 0 ? std::min(cfg->n_games, std::max(cfg->trace_capacity, 2 * cfg->n_slots)) : cfg->n_games;

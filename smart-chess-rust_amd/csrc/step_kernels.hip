@@ -9,12 +9,8 @@
 // Bit-identical to k_mcts + k_tower32 (same device functions): tests/test_gpu_parity*.py run through this path; the
 // unfused pair remains for the synthetic evaluators, the final flush and the timed samples of the bench.
 //
-// The search arithmetic must not be contracted into FMAs (src/mcts.rs:69-75 is plain f32) while the tower's epilogues are
-// written for contraction: this unit is compiled like nn_kernels.hip (contraction on), and the search functions carry
-// `#pragma clang fp contract(off)` in their bodies and use raw hardware transcendentals, so that they compile to the same
-// instructions here and in mcts_kernels.hip (checked: k_mcts is identical with and without -ffp-contract=off).
-#define SC_NO_KERNELS   // device functions only: the kernels of these headers live in their own translation units
-#include "mcts_kernels.hpp"
+// This unit is compiled like nn_kernels.hip, contraction on; the search functions look after themselves (search_select.hpp).
+#include "search_expand.hpp"
 #include "nn_kernels.hpp"
 #include "nn_tower32.hpp"
 

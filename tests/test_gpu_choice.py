@@ -1,7 +1,7 @@
 """GPU (-m gpu): the end-of-ply move choice (mcts::step, src/mcts.rs:298-317; NNPlayer::bestmove, src/play.rs:268-277) of the
 device against the host, on crafted inputs.
 
-`sc_debug_choose_child` runs `choose_child` of csrc/mcts_kernels.hpp -- the function `k_mcts` and the fused `k_step` call at
+`sc_debug_choose_child` runs `choose_child` of csrc/search_expand.hpp -- the function `k_mcts` and the fused `k_step` call at
 the end of every ply -- on given visit counts, one wave per case.  Every assertion is exact equality: the chosen index, and the
 bit pattern of the f32 weight total.  The reference of a decision is the oracle's `orc_choose_child` (oracle/mcts.c), the
 reference of a single weight is the host libm's `powf` through ctypes (what Rust's `f32::powf` and the oracle call); numpy's own

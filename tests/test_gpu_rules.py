@@ -320,3 +320,77 @@ def test_search_lockstep_from_edge_positions(scamd, orc, k):
             assert list(sp.slot(0)["path"]) == list(srch.last_path())
     assert sp.stats()["error_flags"] == 0
     sp.close()
+
+
+def _replay_lines(orc):
+    """three lines for the replay step k_set_position and k_encode_positions share: under 8 plies; a corpus line cut one move
+    before its threefold repetition; 81 plies whose last position is the one after ply 1 -- 1. a4, then the g1 knight walks a
+    cycle of 8 squares and the b8 knight one of 10, which meet again after 40 moves each -- so the repeated position lies 80
+    plies back and the scan's second round of 64 lanes finds it"""
+    short = [orc.from_uci(u) for u in ("e2e4", "c7c5", "g1f3")]
+    three = [orc.from_uci(u) for u in min((e["uci"] for e in load_edge_lines() if e["category"] == "threefold"), key=len)]
+    st = orc.State()
+    for m in three:
+        st.push(m)
+    while st.is_repetition(3):
+        st.pop()
+        three = three[:-1]
+    assert any(_pushed_rep3(st, m) for m in st.legal_moves())
+    wn = ["g1", "f3", "d4", "f5", "g3", "e4", "g5", "h3"]
+    bn = ["b8", "a6", "c5", "e6", "f4", "g6", "e5", "c4", "a5", "c6"]
+    long = ["a2a4"]
+    for k in range(40):
+        long += [bn[k % 10] + bn[(k + 1) % 10], wn[k % 8] + wn[(k + 1) % 8]]
+    long = [orc.from_uci(u) for u in long]
+    for line, rep2 in ((short, False), (three, True), (long, True)):
+        st = orc.State()
+        for m in line:
+            assert m in st.legal_moves()
+            st.push(m)
+        assert st.legal_moves() and st.is_repetition(2) == rep2 and not st.is_repetition(3)
+        # (the oracle's outcome claims the draw one move early, python-chess can_claim_threefold_repetition: the search goes on)
+        assert st.outcome() == (dict(termination="ThreefoldRepetition", winner=None) if line is three else None)
+    assert len(short) < 8 and len(long) == 81
+    return [short, three, long]
+
+
+def _pushed_rep3(st, m):
+    st.push(m)
+    r = st.is_repetition(3)
+    st.pop()
+    return r
+
+
+@pytest.mark.parametrize("k", range(3))
+def test_replay_step_callers_agree(scamd, orc, eng, idx_table, k):
+    """replay_step (position_chain.hpp) through both of its callers on the same line: sc_encode_positions -- planes, meta, legal
+    moves, action indices, outcome -- equals the oracle; the slot sc_selfplay_set_position fills has the line's ply, the oracle's
+    legal moves as the root's children after one simulation (the row sc_encode_positions gave), and searches in lockstep with
+    the oracle from there (the long line: leaves 64 plies and more from the repeated position)"""
+    line = _replay_lines(orc)[k]
+    st = orc.State()
+    for m in line:
+        st.push(m)
+    ex = _Expect()
+    ex.add(line, st)
+    r = _encode(scamd, eng, [line])
+    nl = _compare(scamd, eng, idx_table, ex, "replay line %d" % k)
+    R = 60
+    sp = scamd.SelfPlay(None, n_slots=2, n_games=2, rollout_num=R, num_steps=20, cpuct=2.5, with_noise=False,
+                        evaluator="synth", seed=3)
+    sp.set_position(0, line)
+    s0 = sp.slot(0)
+    assert (s0["ply"], s0["sim"], s0["status"]) == (len(line), 0, 1)
+    srch = orc.Search(st)
+    for s in range(R - 1):
+        sp.enqueue(1)
+        srch.sim(cpuct=2.5, with_noise=False)
+        if s % 7 == 0 or s > R - 5:
+            t, d = sp.tree(0), srch.dump()
+            assert _same_tree(t, d), s
+            assert list(sp.slot(0)["path"]) == list(srch.last_path())
+        if s == 0:
+            assert t["n_child"][0] == nl[0] == len(ex.legal[0])
+            assert list(t["move"][1:1 + nl[0]]) == list(r["lm"][0, :nl[0]]) == list(ex.legal[0])
+    assert sp.stats()["error_flags"] == 0
+    sp.close()

@@ -5,6 +5,7 @@ R=$(cd $(dirname $0)/.. && pwd)
 C=$R/smart-chess-rust_amd/csrc; O=$R/smart-chess-rust_amd/lib_exp$SC_EXP_TAG; mkdir -p $O
 H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DSC_EXP $SC_EXP_DEFS"
 $H -ffp-contract=off -c $C/mcts_kernels.hip -o $O/mcts.o 
+$H -ffp-contract=off -c $C/encode_kernels.hip -o $O/encode.o
 $H -mllvm -amdgpu-mfma-vgpr-form=1 -c $C/nn_kernels.hip -o $O/nn.o 
 $H -mllvm -amdgpu-mfma-vgpr-form=1 -c $C/step_kernels.hip -o $O/step.o
 $H -ffp-contract=off -c $C/score_kernels.hip -o $O/score.o

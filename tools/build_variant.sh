@@ -5,6 +5,7 @@ set -e
 R=/root/repo; C=$R/smart-chess-rust_amd/csrc; O=$R/smart-chess-rust_amd/lib_$1; mkdir -p $O
 H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $2"
 $H -ffp-contract=off -c $C/mcts_kernels.hip -o $O/mcts.o &
+$H -ffp-contract=off -c $C/encode_kernels.hip -o $O/encode.o &
 $H -mllvm -amdgpu-mfma-vgpr-form=1 -c $C/nn_kernels.hip -o $O/nn.o &
 $H -mllvm -amdgpu-mfma-vgpr-form=1 -c $C/step_kernels.hip -o $O/step.o &
 $H -ffp-contract=off -c $C/score_kernels.hip -o $O/score.o &

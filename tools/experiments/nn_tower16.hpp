@@ -578,13 +578,13 @@ __global__ __launch_bounds__(256, 1) void k_tower(TowerArgs A) {
     // ---- log_softmax over 4672 (module.py:80), then the legal-move gather of torch.rs:148-175
     float mx = -3.0e38f;
     for (int i = tid; i < 4672; i += 256) mx = fmaxf(mx, s_z[i]);
-    mx = wave_max64(mx);
+    mx = wave_max_fixed(mx);
     if (lane == 0) s_red[wave] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
     float se = 0.f;
     for (int i = tid; i < 4672; i += 256) se += __expf(s_z[i] - mx);
-    se = wave_sum64(se);
+    se = wave_sum_fixed(se);
     if (lane == 0) s_red[4 + wave] = se;
     __syncthreads();
     se = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
@@ -599,7 +599,7 @@ __global__ __launch_bounds__(256, 1) void k_tower(TowerArgs A) {
         float e = 0.f;
         if (tid < n) e = __expf(s_z[li[tid]] - lse);  // n <= 218 < 256 threads
         float s = e;
-        s = wave_sum64(s);
+        s = wave_sum_fixed(s);
         __syncthreads();
         if (lane == 0) s_red[wave] = s;
         __syncthreads();

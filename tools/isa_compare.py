@@ -2,11 +2,13 @@
 
     python tools/isa_compare.py OLD_TREE [NEW_TREE] [--rename OLD=NEW ...] [--keep DIR]
 
-Compiles step_kernels.hip and mcts_kernels.hip of both trees to device-only assembly with build.py's flags, demangles, strips
-comments, directives and label numbering, and compares every function by its demangled name.  --rename maps a name of the old
-tree to its name in the new one (applied to the whole text, so a kernel's own LDS symbols follow).  NEW_TREE defaults to the tree
-this file is in.  Exit status 1 when a function present in both trees differs."""
+Compiles every kernel unit each tree's build.py lists (the units may differ between the trees: kernels move) to device-only
+assembly with that unit's flags, demangles, strips comments, directives and label numbering, pools a tree's functions by
+demangled name and compares the pools.  --rename maps a name of the old tree to its name in the new one (applied to the whole
+text, so a kernel's own LDS symbols follow).  NEW_TREE defaults to the tree this file is in.  Exit status 1 when a function
+present in both trees differs."""
 import argparse
+import ast
 import os
 import re
 import subprocess
@@ -14,9 +16,20 @@ import sys
 import tempfile
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-# smart-chess-rust_amd/build.py's flags per translation unit
-UNITS = (("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("mcts_kernels.hip", ["-ffp-contract=off"]))
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S"]
+
+
+def units(tree):
+    """(unit, flags) of the kernel units (*_kernels.hip) in the tree's build.py"""
+    pairs = re.findall(r'\("(\w+\.hip)",\s*(\[[^\]]*\])\)', open(os.path.join(tree, "smart-chess-rust_amd", "build.py")).read())
+    return [(u, ast.literal_eval(f)) for u, f in pairs if u.endswith("_kernels.hip")]
+
+
+def pool(tree, tag, tmp, renames):
+    fns = {}
+    for unit, extra in units(tree):
+        fns.update(functions(assembly(tree, unit, extra, os.path.join(tmp, tag + "_" + unit + ".s")), renames))
+    return fns
 
 
 def assembly(tree, unit, extra, out):
@@ -59,22 +72,20 @@ def main():
     tmp = a.keep or tempfile.mkdtemp(prefix="isa_compare_")
     os.makedirs(tmp, exist_ok=True)
     differ = 0
-    for unit, extra in UNITS:
-        old = functions(assembly(a.old_tree, unit, extra, os.path.join(tmp, "old_" + unit + ".s")), renames)
-        new = functions(assembly(a.new_tree, unit, extra, os.path.join(tmp, "new_" + unit + ".s")), [])
-        print("== %s: %d functions in the old tree, %d in the new" % (unit, len(old), len(new)))
-        for name in sorted(set(old) | set(new)):
-            short = name if len(name) <= 110 else name[:107] + "..."
-            if name not in new:
-                print("  only old   %6d  %s" % (len(old[name]), short))
-            elif name not in old:
-                print("  only new   %6d  %s" % (len(new[name]), short))
-            elif old[name] == new[name]:
-                print("  identical  %6d  %s" % (len(new[name]), short))
-            else:
-                differ += 1
-                first = next((i for i, (x, y) in enumerate(zip(old[name], new[name])) if x != y), min(len(old[name]), len(new[name])))
-                print("  DIFFER     %6d -> %d (first at instruction %d)  %s" % (len(old[name]), len(new[name]), first, short))
+    old, new = pool(a.old_tree, "old", tmp, renames), pool(a.new_tree, "new", tmp, [])
+    print("== %d functions in the old tree, %d in the new" % (len(old), len(new)))
+    for name in sorted(set(old) | set(new)):
+        short = name if len(name) <= 110 else name[:107] + "..."
+        if name not in new:
+            print("  only old   %6d  %s" % (len(old[name]), short))
+        elif name not in old:
+            print("  only new   %6d  %s" % (len(new[name]), short))
+        elif old[name] == new[name]:
+            print("  identical  %6d  %s" % (len(new[name]), short))
+        else:
+            differ += 1
+            first = next((i for i, (x, y) in enumerate(zip(old[name], new[name])) if x != y), min(len(old[name]), len(new[name])))
+            print("  DIFFER     %6d -> %d (first at instruction %d)  %s" % (len(old[name]), len(new[name]), first, short))
     print("%d function(s) differ" % differ)
     return 1 if differ else 0
 
