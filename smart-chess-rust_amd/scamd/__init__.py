@@ -19,8 +19,9 @@ reference's usage:
 There is NO CPU fallback: importing works anywhere (so the C ABI can be checked), but every
 compute entry point raises EngineError when the HIP library or a GPU is missing.
 """
-from .binding import (ChessHip, Engine, EngineError, Play, SelfPlay, encode_move, encode_positions, encode_steps, encode_steps_batch,  # noqa: F401
-                      encode_steps_torch, score_torch, compare_torch, gather_batch_torch, ReplayBuffer, ReplayIndex, pack_steps, hip_runtime, hip_runtime_files,
-                      choose_child, enqueue_interleaved, elo, find_max, lib, lib_path, play_match, runtime_flags, search,
-                      move_uci, uci_move, write_trace_json, TERMINATION)
+from .binding import EngineError, TERMINATION, encode_move, hip_runtime, hip_runtime_files, lib, lib_path, move_uci, runtime_flags, uci_move  # noqa: F401
+from .net import ChessHip, Engine, encode_positions  # noqa: F401
+from .training import compare_torch, encode_steps, encode_steps_batch, encode_steps_torch, pack_steps, score_torch  # noqa: F401
+from .replay import ReplayBuffer, ReplayIndex, gather_batch_torch  # noqa: F401
+from .selfplay import Play, SelfPlay, choose_child, elo, enqueue_interleaved, find_max, play_match, search, write_trace_json  # noqa: F401
 from . import binding  # noqa: F401

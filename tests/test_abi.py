@@ -6,20 +6,10 @@ import os
 import re
 
 import pytest
+from support import scamd_built  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    import importlib.util
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import build as scbuild
-    scbuild.build()
-    import scamd as m
-    return m
 
 
 def test_exports_exactly_the_declared_symbols(scamd):
@@ -196,3 +186,36 @@ def test_rust_binding_functions_are_the_headers(scamd):
     # INTEGRATION.md points at the file instead of carrying a second copy of the structs
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "integration/hip.rs" in doc and "#[repr(C)]" not in doc
+
+
+# the names `from .binding import (...)` of scamd/__init__.py listed before the package was split into modules
+_PUBLIC = {"ChessHip", "Engine", "EngineError", "Play", "SelfPlay", "encode_move", "encode_positions", "encode_steps", "encode_steps_batch",
+           "encode_steps_torch", "score_torch", "compare_torch", "gather_batch_torch", "ReplayBuffer", "ReplayIndex", "pack_steps", "hip_runtime",
+           "hip_runtime_files", "choose_child", "enqueue_interleaved", "elo", "find_max", "lib", "lib_path", "play_match", "runtime_flags", "search",
+           "move_uci", "uci_move", "write_trace_json", "TERMINATION"}
+_BINDING = {"ABI", "lib", "lib_path", "NetConfig", "SelfplayConfig", "Stats", "TraceInfo", "EngineError", "ERR_HANDOFF", "MAX_MOVES", "TERMINATION",
+            "EVALUATORS", "hip_runtime_files", "hip_runtime", "move_uci", "uci_move", "encode_move", "runtime_flags", "encode_steps_last_timing"}
+
+
+def test_public_names(scamd):
+    """scamd exports what it exported as one module, no more and no less: besides those names its namespace holds only its own
+    submodules (Python binds an imported submodule to its package), `binding` among them; and scamd.binding keeps what bench.py,
+    the tools and the tests read from it"""
+    import types
+    public = {n for n in vars(scamd) if not n.startswith("_")}
+    modules = {n for n in public if isinstance(getattr(scamd, n), types.ModuleType)}
+    assert public - modules == _PUBLIC, (public - modules) ^ _PUBLIC
+    assert "binding" in modules and all(getattr(scamd, n).__name__ == f"scamd.{n}" for n in modules), modules
+    assert not [n for n in sorted(_BINDING) if not hasattr(scamd.binding, n)]
+
+
+def test_import_leaves_torch_out_and_sets_the_kernarg_default(scamd):
+    """in a fresh process `import scamd; scamd.lib()` does not import torch (a host decides the order of the two HIP runtimes
+    itself) and leaves HIP_FORCE_DEV_KERNARG=1 in os.environ"""
+    import subprocess
+    import sys
+    code = ("import os, sys; sys.path.insert(0, %r); import scamd; scamd.lib(); "
+            "print('torch' in sys.modules, os.environ.get('HIP_FORCE_DEV_KERNARG'))" % os.path.join(ROOT, "smart-chess-rust_amd"))
+    env = {k: v for k, v in os.environ.items() if k != "HIP_FORCE_DEV_KERNARG"}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, check=True)
+    assert r.stdout.split() == ["False", "1"], r.stdout + r.stderr

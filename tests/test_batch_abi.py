@@ -3,31 +3,17 @@ exported; bad arguments are refused before anything touches a device; without a 
 buffer's bookkeeping (ReplayIndex, numpy only) keeps whole games, evicts the oldest, follows the reference's start_step rule and
 cuts an epoch as DataLoader(drop_last=True) does; and the numpy yardstick of the GPU tests (tests/batch_ref.py) is pinned on a
 hand-written case."""
-import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import batch_ref
+from support import _p, scamd_built  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import build as scbuild
-    scbuild.build()
-    import scamd as m
-    return m
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _host_args():

@@ -8,19 +8,10 @@ import subprocess
 
 import numpy as np
 import pytest
+from support import scamd_built  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sc_encode_steps_device", "sc_selfplay_encode_traces")
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import build as scbuild
-    scbuild.build()
-    import scamd as m
-    return m
 
 
 def test_new_symbols_are_declared_bound_and_exported(scamd):

@@ -15,80 +15,18 @@ import pytest
 
 import batch_ref
 from helpers import random_games
+from support import open_dev, _p, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H2D, D2H = 1, 2   # hipMemcpyHostToDevice, hipMemcpyDeviceToHost
 FILL = 0x5a
 N_LEGAL = (0, 1, 63, 64, 65, 128, 129, 192, 193, 218)   # the boundaries of the scatter's lane rounds
 KEYS = ("boards", "meta", "dist_legal", "legal_idx", "n_legal", "outcome")
 
 
 @pytest.fixture(scope="module")
-def scamd():
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import scamd as m
-    if m.lib().sc_device_count() <= 0:
-        pytest.fail("no MI355X visible: the HIP path cannot be tested (and there is no fallback)")
-    return m
-
-
-class Dev:
-    """device buffers and one non-default stream on the engine's HIP runtime"""
-
-    def __init__(self, scamd):
-        self.hip = scamd.hip_runtime()
-        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.hip.hipFree.argtypes = [C.c_void_p]
-        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-        self.hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-        self.hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-        self.hip.hipStreamDestroy.argtypes = [C.c_void_p]
-        self.bufs = []
-        s = C.c_void_p()
-        assert self.hip.hipStreamCreate(C.byref(s)) == 0
-        self.stream = s
-
-    def alloc(self, nbytes, fill=FILL):
-        p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(p), max(int(nbytes), 1)) == 0
-        assert self.hip.hipMemset(p, fill, max(int(nbytes), 1)) == 0   # garbage: every byte the call owns must be written
-        self.bufs.append(p)
-        return p
-
-    def upload(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.alloc(a.nbytes)
-        if a.nbytes:
-            assert self.hip.hipMemcpy(p, a.ctypes.data_as(C.c_void_p), a.nbytes, H2D) == 0
-        return p
-
-    def read(self, p, shape, dtype):
-        out = np.empty(shape, dtype)
-        if out.nbytes:
-            assert self.hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), p, out.nbytes, D2H) == 0
-        return out
-
-    def sync(self):
-        assert self.hip.hipStreamSynchronize(self.stream) == 0
-
-    def close(self):
-        self.sync()
-        for p in self.bufs:
-            self.hip.hipFree(p)
-        self.hip.hipStreamDestroy(self.stream)
-
-
-@pytest.fixture(scope="module")
 def dev(scamd):
-    d = Dev(scamd)
-    yield d
-    d.close()
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    yield from open_dev(scamd, FILL)
 
 
 def _bits(a):

@@ -12,20 +12,11 @@ import numpy as np
 import pytest
 
 import choice_cases as cc
+from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import scamd as m
-    if m.lib().sc_device_count() <= 0:
-        pytest.fail("no MI355X visible: the HIP path cannot be tested (and there is no fallback)")
-    return m
 
 
 def _bits(a):

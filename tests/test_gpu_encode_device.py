@@ -5,7 +5,6 @@ use, the ring as a source, the layouts, the grouping by history records -- and d
 sampled games of the device result (assert_games_equal_oracle) and of the host result.  Device buffers come from hipMalloc on
 the HIP runtime libsc_engine.so uses (ctypes): this file does not import torch -- the torch interop runs in a child process of
 its own."""
-import ctypes as C
 import json
 import os
 import random
@@ -16,70 +15,10 @@ import numpy as np
 import pytest
 
 from helpers import random_games
+from support import dev_per_test, _p, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-H2D, D2H = 1, 2   # hipMemcpyHostToDevice, hipMemcpyDeviceToHost
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import scamd as m
-    if m.lib().sc_device_count() <= 0:
-        pytest.fail("no MI355X visible: the HIP path cannot be tested (and there is no fallback)")
-    return m
-
-
-class Dev:
-    """device buffers and one non-default stream on the engine's HIP runtime"""
-
-    def __init__(self, scamd):
-        self.hip = scamd.hip_runtime()
-        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.hip.hipFree.argtypes = [C.c_void_p]
-        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-        self.hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-        self.hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-        self.hip.hipStreamDestroy.argtypes = [C.c_void_p]
-        self.bufs = []
-        s = C.c_void_p()
-        assert self.hip.hipStreamCreate(C.byref(s)) == 0
-        self.stream = s
-
-    def alloc(self, nbytes, fill=0x5a):
-        p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(p), max(int(nbytes), 1)) == 0
-        assert self.hip.hipMemset(p, fill, max(int(nbytes), 1)) == 0   # garbage: every byte the call owns must be written
-        self.bufs.append(p)
-        return p
-
-    def read(self, p, shape, dtype):
-        out = np.empty(shape, dtype)
-        if out.nbytes:
-            assert self.hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), p, out.nbytes, D2H) == 0
-        return out
-
-    def sync(self):
-        assert self.hip.hipStreamSynchronize(self.stream) == 0
-
-    def close(self):
-        self.sync()
-        for p in self.bufs:
-            self.hip.hipFree(p)
-        self.hip.hipStreamDestroy(self.stream)
-
-
-@pytest.fixture
-def dev(scamd):
-    d = Dev(scamd)
-    yield d
-    d.close()
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _outputs(dev, P, n, layout):

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from helpers import random_games
+from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,16 +34,6 @@ LINES = [
     ["g1f3", "g8f6", "f3g1", "f6g8", "g1f3", "g8f6", "f3g1"],  # repetition planes set, Black to move
 ]
 SLOTS = [0, 17, 31, 40, 63]
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import scamd as m
-    if m.lib().sc_device_count() <= 0:
-        pytest.fail("no MI355X visible: the HIP path cannot be tested (and there is no fallback)")
-    return m
 
 
 class GpuPredictEvaluator:

@@ -12,21 +12,12 @@ import numpy as np
 import pytest
 
 from helpers import random_games
+from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 RTOL = ATOL = 1e-2   # reference convention, scripts/eval_speed.py:40-43
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import scamd as m
-    if m.lib().sc_device_count() <= 0:
-        pytest.fail("no MI355X visible: the HIP path cannot be tested (and there is no fallback)")
-    return m
 
 
 # ---------------------------------------------------------------------------------- rules + encoder (a10-a16)

@@ -12,21 +12,12 @@ import pytest
 
 from helpers import edge_features, load_edge_lines, mv_parts, random_games, special_walk
 from test_gpu_parity import _random_steps, _same_tree
+from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAXC = 224
 HIST_BUDGET = 512 << 20     # bytes of history scratch per sc_encode_positions call: n * (longest line + 2) * 80
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import scamd as m
-    if m.lib().sc_device_count() <= 0:
-        pytest.fail("no MI355X visible: the HIP path cannot be tested (and there is no fallback)")
-    return m
 
 
 @pytest.fixture(scope="module")

@@ -18,79 +18,12 @@ import pytest
 
 import score_ref
 from helpers import random_games
+from support import dev_per_module, _p, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-H2D, D2H = 1, 2
 GUARD = 0x5a5a5a5a
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import scamd as m
-    if m.lib().sc_device_count() <= 0:
-        pytest.fail("no MI355X visible: the HIP path cannot be tested (and there is no fallback)")
-    return m
-
-
-class Dev:
-    """device buffers (pre-filled with 0x5a) and one non-default stream on the engine's HIP runtime"""
-
-    def __init__(self, scamd):
-        self.hip = scamd.hip_runtime()
-        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.hip.hipFree.argtypes = [C.c_void_p]
-        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-        self.hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-        self.hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-        self.hip.hipStreamDestroy.argtypes = [C.c_void_p]
-        self.bufs = []
-        s = C.c_void_p()
-        assert self.hip.hipStreamCreate(C.byref(s)) == 0
-        self.stream = s
-
-    def alloc(self, nbytes):
-        p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(p), max(int(nbytes), 1)) == 0
-        assert self.hip.hipMemset(p, 0x5a, max(int(nbytes), 1)) == 0
-        self.bufs.append(p)
-        return p
-
-    def put(self, a):
-        a = np.ascontiguousarray(a)
-        p = self.alloc(a.nbytes)
-        if a.nbytes:
-            assert self.hip.hipMemcpy(p, a.ctypes.data_as(C.c_void_p), a.nbytes, H2D) == 0
-        return p
-
-    def read(self, p, shape, dtype):
-        out = np.empty(shape, dtype)
-        if out.nbytes:
-            assert self.hip.hipMemcpy(out.ctypes.data_as(C.c_void_p), p, out.nbytes, D2H) == 0
-        return out
-
-    def sync(self):
-        assert self.hip.hipStreamSynchronize(self.stream) == 0
-
-    def close(self):
-        self.sync()
-        for p in self.bufs:
-            self.hip.hipFree(p)
-        self.hip.hipStreamDestroy(self.stream)
-
-
-@pytest.fixture(scope="module")
-def dev(scamd):
-    d = Dev(scamd)
-    yield d
-    d.close()
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _at(p, nbytes):
@@ -138,7 +71,7 @@ class Positions:
         self.n_legal = dev.read(self.d["n_legal"], (P,), np.int32)
         win = np.asarray([rnd.choice((-1.0, 0.0, 1.0)) for _ in steps], np.float32)
         self.outcome = np.repeat(win, np.diff(off.astype(np.int64)))
-        self.d["outcome"] = dev.put(self.outcome)
+        self.d["outcome"] = dev.upload(self.outcome)
 
 
 @pytest.fixture(scope="module")
@@ -308,7 +241,7 @@ def _check_compare_summary(tv, dv, s):
 def test_compare_engines(scamd, dev, big):
     g = np.load(os.path.join(GOLD, "nn_ref_b10_c128.npz"))
     n = g["boards"].shape[0]
-    d_b, d_m = dev.put(g["boards"].astype(np.int8)), dev.put(g["meta"].astype(np.int32))
+    d_b, d_m = dev.upload(g["boards"].astype(np.int8)), dev.upload(g["meta"].astype(np.int32))
     a = scamd.Engine(10, 128, seed=int(g["seed"]))
     b = scamd.Engine(10, 128, seed=int(g["seed"]), precision="fp8")
     a2 = scamd.Engine(10, 128, seed=int(g["seed"]))
@@ -402,7 +335,7 @@ def test_refusals(scamd, dev, big):
         nl[2] = 219
         li[5, 0] = 4672
         nl[6] = -1
-        d_nl, d_li = dev.put(nl), dev.put(li)
+        d_nl, d_li = dev.upload(nl), dev.upload(li)
         ce, s5 = dev.alloc(n * 4), dev.alloc(5 * 8)
         rc = L.sc_score_positions(eng.h, n, d["boards"], d["meta"], None, d["dist_legal"], d_li, d_nl, d["outcome"], dev.stream, ce, None, None,
                                   None, s5)

@@ -12,18 +12,10 @@ import numpy as np
 import pytest
 
 import score_ref
+from support import _p, scamd_built  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sc_forward_device": 7, "sc_score_positions": 15, "sc_compare_engines": 9}
-
-
-@pytest.fixture(scope="module")
-def scamd():
-    sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-    import build as scbuild
-    scbuild.build()
-    import scamd as m
-    return m
 
 
 def test_new_symbols_are_declared_bound_and_exported(scamd):
@@ -41,10 +33,6 @@ def test_new_symbols_are_declared_bound_and_exported(scamd):
     assert callable(scamd.Engine.forward_torch)
     # the summaries are plain double arrays: the header declares no struct for them
     assert len(re.findall(r"typedef\s+struct\s*\{", hdr)) == 4
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def test_bad_arguments_are_refused_before_the_device(scamd):
