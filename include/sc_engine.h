@@ -319,6 +319,27 @@ int sc_selfplay_enable_timing(sc_selfplay*, int stride);
  * Needs n_games == n_slots (all games advance in lockstep, no slot recycling) and must precede the first enqueue.
  * Reference settings: with_noise = 0, outcome_gate = -1 (outcome after every ply), num_steps = 200, tie_random = 1. */
 int sc_selfplay_set_players(sc_selfplay*, sc_engine* white, sc_engine* black, uint64_t synth_salt_white, uint64_t synth_salt_black);
+/* Match play with slot recycling: n_games games on n_slots slots (any n_games >= 1), both colour assignments in one handle.
+ * Players: a = index 0, b = index 1 (engines for SC_EVAL_NET, the two salts for the synthetic evaluators).  Simulation step t is
+ * evaluated by player (t / rollout_num) & 1 for every slot, as with sc_selfplay_set_players; a game starts only at a ply
+ * boundary (t % rollout_num == 0) whose step its White evaluates, so games of different ages share the handle and a finished
+ * game's slot goes on with the next game.
+ * Colour rule: colours = 0: a is White in every game.  colours = 1: the White of game k (0-based on this handle, k = game_id -
+ * first_game_id) is player k & 1 -- a in the even games, b in the odd ones; with an odd n_games the extra game has a as White.
+ * Every game 0..n_games-1 is played exactly once; game k is the game a lockstep handle of its pairing plays under the same
+ * seed and game id.
+ * Idle bound: a slot whose game ends takes a game that can start at once if one is left (its White evaluates the ply that
+ * begins), else one of the other colour assignment, which starts one ply later: while games remain, a slot waits for at most
+ * one ply between two games (with a trace ring, a game also waits for its row as on every handle; with colours = 1 an odd ring
+ * size is used as the even number below it).  With colours = 0 a slot whose game ends after an odd number of plies waits one.
+ * Preconditions as sc_selfplay_set_players without n_games == n_slots: before the first enqueue, rollout_factor = 0, both
+ * engines on the handle's device and of the handle's split-K.  Reference settings as there.  < 0 on error (-3: no HIP device). */
+int sc_selfplay_set_match(sc_selfplay*, sc_engine* a, sc_engine* b, uint64_t synth_salt_a, uint64_t synth_salt_b, int colours);
+/* out[w*4 + r]: games finished so far with player w (0 = a, 1 = b) as White and
+ * result r = 0 White won, 1 Black won, 2 draw, 3 no outcome.
+ * Completes the enqueued work first.  Counted on the device when a game ends: it does not need the traces, which a ring
+ * (trace_capacity > 0) overwrites.  -1 on a handle without sc_selfplay_set_match. */
+int sc_selfplay_match_tally(sc_selfplay*, int64_t out[8]);
 int sc_selfplay_timing(sc_selfplay*, int reset, float* ms_total, float* ms_nn, int64_t* nn_launches);
 /* Kernel launches per simulation step this handle uses with SC_EVAL_NET (steps bracketed for sc_selfplay_timing always use 3):
  * 1 = the fused step kernel with value_head.ffn.0 inside (whole 64-slot blocks, every workgroup resident, and no other

@@ -117,6 +117,10 @@ extern "C" {
                              child_off: *mut i32, child_move: *mut u16, child_n: *mut i32, child_q: *mut f32,
                              child_uct: *mut f32) -> c_int;
     fn sc_selfplay_write_trace_json(sp: *mut ScSelfplay, game: c_int, path: *const c_char) -> c_int;
+    // evaluation matches (scripts/leader-board, src/play.rs:318-343): n_games on n_slots recycled slots, both colour assignments
+    fn sc_selfplay_set_match(sp: *mut ScSelfplay, a: *mut ScEngine, b: *mut ScEngine, synth_salt_a: u64, synth_salt_b: u64,
+                             colours: c_int) -> c_int;
+    fn sc_selfplay_match_tally(sp: *mut ScSelfplay, out: *mut i64) -> c_int;
     // NNPlayer::bestmove's search as one call (src/play.rs:241-252)
     fn sc_search(e: *mut ScEngine, moves: *const u16, n_moves: c_int, rollout: c_int, cpuct: f32, with_noise: c_int, seed: u64,
                  cap: c_int, child_move: *mut u16, child_n: *mut i32, child_q: *mut f32, child_prior: *mut f32,

@@ -202,10 +202,12 @@ struct sc_selfplay {
     bool have_span = false;
     int64_t nn_launches = 0;
     bool pending_final = false;
-    // match play (sc_selfplay_set_players): player of even / odd plies
+    // match play (sc_selfplay_set_players): player of even / odd plies; with slot recycling (sc_selfplay_set_match, p.match_recycle)
+    // players a / b, the evaluators of the launches t with (t / rollout) & 1 == 0 / 1
     bool match = false;
     sc_engine* player[2] = {nullptr, nullptr};
     uint64_t salt[2] = {0, 0};
+    long long* d_match_sum = nullptr;   // sc_selfplay_match_tally: the tally summed over the slots [8]
     scnn::bf16_t* d_hval = nullptr;  // value-head features of the current leaves [n_slots][64][256]
     float* d_vpart = nullptr;        // split-K partials of value_head.ffn.0 [ksplit][n_slots][128]
     // streaming drain (sc_selfplay_poll): per trace-ring row, the game id last reported to the host (+1; 0 = none)

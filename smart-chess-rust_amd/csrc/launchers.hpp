@@ -16,6 +16,8 @@ void debug_find_max(const float* d_u, int n, int* d_out, hipStream_t s);
 void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc, const float* d_temperature, const float* d_u, int tie_random,
                         const float* d_w, const int32_t* d_w_off, int w_max, int32_t* d_choice, float* d_total, hipStream_t s);
 void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s);
+void match_boundary(const sc::SpParams& p, hipStream_t s);   // match recycling: count the games that ended, start the next ones
+void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s);   // [n_slots][2][4] -> [8]
 // encode_kernels.hip (compiled with -ffp-contract=off)
 void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
                       int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,

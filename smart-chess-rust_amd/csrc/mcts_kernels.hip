@@ -65,12 +65,91 @@ __global__ __launch_bounds__(64) void k_synth_eval(SpParams p) {
     }
 }
 
+// ------------------------------------------------------------------ match play with slot recycling (sc_selfplay_set_match)
+// Every live game of a fixed-rollout handle ends its ply in the same launch, t % rollout == 0, and launch t is evaluated by
+// player (t / rollout) & 1 for ALL slots.  So games of different ages share a handle as long as each of them starts at such a
+// boundary, in a launch its White evaluates: from then on its even plies fall on its White's launches.  The search kernels know
+// nothing of this: the host gives them total_games = 0, so a slot whose game ends goes idle (start_new_game), and runs the two
+// phases of k_match_boundary between the two halves of a boundary launch -- after the expansions that end the ply, before the
+// selection of the next ply's first leaves.
+// The player that is White in game ordinal k:
+__device__ inline int match_white(const SpParams& p, unsigned long long k) { return p.match_colours ? (int)(k & 1) : 0; }
+// The next ordinal whose White is player `side`, or total_games when there is none left.  One counter per side keeps the
+// ordinals unique and every game 0..total_games-1 played once: with alternating colours side j draws j, j + 2, j + 4, ...
+// (an odd total leaves the extra game to player 0), otherwise side 0 draws 0, 1, 2, ... and side 1 nothing.
+__device__ inline unsigned long long match_ordinal(SpParams& p, int lane, int side) {
+    const unsigned long long total = (unsigned long long)p.total_games;
+    if (!p.match_colours && side) return total;
+    unsigned long long n = 0;
+    if (lane == 0) n = atomicAdd(&p.cnt->match_next[side], 1ULL);
+    n = __shfl(n, 0, 64);
+    const unsigned long long k = p.match_colours ? 2ULL * n + (unsigned long long)side : n;
+    return k < total ? k : total;
+}
+// Phase 1 for one slot.  A free slot takes a game that can start at THIS boundary if one is left, else one of the other side,
+// which starts one ply later: while games remain a slot waits one ply at the most between two games (a busy trace-ring row
+// aside).  A game that may not start yet parks its ordinal in the slot, as one that waits for a ring row does (try_start_game),
+// but as ST_MATCH_WAIT: the search kernel retries ST_PENDING in every launch, and a match game must start at a boundary.
+__device__ inline void match_slot_start(SpParams& p, int g, int lane) {
+    GameCtl& c = p.ctl[g];
+    const int st = c.status, side = p.match_side & 1;
+    const unsigned long long total = (unsigned long long)p.total_games;
+    unsigned long long k;
+    if (st == ST_MATCH_WAIT) {
+        k = c.game_id - p.first_game_id;
+    } else if (st == ST_IDLE) {
+        k = match_ordinal(p, lane, side);
+        if (k >= total) k = match_ordinal(p, lane, side ^ 1);
+        if (k >= total) return;
+    } else {
+        return;
+    }
+    wave_sync();
+    if (side == match_white(p, k)) {
+        try_start_game(p, g, lane, k);
+        if (lane == 0 && c.status == ST_PENDING) c.status = ST_MATCH_WAIT;
+    } else if (lane == 0) {
+        c.status = ST_MATCH_WAIT;
+        c.leaf_kind = LK_NONE;
+        c.game_id = p.first_game_id + k;
+    }
+}
+// phase 0: a slot whose game has ended since the last boundary counts it -- int32 [slot][White's player][White won / Black won
+// / draw / no outcome], the slot's own row -- from the game's trace header, which no later game can have taken yet: rows are
+// taken in phase 1 only, a launch of its own.  trace_slot < 0 marks the slot as counted.  phase 1: match_slot_start.
+__global__ __launch_bounds__(64) void k_match_boundary(SpParams p, int phase) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (phase == 1) {
+        match_slot_start(p, g, lane);
+        return;
+    }
+    GameCtl& c = p.ctl[g];
+    if (lane != 0 || c.status != ST_IDLE || c.trace_slot < 0) return;
+    const TraceHdr& th = p.thdr[c.trace_slot];
+    const int w = match_white(p, c.game_id - p.first_game_id);
+    const int r = !th.has_outcome ? 3 : th.winner == 1 ? 0 : th.winner == 0 ? 1 : 2;
+    p.match_tally()[((size_t)g * 2 + w) * 4 + r] += 1;
+    c.trace_slot = -1;
+}
+
 __global__ __launch_bounds__(64) void k_init_slots(SpParams p) {
     const int g = blockIdx.x, lane = threadIdx.x;
     uint4* b = reinterpret_cast<uint4*>(p.boards + (size_t)g * 7168);
     for (int i = lane; i < 448; i += 64) b[i] = make_uint4(0, 0, 0, 0);
     if (lane < 8) p.meta[(size_t)g * 8 + lane] = 0;
     if (lane == 0) p.n_legal[g] = 0;
+    if (p.match_recycle) {
+        // (sc_selfplay_set_match runs this kernel again on the handle's fresh state.)  This is the boundary of ply 0, player 0's:
+        // a slot takes a game with player 0 as White, which starts now, or one of player 1's and waits a ply
+        if (lane == 0) {
+            p.ctl[g].status = ST_IDLE;
+            p.ctl[g].leaf_kind = LK_NONE;
+            p.ctl[g].trace_slot = -1;
+        }
+        wave_sync();
+        match_slot_start(p, g, lane);
+        return;
+    }
     // slot g starts with game g (a deterministic slot <-> game map at start; later games are drawn from the counter as
     // slots free up); no game has finished yet, so nothing else touches the counter during this launch
     if (g == 0 && lane == 0)
@@ -124,6 +203,16 @@ __global__ __launch_bounds__(64) void k_mcts(SpParams p, int do_expand, int do_s
     if (do_select) dev_select(p, g, lane, s_stage, s_moves, &s_pos, s_ps, s_hist, cs_pre, cs_pre_valid);
 }
 
+// ------------------------------------------------------------------ sc_selfplay_match_tally
+// out[w * 4 + r] = the sum over the slots of tally[slot][w][r] (k_match_boundary); one wave, thread = column
+__global__ __launch_bounds__(64) void k_match_tally(const int32_t* tally, int n_slots, long long* out) {
+    const int j = threadIdx.x;
+    if (j >= 8) return;
+    long long s = 0;
+    for (int g = 0; g < n_slots; g++) s += tally[(size_t)g * 8 + j];
+    out[j] = s;
+}
+
 // ------------------------------------------------------------------ sc_selfplay_set_position
 __global__ __launch_bounds__(64) void k_set_position(SpParams p, int g, const uint16_t* moves, int n_moves) {
     const int lane = threadIdx.x;
@@ -168,6 +257,13 @@ void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc
     if (n_cases <= 0) return;
     hipLaunchKernelGGL(sc::k_debug_choose_child, dim3(n_cases), dim3(64), 0, s, n_cases, d_n_act, d_nc, d_temperature, d_u, tie_random,
                        d_w, d_w_off, w_max, d_choice, d_total);
+}
+void match_boundary(const sc::SpParams& p, hipStream_t s) {
+    hipLaunchKernelGGL(sc::k_match_boundary, dim3(p.n_slots), dim3(64), 0, s, p, 0);
+    hipLaunchKernelGGL(sc::k_match_boundary, dim3(p.n_slots), dim3(64), 0, s, p, 1);
+}
+void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s) {
+    hipLaunchKernelGGL(sc::k_match_tally, dim3(1), dim3(64), 0, s, d_tally, n_slots, d_out);
 }
 void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s) {
     hipLaunchKernelGGL(sc::k_set_position, dim3(1), dim3(64), 0, s, p, slot, d_moves, n_moves);

@@ -1,5 +1,6 @@
 // mcts_types.hpp -- device-resident state of the self-play engine (shared by host code and kernels).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "chess_rules.hpp"
@@ -7,7 +8,8 @@
 namespace sc {
 
 constexpr int MAXC = 224;  // SC_MAX_MOVES
-enum { ST_IDLE = 0, ST_ACTIVE = 1, ST_FINISHED = 2, ST_PENDING = 3 };   // PENDING: a game id is drawn, its trace-ring row is still in use
+enum { ST_IDLE = 0, ST_ACTIVE = 1, ST_FINISHED = 2, ST_PENDING = 3, ST_MATCH_WAIT = 4 };   // PENDING: a game id is drawn, its trace-ring row is still in use
+// MATCH_WAIT (sc_selfplay_set_match): a game id is drawn; the game starts at a ply boundary its White evaluates (k_match_boundary)
 enum { TR_FREE = 0, TR_LIVE = 1, TR_DONE = 2 };   // TraceHdr::state
 enum { SYNTH_HASH = 1, SYNTH_COARSE = 2, SYNTH_UNIFORM = 3 };   // SpParams::evaluator of the synthetic evaluators (sc_engine.h)
 enum { LK_NONE = 0, LK_EVAL = 1, LK_TERM_NEW = 2, LK_TERM_CACHED = 3 };
@@ -41,6 +43,7 @@ struct TraceHdr {
 struct Counters {
     unsigned long long next_game, sims_done, nn_evals, plies_done;
     int32_t games_finished, err;
+    unsigned long long match_next[2];   // match recycling: ordinals drawn so far per start side (mcts_kernels.hip match_ordinal)
 };
 
 struct SpParams {
@@ -48,6 +51,11 @@ struct SpParams {
     int tie_random;        // temperature 0: uniformly random child among the most visited (match play, src/play.rs:268-277)
     int trace_hold;        // trace ring: a finished trace is kept until the host has released it (sc_selfplay_poll); 0: overwritten
     float rollout_factor;  // > 0: per-ply budget min(300, n_legal * factor) instead of `rollout` (src/main.rs:175-176)
+    // Match play with slot recycling (sc_selfplay_set_match; 0 on every other handle), read by k_match_boundary and k_init_slots
+    // only.  match_side: the player (0 = a, 1 = b) that evaluates the ply which begins at this boundary.  match_colours 0: player 0
+    // is White in every game; 1: the White of game ordinal k is player k & 1.
+    // (Four bytes in what was padding in front of synth_salt: the argument block of the fused step kernel keeps its cache lines.)
+    uint8_t match_recycle, match_side, match_colours, match_pad;
     uint64_t synth_salt;   // synthetic evaluator: second deterministic "player" (match tests)
     float cpuct, temperature, epsilon;
     uint64_t seed, first_game_id;
@@ -80,6 +88,7 @@ struct SpParams {
     float* t_cu;
     Counters* cnt;
     unsigned long long* slot_cnt;   // [n_slots][2] simulations / network evaluations per slot (no contended atomics on the hot path)
+                                    // ... and behind them the match tally (match_tally() below)
     // fused value-head tail (NET evaluator): split-K partials of value_head.ffn.0 + fp32 parameters
     int vf_fused, vf_ksplit;
     const float* vpart;
@@ -90,6 +99,11 @@ struct SpParams {
     const float* choice_w;
     int choice_w_max;
     unsigned long long* dbg_cycles;  // optional [slot][32] stamps of the last launch (developer aid): 0..7 the search's cycle stamps, 8.. experiment builds
+    // Match recycling: finished games per slot, int32 [n_slots][2][4] by White's player and result (White won / Black won / draw /
+    // no outcome).  It lives in the tail of the slot_cnt allocation: a pointer of its own would take the argument block of the
+    // fused step kernel (700 bytes) into a twelfth cache line.
+    SC_HD int32_t* match_tally() const { return reinterpret_cast<int32_t*>(slot_cnt + (size_t)n_slots * 2); }
+    static constexpr size_t slot_cnt_words(size_t n_slots) { return n_slots * 2 + n_slots * 4; }   // 8-byte words of the allocation
 };
 
 

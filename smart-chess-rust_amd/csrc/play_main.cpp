@@ -11,6 +11,10 @@
 // the outcome (or null) stored in the trace.  Stockfish opponents (--black-type stockfish) are out of scope.
 // Extra flags (no reference counterpart): --games, --seed, --blocks / --channels / --white-seed / --black-seed (random
 // networks when no checkpoint is given).
+// --concurrency C plays the games on C recycled slots (sc_selfplay_set_match): a finished game's slot goes on with the next game.
+// --swap also plays --games games with the colours exchanged, in the same handle (scripts/leader-board:44-54 runs `play` twice):
+// their traces go to --swap-output (the leader-board's b_ prefix), numbered 1..games like the first set.  Without these flags
+// all games run in lockstep on --games slots, as before.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,8 +25,9 @@
 
 struct Args {
     std::string white_device, black_device = "<not-specified>", black_type = "stockfish";
-    std::string black_checkpoint = "<not-specified>", white_checkpoint = "<not-specified>", output = "01.json";
-    int rollout = 60, temperature_switch = 0, games = 1, blocks = 10, channels = 256;
+    std::string black_checkpoint = "<not-specified>", white_checkpoint = "<not-specified>", output = "01.json", swap_output;
+    int rollout = 60, temperature_switch = 0, games = 1, blocks = 10, channels = 256, concurrency = 0;
+    bool swap = false;
     float temperature = 0.0f, cpuct = 0.0f;
     unsigned long long seed = 0xC0FFEEULL, white_seed = 1, black_seed = 2;
 };
@@ -31,7 +36,8 @@ static void usage() {
     fprintf(stderr,
             "usage: sc-play --white-device cuda -w|--white-checkpoint W.scw [--black-device cuda] [--black-type nn]\n"
             "               [--black-checkpoint B.scw] [-r|--rollout 60] [--temperature 0] [--temperature-switch 0] [--cpuct 0]\n"
-            "               [-o|--output 01.json] [--games 1] [--seed S] [--blocks 10] [--channels 256] [--white-seed 1] [--black-seed 2]\n");
+            "               [-o|--output 01.json] [--games 1] [--seed S] [--blocks 10] [--channels 256] [--white-seed 1] [--black-seed 2]\n"
+            "               [--concurrency SLOTS] [--swap --swap-output b_01.json]\n");
 }
 
 static bool parse(int argc, char** argv, Args& a) {
@@ -64,6 +70,9 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (k == "--cpuct") a.cpuct = (float)atof(val());
         else if (k == "-o" || k == "--output") a.output = val();
         else if (k == "--games") a.games = atoi(val());
+        else if (k == "--concurrency") a.concurrency = atoi(val());
+        else if (k == "--swap" && !has) a.swap = true;
+        else if (k == "--swap-output") a.swap_output = val();
         else if (k == "--seed") a.seed = strtoull(val(), nullptr, 0);
         else if (k == "--blocks") a.blocks = atoi(val());
         else if (k == "--channels") a.channels = atoi(val());
@@ -75,8 +84,8 @@ static bool parse(int argc, char** argv, Args& a) {
     return true;
 }
 
-static std::string out_name(const Args& a, int game_number) {
-    std::string t = a.output;
+static std::string out_name(const Args& a, const std::string& pattern, int game_number) {
+    std::string t = pattern;
     size_t p = t.find("{}");
     if (p != std::string::npos) return t.substr(0, p) + std::to_string(game_number) + t.substr(p + 2);
     if (a.games == 1) return t;
@@ -107,6 +116,15 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--games and --rollout must be positive\n");
         return 2;
     }
+    const bool recycle = a.swap || a.concurrency != 0;
+    if (a.swap == a.swap_output.empty()) {
+        fprintf(stderr, "--swap and --swap-output go together\n");
+        return 2;
+    }
+    if (recycle && a.concurrency < 0) {
+        fprintf(stderr, "--concurrency must be positive\n");
+        return 2;
+    }
     if (sc_device_count() <= 0) {
         fprintf(stderr, "no MI355X visible\n");
         return 1;
@@ -120,7 +138,9 @@ int main(int argc, char** argv) {
     }
     printf("Players loaded.\n");   // play.rs:455
     sc_selfplay_config c{};
-    c.n_slots = c.n_games = a.games;
+    const int total = a.swap ? 2 * a.games : a.games;
+    c.n_games = total;
+    c.n_slots = recycle ? (a.concurrency > 0 && a.concurrency < total ? a.concurrency : total) : a.games;
     c.rollout_num = a.rollout;
     c.num_steps = 200;             // play.rs:325
     c.cpuct = a.cpuct;
@@ -134,29 +154,50 @@ int main(int argc, char** argv) {
     c.tie_random = 1;              // play.rs:268-277
     sc_selfplay* sp = nullptr;
     int rc = sc_selfplay_create(w, 0, &c, &sp);
-    if (!rc) rc = sc_selfplay_set_players(sp, w, b, 0, 0);
+    if (!rc) rc = recycle ? sc_selfplay_set_match(sp, w, b, 0, 0, a.swap ? 1 : 0) : sc_selfplay_set_players(sp, w, b, 0, 0);
     if (!rc) rc = sc_selfplay_run(sp, 0);
     if (rc) {
         fprintf(stderr, "%s\n", sc_last_error());
         return 1;
     }
-    int white = 0, black = 0, draw = 0, none = 0;
-    for (int g = 0; g < a.games; g++) {
+    // [0]: the games with --white-checkpoint's network as White, [1] (--swap): as Black; White won / Black won / draw / no outcome
+    long long res[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    for (int g = 0; g < total; g++) {
         sc_trace_info info{};
         if (sc_selfplay_get_trace(sp, g, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) continue;
-        if (!info.has_outcome) none++;
-        else if (info.winner == 1) white++;
-        else if (info.winner == 0) black++;
-        else draw++;
-        std::string path = out_name(a, (int)info.game_id + 1);
+        const int set = a.swap ? (int)(info.game_id & 1) : 0;
+        res[set][!info.has_outcome ? 3 : info.winner == 1 ? 0 : info.winner == 0 ? 1 : 2]++;
+        const int number = (int)(a.swap ? info.game_id / 2 : info.game_id) + 1;
+        std::string path = out_name(a, set ? a.swap_output : a.output, number);
         if (sc_selfplay_write_trace_json(sp, g, path.c_str())) {
             fprintf(stderr, "%s\n", sc_last_error());
             rc = 1;
         }
     }
-    // Total/WhiteWin/BlackWin is the input format of scripts/elo.py
-    printf("games %d white-wins %d black-wins %d draws %d unfinished %d   (elo.py input: %d/%d/%d)\n", a.games, white, black, draw, none,
-           a.games, white, black);
+    if (!recycle) {
+        // Total/WhiteWin/BlackWin is the input format of scripts/elo.py
+        printf("games %d white-wins %lld black-wins %lld draws %lld unfinished %lld   (elo.py input: %d/%lld/%lld)\n", a.games, res[0][0], res[0][1],
+               res[0][2], res[0][3], a.games, res[0][0], res[0][1]);
+    } else {
+        // the device's tally, which must agree with the traces just written; the elo.py triple is Total / wins of the --white-checkpoint
+        // network / wins of the --black-checkpoint network over both colour assignments
+        int64_t tally[8] = {0};
+        if (sc_selfplay_match_tally(sp, tally)) {
+            fprintf(stderr, "%s\n", sc_last_error());
+            rc = 1;
+        }
+        for (int i = 0; i < 8; i++)
+            if (tally[i] != res[i / 4][i % 4]) {
+                fprintf(stderr, "match tally [%d] = %lld differs from the traces' %lld\n", i, (long long)tally[i], res[i / 4][i % 4]);
+                rc = 1;
+            }
+        printf("games %d slots %d as-white: white-wins %lld black-wins %lld draws %lld unfinished %lld", total, c.n_slots, (long long)tally[0],
+               (long long)tally[1], (long long)tally[2], (long long)tally[3]);
+        if (a.swap)
+            printf("  as-black: white-wins %lld black-wins %lld draws %lld unfinished %lld", (long long)tally[4], (long long)tally[5],
+                   (long long)tally[6], (long long)tally[7]);
+        printf("   (elo.py input: %d/%lld/%lld)\n", total, (long long)(tally[0] + tally[5]), (long long)(tally[1] + tally[4]));
+    }
     sc_selfplay_destroy(sp);
     sc_engine_destroy(w);
     sc_engine_destroy(b);

@@ -66,11 +66,24 @@ static void match_tail_params(const sc_selfplay* sp, sc::SpParams& q, int64_t t)
     q.vf_fc2w = (uint32_t)ep->net.f_fc2w;
     q.vf_fc2b = (uint32_t)ep->net.f_fc2b;
 }
+// Match play with slot recycling.  The search launches never start a game (total_games = 0: a slot whose game ends goes idle);
+// games start at the ply boundaries, t % rollout == 0, between the two halves of launch t: after the expansions that end the
+// ply, k_match_boundary counts the games that ended and starts those whose White is the player of launch t, (t / rollout) & 1.
+static void match_search_params(const sc_selfplay* sp, sc::SpParams& q) {
+    if (sp->p.match_recycle) q.total_games = 0;
+}
+static void match_boundary(const sc_selfplay* sp, int64_t t) {
+    sc::SpParams q = sp->p;
+    q.match_side = (uint8_t)((t / q.rollout) & 1);
+    scl::match_boundary(q, sp->stream);
+}
 void sp_flush(sc_selfplay* sp) {
     if (sp->pending_final) {
         sc::SpParams q = sp->p;
         match_tail_params(sp, q, sp->sim_steps_enqueued - 1);
-        scl::mcts(q, 1, 0, sp->stream);
+        match_search_params(sp, q);
+        scl::mcts(q, 1, 0, sp->stream);   // the first half of the launch that the next enqueue starts with
+        if (sp->p.match_recycle && sp->sim_steps_enqueued % sp->p.rollout == 0) match_boundary(sp, sp->sim_steps_enqueued);
         sp->pending_final = false;
     }
 }
@@ -190,7 +203,7 @@ int sc_selfplay_create(sc_engine* e, int device_id, const sc_selfplay_config* cf
     rc |= sp_alloc(sp, &p.t_cq, T * S * 224, false);
     rc |= sp_alloc(sp, &p.t_cu, T * S * 224, false);
     rc |= sp_alloc(sp, &p.cnt, 1);
-    rc |= sp_alloc(sp, &p.slot_cnt, (size_t)cfg->n_slots * 2);
+    rc |= sp_alloc(sp, &p.slot_cnt, sc::SpParams::slot_cnt_words(G));
     // the temperature is fixed for the handle's life (sc_selfplay_set_players / sc_selfplay_set_search do not touch it), and no
     // ply searches more than rollout_num simulations (the cap of --rollout-factor, 300, is rollout_num: checked above)
     float* d_choice_w = nullptr;
@@ -326,6 +339,13 @@ int sc_selfplay_enqueue_sims(sc_selfplay* sp, int n) {
             e = sp->player[cur];
             q.synth_salt = sp->salt[cur];
             match_tail_params(sp, q, t - 1);
+            match_search_params(sp, q);
+            if (p.match_recycle && t > 0 && t % p.rollout == 0) {
+                // a ply boundary: the launch's first half on its own (a no-op where sp_flush has already run it), the games
+                // that end and start here, then the launch as usual (nothing is left for its first half to do)
+                scl::mcts(q, 1, 0, s);
+                match_boundary(sp, t);
+            }
         }
         if (p.evaluator != SC_EVAL_NET) {
             scl::mcts(q, 1, 1, s);   // finish the previous simulation (expand/backward/ply transition), select + encode the next leaf
@@ -389,6 +409,70 @@ int sc_selfplay_set_players(sc_selfplay* sp, sc_engine* white, sc_engine* black,
     return 0;
 }
 
+// sc_selfplay_set_players' preconditions on the rollout and the engines (not its n_games == n_slots)
+static int match_players_check(sc_selfplay* sp, sc_engine* a, sc_engine* b) {
+    if (sp->cfg.rollout_factor > 0.f) return fail("match play needs a fixed rollout (lockstep plies)");
+    if (sp->cfg.evaluator == SC_EVAL_NET) {
+        if (!a || !b) return fail("match play with SC_EVAL_NET needs two engines");
+        if (a->device != sp->device || b->device != sp->device) return fail("both engines must live on the handle's device");
+        if (a->ksplit != sp->engine->ksplit || b->ksplit != sp->engine->ksplit) return fail("engines differ in split-K");
+        TRY(engine_reserve(a, sp->cfg.n_slots));
+        TRY(engine_reserve(b, sp->cfg.n_slots));
+    }
+    return 0;
+}
+
+int sc_selfplay_set_match(sc_selfplay* sp, sc_engine* a, sc_engine* b, uint64_t salt_a, uint64_t salt_b, int colours) {
+    if (!sp) {
+        TRY(use_device(nullptr, 0));
+        return fail("null handle");
+    }
+    if (sp->poisoned) return sp_refuse(sp);
+    if (sp->sim_steps_enqueued != 0 || sp->match) return fail("set_match must precede the first enqueue (and any other choice of players)");
+    if (colours != 0 && colours != 1) return fail("set_match: colours must be 0 (a is White in every game) or 1 (a and b alternate as White)");
+    TRY(match_players_check(sp, a, b));
+    HIPOK(hipSetDevice(sp->device));
+    sc::SpParams& p = sp->p;
+    TRY(sp_alloc(sp, &sp->d_match_sum, 8));
+    // With alternating colours a game waits for its ring row's previous game, cap ordinals back: of the SAME side only if cap is
+    // even, and then drawn before it.  An odd ring could leave every slot waiting for games of the other side that no slot is
+    // left to draw.
+    if (colours && p.trace_cap < p.total_games && (p.trace_cap & 1)) p.trace_cap -= 1;   // (>= 2 * n_slots still)
+    // The slots were set up for plain self-play (sc_selfplay_create: slot g plays game g).  Nothing has run since: take that
+    // back and set them up again by the match's start rule.
+    HIPOK(hipDeviceSynchronize());   // (the zero-fills above ran on the NULL stream)
+    HIPOK(hipMemsetAsync(p.cnt, 0, sizeof(sc::Counters), sp->stream));
+    HIPOK(hipMemsetAsync(p.ctl, 0, (size_t)p.n_slots * sizeof(sc::GameCtl), sp->stream));
+    HIPOK(hipMemsetAsync(p.thdr, 0, (size_t)p.trace_cap * sizeof(sc::TraceHdr), sp->stream));
+    p.match_recycle = 1;
+    p.match_colours = (uint8_t)colours;
+    scl::init_slots(p, sp->stream);   // (match_side = 0: the boundary of ply 0)
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(sp->stream));
+    sp->match = true;
+    sp->player[0] = a;
+    sp->player[1] = b;
+    sp->salt[0] = salt_a;
+    sp->salt[1] = salt_b;
+    return 0;
+}
+
+int sc_selfplay_match_tally(sc_selfplay* sp, int64_t out[8]) {
+    if (!sp) {
+        TRY(use_device(nullptr, 0));
+        return fail("null handle");
+    }
+    if (!out) return fail("null argument");
+    if (!sp->p.match_recycle) return fail("match_tally needs a handle set up by sc_selfplay_set_match");
+    TRY(sp_quiesce(sp, true));
+    scl::match_tally(sp->p.match_tally(), sp->p.n_slots, sp->d_match_sum, sp->stream);
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(sp->stream));
+    static_assert(sizeof(long long) == sizeof(int64_t), "the reduction kernel writes int64");
+    HIPOK(hipMemcpy(out, sp->d_match_sum, 8 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int sc_selfplay_enqueue_interleaved(sc_selfplay** handles, int n_handles, int n) {
     if (!handles || n_handles <= 0 || n < 0) return fail("bad argument");
     for (int i = 0; i < n; i++)
@@ -409,7 +493,7 @@ int sc_selfplay_get_stats(sc_selfplay* sp, sc_selfplay_stats* out) {
     std::vector<sc::GameCtl> ctl((size_t)sp->p.n_slots);
     HIPOK(hipMemcpy(ctl.data(), sp->p.ctl, ctl.size() * sizeof(sc::GameCtl), hipMemcpyDeviceToHost));
     int active = 0;
-    for (auto& g : ctl) active += g.status == sc::ST_ACTIVE || g.status == sc::ST_PENDING;
+    for (auto& g : ctl) active += g.status == sc::ST_ACTIVE || g.status == sc::ST_PENDING || g.status == sc::ST_MATCH_WAIT;
     std::vector<unsigned long long> sc((size_t)sp->p.n_slots * 2);
     HIPOK(hipMemcpy(sc.data(), sp->p.slot_cnt, sc.size() * 8, hipMemcpyDeviceToHost));
     unsigned long long sims = 0, evals = 0;

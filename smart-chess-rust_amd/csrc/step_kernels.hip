@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256, 1) void k_step(scnn::TowerArgs A, sc::SpParams
 #ifdef SC_EXP
     const long long t_entry = clock64();   // experiment builds: the kernel's first instruction (tools/dbg_expand.py)
 #endif
-    // the two argument blocks: 684 bytes = 11 cache lines (kernarg_prefetch, nn_kernels.hpp)
+    // the two argument blocks: 700 bytes = 11 cache lines (kernarg_prefetch, nn_kernels.hpp)
     scnn::kernarg_prefetch<sizeof(scnn::TowerArgs) + sizeof(sc::SpParams) + sizeof(int)>();
 #ifdef SC_EXP
     if (p.dbg_cycles && threadIdx.x == 0) p.dbg_cycles[(size_t)g * 32 + 21] = t_entry;

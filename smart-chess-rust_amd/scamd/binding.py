@@ -82,6 +82,8 @@ ABI = {
     "sc_search": (_i, [_vp, _vp, _i, _i, _f, _i, C.c_uint64, _i, _vp, _vp, _vp, _vp, _vp]),
     "sc_selfplay_set_search": (_i, [_vp, _f, _f, _i]),
     "sc_selfplay_set_players": (_i, [_vp, _vp, _vp, C.c_uint64, C.c_uint64]),
+    "sc_selfplay_set_match": (_i, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _i]),
+    "sc_selfplay_match_tally": (_i, [_vp, _vp]),
     "sc_selfplay_enable_timing": (_i, [_vp, _i]),
     "sc_selfplay_timing": (_i, [_vp, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i64)]),
     "sc_selfplay_launches_per_step": (_i, [_vp]),

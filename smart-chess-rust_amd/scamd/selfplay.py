@@ -36,6 +36,19 @@ class SelfPlay(_Handle):
         self._players = (white, black)   # keep the engines alive
         _check(self.L.sc_selfplay_set_players(self.h, white.h if white else None, black.h if black else None, salt_white, salt_black))
 
+    def set_match(self, a=None, b=None, salt_a=0, salt_b=0, colours=1):
+        """match play with slot recycling (sc_selfplay_set_match): n_games games on n_slots slots; colours=1: `a` is White in
+        the even games of the handle and `b` in the odd ones, colours=0: `a` in all of them"""
+        self._players = (a, b)   # keep the engines alive
+        _check(self.L.sc_selfplay_set_match(self.h, a.h if a else None, b.h if b else None, salt_a, salt_b, colours))
+
+    def match_tally(self):
+        """sc_selfplay_match_tally: the games finished so far, by the player that was White and by result"""
+        out = np.zeros(8, np.int64)
+        _check(self.L.sc_selfplay_match_tally(self.h, _p(out)))
+        return {key: dict(zip(("White", "Black", "draw", "unfinished"), (int(x) for x in out[4 * w:4 * w + 4])))
+                for w, key in enumerate(("a_white", "b_white"))}
+
     def sync(self):
         _check(self.L.sc_selfplay_synchronize(self.h))
 
@@ -281,10 +294,15 @@ def elo(total, wins, losses):
 
 
 def play_match(a, b, n_games=100, rollout=100, cpuct=1.5, temperature=0.0, temperature_switch=0, num_steps=200, seed=0,
-               swap=True):
+               swap=True, concurrency=None):
     """Batched `scripts/leader-board:44-54`: n_games with engine `a` as White and `b` as Black, then (swap) the same
     number with the colours exchanged; every game is `play`'s loop (src/play.rs:241-343: no noise, outcome after every
-    ply, at most 200 plies, random tie-break).  -> dict(results per colour assignment, a's score, Elo of a over b)."""
+    ply, at most 200 plies, random tie-break).  -> dict(results per colour assignment, a's score, Elo of a over b).
+    concurrency=C: all games in ONE handle of min(C, games) recycled slots (SelfPlay.set_match): a finished game's slot goes
+    on with the next game, `a` is White in the handle's even games (as_white) and, with swap, `b` in the odd ones (as_black);
+    results come from the device's tally.  None: one lockstep handle of n_games slots per colour assignment."""
+    if concurrency is not None:
+        return _play_match_recycled(a, b, n_games, rollout, cpuct, temperature, temperature_switch, num_steps, seed, swap, int(concurrency))
     out = {"as_white": None, "as_black": None}
     tot = win = lost = 0
     # Both colour assignments play at the same time: each handle launches on the stream of its White engine, so the two sets of
@@ -327,6 +345,31 @@ def play_match(a, b, n_games=100, rollout=100, cpuct=1.5, temperature=0.0, tempe
         win += res[a_col]
         lost += res[b_col]
     out.update(total=tot, a_wins=win, b_wins=lost, elo_a_minus_b=elo(tot, win, lost))
+    return out
+
+
+def _play_match_recycled(a, b, n_games, rollout, cpuct, temperature, temperature_switch, num_steps, seed, swap, concurrency):
+    total = 2 * n_games if swap else n_games
+    if concurrency < 1:
+        raise ValueError("play_match: concurrency must be positive")
+    sp = SelfPlay(a, n_slots=min(concurrency, total), n_games=total, rollout_num=rollout, num_steps=num_steps, cpuct=cpuct,
+                  temperature=temperature, temperature_switch=temperature_switch, with_noise=False, outcome_gate=-1, seed=seed,
+                  tie_random=True)
+    sp.set_match(a, b, colours=1 if swap else 0)
+    while True:
+        sp.enqueue(2 * rollout)                  # two plies per look at the statistics
+        if sp.stats()["games_active"] == 0:
+            break
+    tally = sp.match_tally()
+    stride = 2 if swap else 1
+    out = {"as_white": dict(results=tally["a_white"], traces=[sp.trace(g) for g in range(0, total, stride)]), "as_black": None}
+    win, lost = tally["a_white"]["White"], tally["a_white"]["Black"]
+    if swap:
+        out["as_black"] = dict(results=tally["b_white"], traces=[sp.trace(g) for g in range(1, total, 2)])
+        win += tally["b_white"]["Black"]
+        lost += tally["b_white"]["White"]
+    sp.close()
+    out.update(total=total, a_wins=win, b_wins=lost, elo_a_minus_b=elo(total, win, lost))
     return out
 
 

@@ -1,0 +1,242 @@
+"""Match play with slot recycling (-m gpu): sc_selfplay_set_match plays n_games games on n_slots slots in both colour assignments.
+Every game must be the game the oracle's restatement of the `play` loop (src/play.rs:241-343) plays for its pairing, seed and id --
+whichever slot it lands in, whatever that slot played before and however long it waited -- and, with networks, bit for bit the
+game a lockstep handle (sc_selfplay_set_players) plays."""
+import pytest
+
+from support import scamd_gpu  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+
+SALT_A, SALT_B = 0x1111, 0x2222
+SEARCH = dict(rollout_num=16, cpuct=1.5, temperature=0.0, temperature_switch=2)
+HANDLE = dict(evaluator="synth", seed=21, first_game_id=40, with_noise=False, outcome_gate=-1, tie_random=True, **SEARCH)
+N_GAMES = 14
+ST_ACTIVE, ST_MATCH_WAIT = 1, 4   # (a drawn game that waits for a ply boundary of its White)
+KEYS = ("White", "Black", "draw", "unfinished")
+
+
+def _result(trace):
+    oc = trace["outcome"]
+    return "unfinished" if oc is None else "draw" if oc["winner"] is None else oc["winner"]
+
+
+def _count(traces):
+    """{"a_white": ..., "b_white": ...} over traces in ordinal order, colours alternating"""
+    out = {k: dict.fromkeys(KEYS, 0) for k in ("a_white", "b_white")}
+    for k, t in enumerate(traces):
+        out["b_white" if k & 1 else "a_white"][_result(t)] += 1
+    return out
+
+
+@pytest.fixture(scope="module")
+def oracle_games(orc):
+    """the 14 games of case 1 on the CPU oracle: the even ordinals have player a (salt 0x1111) as White, the odd ones player b"""
+    games = []
+    for k in range(N_GAMES):
+        w, b = (SALT_B, SALT_A) if k & 1 else (SALT_A, SALT_B)
+        games.append(orc.match_game(user_white=w, user_black=b, seed=21, game_id=40 + k, num_steps=200, **SEARCH))
+    # what makes the case a test of recycling: slots fall out of phase (an odd length flips the parity of the slot's next start)
+    # and finish at different plies
+    lengths = [len(g["steps"]) for g in games]
+    assert any(n & 1 for n in lengths) and len(set(lengths)) >= 3, lengths
+    return games
+
+
+@pytest.fixture(scope="module")
+def recycled(scamd):
+    sp = scamd.SelfPlay(None, n_slots=4, n_games=N_GAMES, num_steps=200, **HANDLE)
+    sp.set_match(None, None, SALT_A, SALT_B, colours=1)
+    sp.run()
+    traces = [sp.trace(k) for k in range(N_GAMES)]
+    out = dict(stats=sp.stats(), tally=sp.match_tally(), traces=traces)
+    sp.close()
+    return out
+
+
+def test_games_equal_the_oracle_with_slots_out_of_phase(recycled, oracle_games):
+    assert recycled["stats"]["error_flags"] == 0 and recycled["stats"]["games_finished"] == N_GAMES
+    assert recycled["stats"]["games_active"] == 0
+    for k, (tr, ref) in enumerate(zip(recycled["traces"], oracle_games)):
+        assert tr is not None and tr["game_id"] == 40 + k, k
+        assert tr["steps"] == ref["steps"], k
+        assert tr["outcome"] == ref["outcome"], k
+
+
+def test_tally_counts_the_games_by_colour(scamd, recycled, oracle_games):
+    want = _count(recycled["traces"])
+    assert recycled["tally"] == want
+    assert sum(sum(v.values()) for v in want.values()) == N_GAMES
+    assert want == _count(oracle_games)
+    assert sum(want["a_white"].values()) == 7 and sum(want["b_white"].values()) == 7
+    # a trace ring overwrites finished traces: the tally does not depend on them
+    sp = scamd.SelfPlay(None, n_slots=4, n_games=N_GAMES, num_steps=200, trace_capacity=8, **HANDLE)
+    sp.set_match(None, None, SALT_A, SALT_B, colours=1)
+    sp.run()
+    st = sp.stats()
+    assert st["error_flags"] == 0 and st["games_finished"] == N_GAMES and st["games_active"] == 0
+    assert sp.match_tally() == want
+    with pytest.raises(scamd.EngineError):   # ... while the first games' traces are gone
+        sp.trace(0)
+    sp.close()
+
+
+def test_colours_0_keeps_a_white(scamd, orc):
+    sp = scamd.SelfPlay(None, n_slots=3, n_games=7, num_steps=60, **HANDLE)
+    sp.set_match(None, None, SALT_A, SALT_B, colours=0)
+    sp.run()
+    st = sp.stats()
+    assert st["error_flags"] == 0 and st["games_finished"] == 7 and st["games_active"] == 0
+    traces = []
+    for k in range(7):
+        tr = sp.trace(k)
+        ref = orc.match_game(user_white=SALT_A, user_black=SALT_B, seed=21, game_id=40 + k, num_steps=60, **SEARCH)
+        assert tr is not None and tr["game_id"] == 40 + k and tr["steps"] == ref["steps"] and tr["outcome"] == ref["outcome"], k
+        traces.append(tr)
+    tally = sp.match_tally()
+    assert tally["b_white"] == dict.fromkeys(KEYS, 0)
+    want = dict.fromkeys(KEYS, 0)
+    for t in traces:
+        want[_result(t)] += 1
+    assert tally["a_white"] == want and sum(want.values()) == 7
+    sp.close()
+
+
+def test_no_slot_idles_for_two_plies_while_games_remain(scamd):
+    """the handle driven one ply at a time: until every game has been given to a slot, a slot is without a running game for one
+    ply at the most (its next game is of the other colour assignment and starts at the next ply boundary)"""
+    sp = scamd.SelfPlay(None, n_slots=4, n_games=N_GAMES, num_steps=200, **HANDLE)
+    sp.set_match(None, None, SALT_A, SALT_B, colours=1)
+    idle_before, pending_before = [False] * 4, [False] * 4
+    plies = 0
+    while True:
+        sp.enqueue(SEARCH["rollout_num"])
+        plies += 1
+        st = sp.stats()
+        status = [sp.slot(i)["status"] for i in range(4)]
+        idle = [s != ST_ACTIVE for s in status]
+        pending = [s == ST_MATCH_WAIT for s in status]
+        if st["games_finished"] + st["games_active"] < N_GAMES:
+            assert not any(x and y for x, y in zip(idle, idle_before)), (plies, status)
+        # (no trace ring here: a slot that holds a game waits for the game's colour only, at any time)
+        assert not any(x and y for x, y in zip(pending, pending_before)), (plies, status)
+        idle_before, pending_before = idle, pending
+        if st["games_active"] == 0:
+            break
+        assert plies < N_GAMES * 201
+    assert st["games_finished"] == N_GAMES and st["error_flags"] == 0
+    sp.close()
+
+
+def _lockstep(scamd, white, black, cfg):
+    sp = scamd.SelfPlay(white, n_slots=160, n_games=160, **cfg)
+    sp.set_players(white, black)
+    sp.run()
+    assert sp.stats()["error_flags"] == 0
+    traces = [sp.trace(g) for g in range(160)]
+    sp.close()
+    return traces
+
+
+def test_networks_bit_identical_to_the_lockstep_form(scamd):
+    a, b = scamd.Engine(2, 128, seed=1), scamd.Engine(1, 128, seed=2)
+    cfg = dict(rollout_num=8, num_steps=24, seed=3, first_game_id=0, cpuct=1.5, temperature=0.0, temperature_switch=0, with_noise=False,
+               outcome_gate=-1, tie_random=True)
+    ab = _lockstep(scamd, a, b, cfg)
+    ba = _lockstep(scamd, b, a, cfg)
+    assert all(t is not None and len(t["steps"]) >= 1 for t in ab + ba)
+    for n_slots, launches in ((64, 1), (40, 2)):
+        sp = scamd.SelfPlay(a, n_slots=n_slots, n_games=160, **cfg)
+        sp.set_match(a, b, colours=1)
+        assert sp.launches_per_step() == launches
+        sp.run()
+        st = sp.stats()
+        assert st["error_flags"] == 0 and st["games_finished"] == 160 and st["games_active"] == 0
+        for k in range(160):
+            assert sp.trace(k) == (ba if k & 1 else ab)[k], (n_slots, k)   # moves, visit counts and every float
+        sp.close()
+    a.close()
+    b.close()
+
+
+def test_refusals(scamd):
+    mk = lambda **kw: scamd.SelfPlay(None, **{**dict(n_slots=2, n_games=6, evaluator="synth", rollout_num=4, num_steps=4), **kw})
+    sp = mk()
+    sp.enqueue(1)
+    with pytest.raises(scamd.EngineError, match="first enqueue"):
+        sp.set_match(None, None, 1, 2)
+    sp.close()
+    sp = mk(rollout_num=300, rollout_factor=2.0)
+    with pytest.raises(scamd.EngineError, match="fixed rollout"):
+        sp.set_match(None, None, 1, 2)
+    sp.close()
+    sp = mk()
+    with pytest.raises(scamd.EngineError, match="colours"):
+        sp.set_match(None, None, 1, 2, colours=2)
+    with pytest.raises(scamd.EngineError, match="set_match"):   # a plain self-play handle has no tally
+        sp.match_tally()
+    with pytest.raises(scamd.EngineError, match="n_games == n_slots"):   # the lockstep form is what it was
+        sp.set_players(None, None, 1, 2)
+    sp.close()
+    eng = scamd.Engine(1, 128, seed=1)
+    sp = scamd.SelfPlay(eng, n_slots=2, n_games=6, rollout_num=4, num_steps=4)
+    with pytest.raises(scamd.EngineError, match="two engines"):
+        sp.set_match(eng, None)
+    sp.close()
+    eng.close()
+
+
+def test_play_match_with_concurrency(scamd, orc):
+    a, b = scamd.Engine(2, 128, seed=1), scamd.Engine(1, 128, seed=2)
+    r = scamd.play_match(a, b, n_games=6, rollout=12, num_steps=24, seed=3, concurrency=4)
+    assert set(r) == {"as_white", "as_black", "total", "a_wins", "b_wins", "elo_a_minus_b"} and r["total"] == 12
+    for key in ("as_white", "as_black"):
+        res, traces = r[key]["results"], r[key]["traces"]
+        assert set(res) == set(KEYS) and sum(res.values()) == 6 and len(traces) == 6
+        want = dict.fromkeys(KEYS, 0)
+        for t in traces:
+            assert t is not None and 1 <= len(t["steps"]) <= 24
+            assert t["game_id"] % 2 == (key == "as_black")
+            st = orc.State()
+            for mv, _q, kids in t["steps"]:
+                legal = st.legal_uci()
+                assert mv in legal and sorted(c[0] for c in kids) == sorted(legal)
+                st.push(orc.from_uci(mv))
+            want[_result(t)] += 1
+        assert res == want
+    aw, bw = r["as_white"]["results"], r["as_black"]["results"]
+    assert r["a_wins"] == aw["White"] + bw["Black"] and r["b_wins"] == aw["Black"] + bw["White"]
+    assert r["elo_a_minus_b"] == scamd.elo(12, r["a_wins"], r["b_wins"])
+    a.close()
+    b.close()
+
+
+def test_play_cli_swap_on_recycled_slots(tmp_path):
+    """sc-play --swap --concurrency: both colour assignments in one handle, each to its own file pattern, numbered 1..games, and a
+    summary line whose tally agrees with the files (the launcher itself exits non-zero if its traces and the device's tally differ)"""
+    import json
+    import os
+    import re
+    import subprocess
+    play = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "smart-chess-rust_amd", "lib", "sc-play")
+    common = [play, "--white-device", "cuda", "--black-device", "cuda", "--black-type", "nn", "--rollout=12", "--temperature", "0",
+              "--temperature-switch", "0", "--cpuct", "1.5", "--games", "5", "--blocks", "1", "--channels", "128", "--white-seed", "3",
+              "--black-seed", "4", "-o", str(tmp_path / "w_{}.json")]
+    r = subprocess.run(common + ["--swap"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--swap-output" in r.stderr
+    r = subprocess.run(common + ["--swap", "--swap-output", str(tmp_path / "b_{}.json"), "--concurrency", "4"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    m = re.search(r"games 10 slots 4 as-white: white-wins (\d+) black-wins (\d+) draws (\d+) unfinished (\d+)  as-black: white-wins (\d+) "
+                  r"black-wins (\d+) draws (\d+) unfinished (\d+)   \(elo\.py input: 10/(\d+)/(\d+)\)", r.stdout)
+    assert m, r.stdout
+    t = [int(x) for x in m.groups()]
+    for prefix, want in (("w", t[0:4]), ("b", t[4:8])):
+        got = [0, 0, 0, 0]
+        for k in range(1, 6):
+            js = json.load(open(str(tmp_path / f"{prefix}_{k}.json")))
+            assert list(js.keys()) == ["outcome", "steps"] and 1 <= len(js["steps"]) <= 200
+            oc = js["outcome"]
+            got[3 if oc is None else {"White": 0, "Black": 1, None: 2}[oc["winner"]]] += 1
+        assert got == want, (prefix, got, want)
+    assert t[8] == t[0] + t[5] and t[9] == t[1] + t[4]
+    assert sorted(os.listdir(tmp_path)) == sorted([f"{p}_{k}.json" for p in "wb" for k in range(1, 6)])
