@@ -340,6 +340,25 @@ int sc_selfplay_set_match(sc_selfplay*, sc_engine* a, sc_engine* b, uint64_t syn
  * Completes the enqueued work first.  Counted on the device when a game ends: it does not need the traces, which a ring
  * (trace_capacity > 0) overwrites.  -1 on a handle without sc_selfplay_set_match. */
 int sc_selfplay_match_tally(sc_selfplay*, int64_t out[8]);
+/* Opening lines for a match handle (after sc_selfplay_set_match, before the first enqueue; host pointers).
+ * Line i = moves[move_off[i] .. move_off[i+1]) from the start position, 0..600 plies (an empty line is the start position).
+ * Game ordinal k plays line (colours ? k >> 1 : k) % n_lines: with alternating colours games 2j and 2j+1 share a line.
+ * status (may be NULL) int32 [n_lines]: 0 ok; -(j+1): move j of the line is not legal; 1: the line's last position
+ * ends the game (outcome(claim_draw=True) is set, or there is no legal move).  Any non-zero status: returns -1 and the
+ * handle is as before the call.
+ * A game with a line of length L: its position chain 0..L (keys, repetition and irreversibility flags) is what
+ * sc_selfplay_set_position leaves for that move list; the search starts at ply L, and the trace holds the searched plies only
+ * (sc_selfplay_get_trace is unchanged).  num_steps, temperature_switch and outcome_gate count from the first searched ply; the
+ * end-of-ply draw stays keyed by the absolute ply: the game is the CONTINUATION of the from-the-start game of the same id and
+ * seed whose first L moves were the line.
+ * Start rule: the first searched ply belongs to player white(k) ^ (L & 1), and the game starts at a ply boundary of that player;
+ * a slot that draws a game of the other parity holds it for one ply, so the idle bound of sc_selfplay_set_match stands: at most
+ * one ply between two games while games remain, apart from trace-ring waits.  The tally stays by White's player.
+ * The lines are replayed and checked once, by this call; a game start copies L + 1 records on the device.
+ * sc_selfplay_encode_traces refuses (-1) a game whose line is not empty: training tensors need the plies from the start. */
+int sc_selfplay_set_openings(sc_selfplay*, int n_lines, const uint16_t* moves, const uint32_t* move_off, int32_t* status);
+/* the line of handle-local game `game` (pure function of the table and the rule above): returns its length, writes up to cap moves */
+int sc_selfplay_get_opening(sc_selfplay*, int game, uint16_t* moves, int cap);
 int sc_selfplay_timing(sc_selfplay*, int reset, float* ms_total, float* ms_nn, int64_t* nn_launches);
 /* Kernel launches per simulation step this handle uses with SC_EVAL_NET (steps bracketed for sc_selfplay_timing always use 3):
  * 1 = the fused step kernel with value_head.ffn.0 inside (whole 64-slot blocks, every workgroup resident, and no other
@@ -380,7 +399,8 @@ int sc_selfplay_poll(sc_selfplay*, int32_t* finished_games, int cap);
 int sc_selfplay_encode_traces(sc_selfplay*, int n, const int32_t* games, int apply_mirror, int layout, void* stream, uint32_t* ply_off,
                               void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal,
                               int32_t* status);
-/* Writes the reference's trace JSON (src/trace.rs:23-32; serde_json pretty, keys "outcome","steps"). */
+/* Writes the reference's trace JSON (src/trace.rs:23-32; serde_json pretty, keys "outcome","steps").  A game that started from a
+ * non-empty opening line (sc_selfplay_set_openings) gets a third key after "steps": "opening": ["e2e4", ...], the line's moves. */
 int sc_selfplay_write_trace_json(sc_selfplay*, int game, const char* path);
 
 /* tests / NNPlayer::bestmove (src/play.rs:241-288) support: current search tree of a slot in

@@ -121,6 +121,9 @@ extern "C" {
     fn sc_selfplay_set_match(sp: *mut ScSelfplay, a: *mut ScEngine, b: *mut ScEngine, synth_salt_a: u64, synth_salt_b: u64,
                              colours: c_int) -> c_int;
     fn sc_selfplay_match_tally(sp: *mut ScSelfplay, out: *mut i64) -> c_int;
+    // ... from opening lines: game k of the match starts from line (colours ? k >> 1 : k) % n_lines
+    fn sc_selfplay_set_openings(sp: *mut ScSelfplay, n_lines: c_int, moves: *const u16, move_off: *const u32, status: *mut i32) -> c_int;
+    fn sc_selfplay_get_opening(sp: *mut ScSelfplay, game: c_int, moves: *mut u16, cap: c_int) -> c_int;
     // NNPlayer::bestmove's search as one call (src/play.rs:241-252)
     fn sc_search(e: *mut ScEngine, moves: *const u16, n_moves: c_int, rollout: c_int, cpuct: f32, with_noise: c_int, seed: u64,
                  cap: c_int, child_move: *mut u16, child_n: *mut i32, child_q: *mut f32, child_prior: *mut f32,

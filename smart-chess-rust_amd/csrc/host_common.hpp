@@ -208,6 +208,11 @@ struct sc_selfplay {
     sc_engine* player[2] = {nullptr, nullptr};
     uint64_t salt[2] = {0, 0};
     long long* d_match_sum = nullptr;   // sc_selfplay_match_tally: the tally summed over the slots [8]
+    // opening lines (sc_selfplay_set_openings): the lines' position records on the device, replayed once, and the host's copy of
+    // the moves (sc_selfplay_get_opening, the trace JSON).  open_lines.n = 0: none
+    sc::MatchLines open_lines{nullptr, nullptr, 0};
+    std::vector<uint16_t> open_moves;
+    std::vector<uint32_t> open_move_off;   // [n + 1]
     scnn::bf16_t* d_hval = nullptr;  // value-head features of the current leaves [n_slots][64][256]
     float* d_vpart = nullptr;        // split-K partials of value_head.ffn.0 [ksplit][n_slots][128]
     // streaming drain (sc_selfplay_poll): per trace-ring row, the game id last reported to the host (+1; 0 = none)
@@ -240,5 +245,7 @@ int sp_latch(sc_selfplay* sp);   // called with the stream idle: looks at the de
 // the opening of a host read or write: set the device, sp_flush, wait for the stream; with `latch` also sp_latch, and refuse a
 // poisoned handle
 int sp_quiesce(sc_selfplay* sp, bool latch);
+// the opening line of handle-local game `game` (sc_selfplay_set_openings): its length, *moves = its first move; 0 without lines
+int sp_opening(const sc_selfplay* sp, int game, const uint16_t** moves);
 
 #pragma GCC visibility pop

@@ -9,14 +9,17 @@
 
 namespace scl {
 // mcts_kernels.hip (compiled with -ffp-contract=off)
-void init_slots(const sc::SpParams& p, hipStream_t s);
+void init_slots(const sc::SpParams& p, const sc::MatchLines& lines, hipStream_t s);
 void mcts(const sc::SpParams& p, int do_expand, int do_select, hipStream_t s);
 void synth_eval(const sc::SpParams& p, hipStream_t s);
 void debug_find_max(const float* d_u, int n, int* d_out, hipStream_t s);
 void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc, const float* d_temperature, const float* d_u, int tie_random,
                         const float* d_w, const int32_t* d_w_off, int w_max, int32_t* d_choice, float* d_total, hipStream_t s);
 void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s);
-void match_boundary(const sc::SpParams& p, hipStream_t s);   // match recycling: count the games that ended, start the next ones
+void match_boundary(const sc::SpParams& p, const sc::MatchLines& lines, hipStream_t s);   // match recycling: count the games that ended, start the next ones
+// sc_selfplay_set_openings: replay and check n_lines move lists into their records (rec_off as sc::MatchLines::off) -> status [n_lines]
+void open_lines(int n_lines, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_tab, const uint32_t* d_rec_off,
+                int32_t* d_status, hipStream_t s);
 void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s);   // [n_slots][2][4] -> [8]
 // encode_kernels.hip (compiled with -ffp-contract=off)
 void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,

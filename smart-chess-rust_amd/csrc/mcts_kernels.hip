@@ -86,11 +86,37 @@ __device__ inline unsigned long long match_ordinal(SpParams& p, int lane, int si
     const unsigned long long k = p.match_colours ? 2ULL * n + (unsigned long long)side : n;
     return k < total ? k : total;
 }
+// Opening lines (sc_selfplay_set_openings).  Game ordinal k plays line (colours ? k >> 1 : k) % n: with alternating colours the
+// games 2j and 2j + 1 share a line, each player is White on it once.
+__device__ inline int match_line_of(const SpParams& p, const MatchLines& ln, unsigned long long k) {
+    return (int)((p.match_colours ? k >> 1 : k) % (unsigned long long)ln.n);
+}
+// A game that has just become ST_ACTIVE (try_start_game: start position, ply 0) moves to the end of its line: the line's L + 1
+// records, replayed once by k_open_lines, become hist[0..L] of the slot, the last of them the root's position, and the search
+// starts at ply L.  Plain vector loads and stores, 8 bytes a lane; L + 1 <= hist_cap is the host's check.
+__device__ inline void match_copy_line(SpParams& p, int g, int lane, const Position* line, int len) {
+    constexpr int W = (int)(sizeof(Position) / 8);
+    static_assert(sizeof(Position) % 8 == 0, "a record is copied in 8-byte words");
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(line);
+    unsigned long long* hist = reinterpret_cast<unsigned long long*>(p.hist + (size_t)g * p.hist_cap);
+    unsigned long long* root = reinterpret_cast<unsigned long long*>(p.tpos + (size_t)g * p.tpos_cap);
+    const int words = (len + 1) * W;
+    wave_sync();   // (lane 0's stores of the start position, try_start_game, are complete before other lanes store to the same records)
+    for (int i = lane; i < words; i += 64) hist[i] = src[i];
+    if (lane < W) root[lane] = src[len * W + lane];
+    if (lane == 0) {
+        p.ctl[g].ply = len;
+        p.ctl[g].start_ply = len;
+    }
+}
 // Phase 1 for one slot.  A free slot takes a game that can start at THIS boundary if one is left, else one of the other side,
 // which starts one ply later: while games remain a slot waits one ply at the most between two games (a busy trace-ring row
 // aside).  A game that may not start yet parks its ordinal in the slot, as one that waits for a ring row does (try_start_game),
 // but as ST_MATCH_WAIT: the search kernel retries ST_PENDING in every launch, and a match game must start at a boundary.
-__device__ inline void match_slot_start(SpParams& p, int g, int lane) {
+// With opening lines the first searched ply of game k, ply L of the game, is its White's only if L is even: the game starts at a
+// boundary of player white(k) ^ (L & 1).  The ordinals are drawn as before -- the line, and with it the parity, is known only
+// once the ordinal is -- and a game of the other parity waits its one ply.
+__device__ inline void match_slot_start(SpParams& p, const MatchLines& ln, int g, int lane) {
     GameCtl& c = p.ctl[g];
     const int st = c.status, side = p.match_side & 1;
     const unsigned long long total = (unsigned long long)p.total_games;
@@ -105,9 +131,22 @@ __device__ inline void match_slot_start(SpParams& p, int g, int lane) {
         return;
     }
     wave_sync();
-    if (side == match_white(p, k)) {
+    int len = 0;
+    const Position* line = nullptr;
+    if (ln.n > 0) {
+        const int i = match_line_of(p, ln, k);
+        const uint32_t a = ln.off[i], b = ln.off[i + 1];
+        line = ln.tab + a;
+        len = (int)(b - a) - 1;
+    }
+    if (side == (match_white(p, k) ^ (len & 1))) {
         try_start_game(p, g, lane, k);
-        if (lane == 0 && c.status == ST_PENDING) c.status = ST_MATCH_WAIT;
+        int now = 0;
+        if (lane == 0) {
+            now = c.status;
+            if (now == ST_PENDING) c.status = ST_MATCH_WAIT;
+        }
+        if (len > 0 && __shfl(now, 0, 64) == ST_ACTIVE) match_copy_line(p, g, lane, line, len);
     } else if (lane == 0) {
         c.status = ST_MATCH_WAIT;
         c.leaf_kind = LK_NONE;
@@ -117,10 +156,10 @@ __device__ inline void match_slot_start(SpParams& p, int g, int lane) {
 // phase 0: a slot whose game has ended since the last boundary counts it -- int32 [slot][White's player][White won / Black won
 // / draw / no outcome], the slot's own row -- from the game's trace header, which no later game can have taken yet: rows are
 // taken in phase 1 only, a launch of its own.  trace_slot < 0 marks the slot as counted.  phase 1: match_slot_start.
-__global__ __launch_bounds__(64) void k_match_boundary(SpParams p, int phase) {
+__global__ __launch_bounds__(64) void k_match_boundary(SpParams p, MatchLines ln, int phase) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (phase == 1) {
-        match_slot_start(p, g, lane);
+        match_slot_start(p, ln, g, lane);
         return;
     }
     GameCtl& c = p.ctl[g];
@@ -132,22 +171,23 @@ __global__ __launch_bounds__(64) void k_match_boundary(SpParams p, int phase) {
     c.trace_slot = -1;
 }
 
-__global__ __launch_bounds__(64) void k_init_slots(SpParams p) {
+__global__ __launch_bounds__(64) void k_init_slots(SpParams p, MatchLines ln) {
     const int g = blockIdx.x, lane = threadIdx.x;
     uint4* b = reinterpret_cast<uint4*>(p.boards + (size_t)g * 7168);
     for (int i = lane; i < 448; i += 64) b[i] = make_uint4(0, 0, 0, 0);
     if (lane < 8) p.meta[(size_t)g * 8 + lane] = 0;
     if (lane == 0) p.n_legal[g] = 0;
     if (p.match_recycle) {
-        // (sc_selfplay_set_match runs this kernel again on the handle's fresh state.)  This is the boundary of ply 0, player 0's:
-        // a slot takes a game with player 0 as White, which starts now, or one of player 1's and waits a ply
+        // (sc_selfplay_set_match runs this kernel again on the handle's fresh state, and sc_selfplay_set_openings once more, with
+        // the lines.)  This is the boundary of ply 0, player 0's: a slot takes a game with player 0 as White, which starts now, or
+        // one of player 1's and waits a ply
         if (lane == 0) {
             p.ctl[g].status = ST_IDLE;
             p.ctl[g].leaf_kind = LK_NONE;
             p.ctl[g].trace_slot = -1;
         }
         wave_sync();
-        match_slot_start(p, g, lane);
+        match_slot_start(p, ln, g, lane);
         return;
     }
     // slot g starts with game g (a deterministic slot <-> game map at start; later games are drawn from the counter as
@@ -213,6 +253,50 @@ __global__ __launch_bounds__(64) void k_match_tally(const int32_t* tally, int n_
     out[j] = s;
 }
 
+// ------------------------------------------------------------------ sc_selfplay_set_openings
+// One wave per line, once per handle: replay line i from the start position into its records tab[rec_off[i] ..], as k_set_position
+// replays a slot's move list into its chain (the same replay_step: keys, repetition and irreversibility flags), with every move
+// checked against the generated legal moves.  status[i]: 0 ok; -(j + 1): move j is not legal; 1: the game is over in the line's
+// last position (outcome(claim_draw=True), or no legal move).  rec_off[i + 1] - rec_off[i] = the line's length + 1: the host's sum.
+__global__ __launch_bounds__(64) void k_open_lines(int n_lines, const uint16_t* moves, const uint32_t* move_off, Position* tab,
+                                                   const uint32_t* rec_off, int32_t* status) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n_lines) return;
+    __shared__ move_t s_moves[MAXC];
+    __shared__ Position s_np;
+    Position* hist = tab + rec_off[i];
+    const uint16_t* mv = moves + move_off[i];
+    const int nm = (int)(move_off[i + 1] - move_off[i]);
+    Position cur;
+    set_startpos(cur);
+    cur.key = position_key(cur);
+    if (lane == 0) hist[0] = cur;
+    __syncthreads();
+    int st = 0;
+    for (int j = 0; j < nm; j++) {
+        int nlm = 0;
+        gen_legal_wave(cur, s_moves, lane, nlm);
+        __syncthreads();
+        bool found = false;
+        for (int k = 0; k < nlm; k++)
+            if (s_moves[k] == mv[j]) found = true;
+        __syncthreads();
+        if (!found) {
+            st = -(j + 1);
+            break;
+        }
+        replay_step(cur, mv[j], j, hist, hist, &s_np, lane);
+    }
+    if (st == 0) {
+        int n = 0, winner = -1;
+        gen_legal_wave(cur, s_moves, lane, n);
+        __syncthreads();
+        const HistChain hc{hist};
+        if (outcome_claim_draw(hc, nm, &winner) != T_NONE || n == 0) st = 1;
+    }
+    if (lane == 0) status[i] = st;
+}
+
 // ------------------------------------------------------------------ sc_selfplay_set_position
 __global__ __launch_bounds__(64) void k_set_position(SpParams p, int g, const uint16_t* moves, int n_moves) {
     const int lane = threadIdx.x;
@@ -246,7 +330,9 @@ __global__ __launch_bounds__(64) void k_set_position(SpParams p, int g, const ui
 }  // namespace sc
 
 namespace scl {
-void init_slots(const sc::SpParams& p, hipStream_t s) { hipLaunchKernelGGL(sc::k_init_slots, dim3(p.n_slots), dim3(64), 0, s, p); }
+void init_slots(const sc::SpParams& p, const sc::MatchLines& lines, hipStream_t s) {
+    hipLaunchKernelGGL(sc::k_init_slots, dim3(p.n_slots), dim3(64), 0, s, p, lines);
+}
 void mcts(const sc::SpParams& p, int do_expand, int do_select, hipStream_t s) {
     hipLaunchKernelGGL(sc::k_mcts, dim3(p.n_slots), dim3(64), 0, s, p, do_expand, do_select);
 }
@@ -258,9 +344,14 @@ void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc
     hipLaunchKernelGGL(sc::k_debug_choose_child, dim3(n_cases), dim3(64), 0, s, n_cases, d_n_act, d_nc, d_temperature, d_u, tie_random,
                        d_w, d_w_off, w_max, d_choice, d_total);
 }
-void match_boundary(const sc::SpParams& p, hipStream_t s) {
-    hipLaunchKernelGGL(sc::k_match_boundary, dim3(p.n_slots), dim3(64), 0, s, p, 0);
-    hipLaunchKernelGGL(sc::k_match_boundary, dim3(p.n_slots), dim3(64), 0, s, p, 1);
+void match_boundary(const sc::SpParams& p, const sc::MatchLines& lines, hipStream_t s) {
+    hipLaunchKernelGGL(sc::k_match_boundary, dim3(p.n_slots), dim3(64), 0, s, p, lines, 0);
+    hipLaunchKernelGGL(sc::k_match_boundary, dim3(p.n_slots), dim3(64), 0, s, p, lines, 1);
+}
+void open_lines(int n_lines, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_tab, const uint32_t* d_rec_off,
+                int32_t* d_status, hipStream_t s) {
+    if (n_lines <= 0) return;
+    hipLaunchKernelGGL(sc::k_open_lines, dim3(n_lines), dim3(64), 0, s, n_lines, d_moves, d_move_off, d_tab, d_rec_off, d_status);
 }
 void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s) {
     hipLaunchKernelGGL(sc::k_match_tally, dim3(1), dim3(64), 0, s, d_tally, n_slots, d_out);

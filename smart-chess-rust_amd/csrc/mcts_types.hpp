@@ -106,5 +106,13 @@ struct SpParams {
     static constexpr size_t slot_cnt_words(size_t n_slots) { return n_slots * 2 + n_slots * 4; }   // 8-byte words of the allocation
 };
 
+// Opening lines of a match handle (sc_selfplay_set_openings), a further argument of k_match_boundary and k_init_slots (SpParams does
+// not grow).  Line i owns the records tab[off[i] .. off[i + 1]): its position chain from the start position, length + 1 of them.
+// n = 0 (no lines): tab and off are null and every game starts from the start position.
+struct MatchLines {
+    const Position* tab;
+    const uint32_t* off;   // [n + 1]
+    int n;
+};
 
 }  // namespace sc

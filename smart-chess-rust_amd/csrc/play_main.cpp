@@ -15,17 +15,24 @@
 // --swap also plays --games games with the colours exchanged, in the same handle (scripts/leader-board:44-54 runs `play` twice):
 // their traces go to --swap-output (the leader-board's b_ prefix), numbered 1..games like the first set.  Without these flags
 // all games run in lockstep on --games slots, as before.
+// --openings FILE starts game k from line k of FILE (sc_selfplay_set_openings; with --swap both games of a pair from the same line,
+// each network White once).  One line per opening: UCI moves separated by blanks; `#` starts a comment (a line that holds nothing
+// but a comment is skipped); an empty line is the start position.  The games then run on recycled slots (--concurrency, default
+// one slot per game).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <fstream>
+#include <sstream>
 #include <string>
+#include <vector>
 
 #include "../../include/sc_engine.h"
 
 struct Args {
     std::string white_device, black_device = "<not-specified>", black_type = "stockfish";
-    std::string black_checkpoint = "<not-specified>", white_checkpoint = "<not-specified>", output = "01.json", swap_output;
+    std::string black_checkpoint = "<not-specified>", white_checkpoint = "<not-specified>", output = "01.json", swap_output, openings;
     int rollout = 60, temperature_switch = 0, games = 1, blocks = 10, channels = 256, concurrency = 0;
     bool swap = false;
     float temperature = 0.0f, cpuct = 0.0f;
@@ -37,7 +44,7 @@ static void usage() {
             "usage: sc-play --white-device cuda -w|--white-checkpoint W.scw [--black-device cuda] [--black-type nn]\n"
             "               [--black-checkpoint B.scw] [-r|--rollout 60] [--temperature 0] [--temperature-switch 0] [--cpuct 0]\n"
             "               [-o|--output 01.json] [--games 1] [--seed S] [--blocks 10] [--channels 256] [--white-seed 1] [--black-seed 2]\n"
-            "               [--concurrency SLOTS] [--swap --swap-output b_01.json]\n");
+            "               [--concurrency SLOTS] [--swap --swap-output b_01.json] [--openings FILE]\n");
 }
 
 static bool parse(int argc, char** argv, Args& a) {
@@ -73,6 +80,7 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (k == "--concurrency") a.concurrency = atoi(val());
         else if (k == "--swap" && !has) a.swap = true;
         else if (k == "--swap-output") a.swap_output = val();
+        else if (k == "--openings") a.openings = val();
         else if (k == "--seed") a.seed = strtoull(val(), nullptr, 0);
         else if (k == "--blocks") a.blocks = atoi(val());
         else if (k == "--channels") a.channels = atoi(val());
@@ -80,6 +88,54 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (k == "--black-seed") a.black_seed = strtoull(val(), nullptr, 0);
         else if (k == "-h" || k == "--help") { usage(); exit(0); }
         else { fprintf(stderr, "unknown argument %s\n", k.c_str()); usage(); return false; }
+    }
+    return true;
+}
+
+// UCI text -> move (from | to << 6 | promo << 12), 0xffff if it is none
+static unsigned parse_uci(const std::string& t) {
+    if (t.size() < 4 || t.size() > 5) return 0xffff;
+    for (int i = 0; i < 4; i += 2)
+        if (t[i] < 'a' || t[i] > 'h' || t[i + 1] < '1' || t[i + 1] > '8') return 0xffff;
+    unsigned promo = 0;
+    if (t.size() == 5) {
+        const char* at = strchr("nbrq", t[4]);
+        if (!at || !t[4]) return 0xffff;
+        promo = 2u + (unsigned)(at - "nbrq");
+    }
+    return (unsigned)((t[1] - '1') * 8 + (t[0] - 'a')) | (unsigned)((t[3] - '1') * 8 + (t[2] - 'a')) << 6 | promo << 12;
+}
+
+// the opening file: moves and offsets as sc_selfplay_set_openings takes them, and the file's line number of every opening
+static bool read_openings(const std::string& path, std::vector<uint16_t>& moves, std::vector<uint32_t>& off, std::vector<int>& line_no) {
+    std::ifstream f(path);
+    if (!f) {
+        fprintf(stderr, "cannot open %s\n", path.c_str());
+        return false;
+    }
+    off.assign(1, 0);
+    std::string raw;
+    for (int no = 1; std::getline(f, raw); no++) {
+        const size_t hash = raw.find('#');
+        std::istringstream text(raw.substr(0, hash));
+        std::string tok;
+        size_t n = 0;
+        while (text >> tok) {
+            const unsigned m = parse_uci(tok);
+            if (m == 0xffff) {
+                fprintf(stderr, "%s:%d: '%s' is not a UCI move\n", path.c_str(), no, tok.c_str());
+                return false;
+            }
+            moves.push_back((uint16_t)m);
+            n++;
+        }
+        if (n == 0 && hash != std::string::npos) continue;   // a comment line
+        off.push_back((uint32_t)moves.size());
+        line_no.push_back(no);
+    }
+    if (line_no.empty()) {
+        fprintf(stderr, "%s: no opening lines\n", path.c_str());
+        return false;
     }
     return true;
 }
@@ -116,7 +172,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "--games and --rollout must be positive\n");
         return 2;
     }
-    const bool recycle = a.swap || a.concurrency != 0;
+    const bool recycle = a.swap || a.concurrency != 0 || !a.openings.empty();
+    std::vector<uint16_t> op_moves;
+    std::vector<uint32_t> op_off;
+    std::vector<int> op_line_no;
+    if (!a.openings.empty() && !read_openings(a.openings, op_moves, op_off, op_line_no)) return 2;
     if (a.swap == a.swap_output.empty()) {
         fprintf(stderr, "--swap and --swap-output go together\n");
         return 2;
@@ -155,6 +215,13 @@ int main(int argc, char** argv) {
     sc_selfplay* sp = nullptr;
     int rc = sc_selfplay_create(w, 0, &c, &sp);
     if (!rc) rc = recycle ? sc_selfplay_set_match(sp, w, b, 0, 0, a.swap ? 1 : 0) : sc_selfplay_set_players(sp, w, b, 0, 0);
+    if (!rc && !a.openings.empty()) {
+        std::vector<int32_t> status(op_line_no.size(), 0);
+        op_moves.push_back(0);   // (never an empty array)
+        rc = sc_selfplay_set_openings(sp, (int)op_line_no.size(), op_moves.data(), op_off.data(), status.data());
+        for (size_t i = 0; i < status.size(); i++)
+            if (status[i]) fprintf(stderr, "%s:%d: opening refused, status %d\n", a.openings.c_str(), op_line_no[i], status[i]);
+    }
     if (!rc) rc = sc_selfplay_run(sp, 0);
     if (rc) {
         fprintf(stderr, "%s\n", sc_last_error());

@@ -75,7 +75,7 @@ static void match_search_params(const sc_selfplay* sp, sc::SpParams& q) {
 static void match_boundary(const sc_selfplay* sp, int64_t t) {
     sc::SpParams q = sp->p;
     q.match_side = (uint8_t)((t / q.rollout) & 1);
-    scl::match_boundary(q, sp->stream);
+    scl::match_boundary(q, sp->open_lines, sp->stream);
 }
 void sp_flush(sc_selfplay* sp) {
     if (sp->pending_final) {
@@ -94,6 +94,13 @@ int sp_quiesce(sc_selfplay* sp, bool latch) {
     if (!latch) return 0;
     TRY(sp_latch(sp));
     return sp->poisoned ? sp_refuse(sp) : 0;
+}
+
+int sp_opening(const sc_selfplay* sp, int game, const uint16_t** moves) {
+    if (sp->open_lines.n <= 0) return 0;
+    const size_t i = (size_t)((sp->p.match_colours ? game >> 1 : game) % sp->open_lines.n);
+    if (moves) *moves = sp->open_moves.data() + sp->open_move_off[i];
+    return (int)(sp->open_move_off[i + 1] - sp->open_move_off[i]);
 }
 
 // The weights of the end-of-ply move choice (mcts::step, src/mcts.rs:313-315): w[n] = powf((float)n, 1.0f / temperature) for
@@ -262,7 +269,7 @@ int sc_selfplay_create(sc_engine* e, int device_id, const sc_selfplay_config* cf
     // stream: make them complete before the first kernel touches the buffers
     hipError_t he = hipDeviceSynchronize();
     if (he != hipSuccess) return bail(he, "hipDeviceSynchronize");
-    scl::init_slots(p, sp->stream);
+    scl::init_slots(p, sp->open_lines, sp->stream);
     if ((he = hipGetLastError()) != hipSuccess) return bail(he, "k_init_slots");
     if ((he = hipStreamSynchronize(sp->stream)) != hipSuccess) return bail(he, "k_init_slots");
     *out = sp;
@@ -446,7 +453,7 @@ int sc_selfplay_set_match(sc_selfplay* sp, sc_engine* a, sc_engine* b, uint64_t 
     HIPOK(hipMemsetAsync(p.thdr, 0, (size_t)p.trace_cap * sizeof(sc::TraceHdr), sp->stream));
     p.match_recycle = 1;
     p.match_colours = (uint8_t)colours;
-    scl::init_slots(p, sp->stream);   // (match_side = 0: the boundary of ply 0)
+    scl::init_slots(p, sp->open_lines, sp->stream);   // (match_side = 0: the boundary of ply 0; no lines yet)
     HIPOK(hipGetLastError());
     HIPOK(hipStreamSynchronize(sp->stream));
     sp->match = true;
@@ -455,6 +462,89 @@ int sc_selfplay_set_match(sc_selfplay* sp, sc_engine* a, sc_engine* b, uint64_t 
     sp->salt[0] = salt_a;
     sp->salt[1] = salt_b;
     return 0;
+}
+
+// The lines are replayed and checked ONCE, here (k_open_lines), into records that stay on the device; a game start copies its line's
+// records into the slot (k_match_boundary).  Nothing has run on the handle yet: as sc_selfplay_set_match does, the slots' initial
+// draw is taken back and made again, now with the lines.
+int sc_selfplay_set_openings(sc_selfplay* sp, int n_lines, const uint16_t* moves, const uint32_t* move_off, int32_t* status) {
+    if (!sp) return fail("null handle");
+    if (sp->poisoned) return sp_refuse(sp);
+    if (!sp->p.match_recycle) return fail("set_openings needs a handle set up by sc_selfplay_set_match");
+    if (sp->sim_steps_enqueued != 0) return fail("set_openings must precede the first enqueue");
+    if (n_lines < 1 || !move_off) return fail("set_openings: bad argument");
+    sc::SpParams& p = sp->p;
+    std::vector<uint32_t> rec_off((size_t)n_lines + 1, 0);
+    for (int i = 0; i < n_lines; i++) {
+        if (move_off[i + 1] < move_off[i]) return fail("set_openings: move_off must not decrease");
+        const uint32_t len = move_off[i + 1] - move_off[i];
+        if (len > 600 || (int64_t)len + 1 > (int64_t)p.hist_cap)
+            return fail("set_openings: line " + std::to_string(i) + " has " + std::to_string(len) + " plies (at most 600)");
+        rec_off[(size_t)i + 1] = rec_off[(size_t)i] + len + 1;
+        if ((size_t)rec_off[(size_t)i + 1] * sizeof(sc::Position) > ((size_t)1 << 30))
+            return fail("set_openings: the lines' position records exceed 1 GiB");
+    }
+    const size_t n_moves = move_off[n_lines], first = move_off[0], n_rec = rec_off[(size_t)n_lines];
+    if (n_moves > first && !moves) return fail("set_openings: bad argument");
+    if (status) std::fill(status, status + n_lines, 0);
+    HIPOK(hipSetDevice(sp->device));
+    ScopedDev<uint16_t> d_moves;
+    ScopedDev<uint32_t> d_moff, d_roff;
+    ScopedDev<int32_t> d_status;
+    ScopedDev<sc::Position> d_tab;
+    HIPOK(d_moves.alloc(n_moves));
+    HIPOK(d_moff.alloc((size_t)n_lines + 1));
+    HIPOK(d_roff.alloc((size_t)n_lines + 1));
+    HIPOK(d_status.alloc((size_t)n_lines));
+    HIPOK(d_tab.alloc(n_rec));
+    if (n_moves) HIPOK(hipMemcpy(d_moves.p, moves, n_moves * 2, hipMemcpyHostToDevice));
+    HIPOK(hipMemcpy(d_moff.p, move_off, ((size_t)n_lines + 1) * 4, hipMemcpyHostToDevice));
+    HIPOK(hipMemcpy(d_roff.p, rec_off.data(), ((size_t)n_lines + 1) * 4, hipMemcpyHostToDevice));
+    scl::open_lines(n_lines, d_moves.p, d_moff.p, d_tab.p, d_roff.p, d_status.p, sp->stream);
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(sp->stream));
+    std::vector<int32_t> st((size_t)n_lines);
+    HIPOK(hipMemcpy(st.data(), d_status.p, (size_t)n_lines * 4, hipMemcpyDeviceToHost));
+    if (status) std::copy(st.begin(), st.end(), status);
+    for (int i = 0; i < n_lines; i++)
+        if (st[(size_t)i] != 0)
+            return fail("set_openings: line " + std::to_string(i) + " has status " + std::to_string(st[(size_t)i]) +
+                        (st[(size_t)i] < 0 ? " (move " + std::to_string(-st[(size_t)i] - 1) + " is not legal)" : " (the game is over at its end)"));
+    // accepted: the slots' initial draw again, on the fresh state (sc_selfplay_set_match)
+    HIPOK(hipMemsetAsync(p.cnt, 0, sizeof(sc::Counters), sp->stream));
+    HIPOK(hipMemsetAsync(p.ctl, 0, (size_t)p.n_slots * sizeof(sc::GameCtl), sp->stream));
+    HIPOK(hipMemsetAsync(p.thdr, 0, (size_t)p.trace_cap * sizeof(sc::TraceHdr), sp->stream));
+    const sc::MatchLines lines{d_tab.p, d_roff.p, n_lines};
+    scl::init_slots(p, lines, sp->stream);
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(sp->stream));
+    // (a second call replaces the table of the first)
+    for (const void* old : {(const void*)sp->open_lines.tab, (const void*)sp->open_lines.off}) {
+        auto it = std::find(sp->allocs.begin(), sp->allocs.end(), old);
+        if (old && it != sp->allocs.end()) {
+            (void)hipFree(*it);
+            sp->allocs.erase(it);
+        }
+    }
+    sp->open_lines = lines;
+    sp->allocs.push_back(d_tab.p);
+    sp->allocs.push_back(d_roff.p);
+    d_tab.p = nullptr;
+    d_roff.p = nullptr;
+    sp->open_moves.clear();
+    if (n_moves > first) sp->open_moves.assign(moves + first, moves + n_moves);
+    sp->open_move_off.resize((size_t)n_lines + 1);
+    for (int i = 0; i <= n_lines; i++) sp->open_move_off[(size_t)i] = move_off[i] - (uint32_t)first;
+    return 0;
+}
+
+int sc_selfplay_get_opening(sc_selfplay* sp, int game, uint16_t* moves, int cap) {
+    if (!sp) return fail("null handle");
+    if (game < 0 || game >= sp->cfg.n_games || cap < 0 || (cap > 0 && !moves)) return fail("bad argument");
+    const uint16_t* mv = nullptr;
+    const int len = sp_opening(sp, game, &mv);
+    for (int i = 0; i < len && i < cap; i++) moves[i] = mv[i];
+    return len;
 }
 
 int sc_selfplay_match_tally(sc_selfplay* sp, int64_t out[8]) {

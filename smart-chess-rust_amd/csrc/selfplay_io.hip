@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "host_common.hpp"
+#include "trace_json.hpp"
 
 // A row that sc_selfplay_poll has reported and holds (trace_hold) is final, and no kernel writes it until the next poll releases it
 static bool row_held(const sc_selfplay* sp, int row, uint64_t want_id) {
@@ -130,6 +131,9 @@ int sc_selfplay_encode_traces(sc_selfplay* sp, int n, const int32_t* games, int 
     for (int i = 0; i < n; i++) {
         const int g = games[i];
         if (g < 0 || g >= p.total_games) return fail("bad argument: game index out of range");
+        if (sp_opening(sp, g, nullptr) > 0)
+            return fail("encode_traces: game " + std::to_string(g) + " started from an opening line (sc_selfplay_set_openings): training tensors "
+                        "need the plies from the start position");
         const int row = g % p.trace_cap;
         rows[(size_t)i] = row;
         all_held = all_held && row_held(sp, row, p.first_game_id + (uint64_t)g);   // the readiness rules of sc_selfplay_get_trace
@@ -173,7 +177,19 @@ int sc_selfplay_write_trace_json(sc_selfplay* sp, int game, const char* path) {
     std::vector<float> sq((size_t)info.n_steps + 1), cq((size_t)info.n_children_total + 1), cu((size_t)info.n_children_total + 1);
     std::vector<int32_t> co((size_t)info.n_steps + 2), cn((size_t)info.n_children_total + 1);
     TRY(sc_selfplay_get_trace(sp, game, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data()));
-    return sc_trace_write_json(path, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data());
+    const uint16_t* line = nullptr;
+    const int len = sp_opening(sp, game, &line);
+    if (len == 0) return sc_trace_write_json(path, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data());
+    // a game that started from an opening line: a third key, "opening", behind the reference's two
+    if (!path) return fail("bad argument");
+    const std::string js = sctrace::trace_to_json(info.n_steps, info.has_outcome, info.termination, info.winner, sm.data(), sq.data(), co.data(),
+                                                  cm.data(), cn.data(), cq.data(), cu.data(), line, len);
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail(std::string("cannot open ") + path);
+    const size_t w = fwrite(js.data(), 1, js.size(), f);
+    fclose(f);
+    if (w != js.size()) return fail("short write");
+    return 0;
 }
 
 int sc_selfplay_get_tree(sc_selfplay* sp, int slot, int cap, int32_t* n, float* q, float* uct, float* prior, uint16_t* move,

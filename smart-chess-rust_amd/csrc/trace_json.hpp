@@ -1,7 +1,8 @@
 // trace_json.hpp -- writer for the reference's trace file (src/trace.rs:5-42).
 //
 // Trace::save serialises json!({"steps": ..., "outcome": ...}) with serde_json::to_string_pretty:
-//   * object keys in BTreeMap order: "outcome" before "steps" (and "termination" before "winner");
+//   * object keys in BTreeMap order: "outcome" before "steps" (and "termination" before "winner"); a game from an opening line
+//     adds "opening" behind them (sc_selfplay_set_openings);
 //   * 2-space indentation, every array element on its own line;
 //   * steps[i] = [uci, q_root, [[uci, N, Q_sum, uct], ...]] (src/main.rs:198-218);
 //   * f32 values are widened to f64 and printed with the shortest round-trip representation in
@@ -82,7 +83,8 @@ static const char* TERMINATION_NAMES[] = {"", "Checkmate", "Stalemate", "Insuffi
 
 inline std::string trace_to_json(int n_steps, int has_outcome, int termination, int winner, const uint16_t* step_move,
                                  const float* step_q, const int32_t* child_off, const uint16_t* child_move,
-                                 const int32_t* child_n, const float* child_q, const float* child_uct) {
+                                 const int32_t* child_n, const float* child_q, const float* child_uct, const uint16_t* opening = nullptr,
+                                 int n_opening = 0) {
     std::string o;
     o.reserve((size_t)n_steps * 4096 + 256);
     char mv[8];
@@ -130,6 +132,18 @@ inline std::string trace_to_json(int n_steps, int has_outcome, int termination, 
             }
             o += "\n    ]";
             o += i + 1 < n_steps ? ",\n" : "\n";
+        }
+        o += "  ]";
+    }
+    // (no reference counterpart) the opening line a match game started from, sc_selfplay_set_openings: "steps" holds the searched
+    // plies only.  Absent for a game from the start position: the file is then the reference's, byte for byte.
+    if (n_opening > 0) {
+        o += ",\n  \"opening\": [\n";
+        for (int i = 0; i < n_opening; i++) {
+            move_uci(opening[i], mv);
+            o += "    \"";
+            o += mv;
+            o += i + 1 < n_opening ? "\",\n" : "\"\n";
         }
         o += "  ]";
     }

@@ -84,6 +84,8 @@ ABI = {
     "sc_selfplay_set_players": (_i, [_vp, _vp, _vp, C.c_uint64, C.c_uint64]),
     "sc_selfplay_set_match": (_i, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _i]),
     "sc_selfplay_match_tally": (_i, [_vp, _vp]),
+    "sc_selfplay_set_openings": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "sc_selfplay_get_opening": (_i, [_vp, _i, _vp, _i]),
     "sc_selfplay_enable_timing": (_i, [_vp, _i]),
     "sc_selfplay_timing": (_i, [_vp, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i64)]),
     "sc_selfplay_launches_per_step": (_i, [_vp]),

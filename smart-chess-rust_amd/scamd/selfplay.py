@@ -4,8 +4,8 @@ import math
 
 import numpy as np
 
-from .binding import (EVALUATORS, MAX_MOVES, TERMINATION, SelfplayConfig, Stats, TraceInfo, _check, _count, _Handle, _moves, _p,
-                      _stream, _torch, lib, move_uci)
+from .binding import (EVALUATORS, MAX_MOVES, TERMINATION, EngineError, SelfplayConfig, Stats, TraceInfo, _check, _count, _Handle,
+                      _moves, _p, _stream, _torch, lib, move_uci)
 from .net import ChessHip, encode_positions
 from .training import _device_outputs, _finish_outputs
 
@@ -41,6 +41,28 @@ class SelfPlay(_Handle):
         the even games of the handle and `b` in the odd ones, colours=0: `a` in all of them"""
         self._players = (a, b)   # keep the engines alive
         _check(self.L.sc_selfplay_set_match(self.h, a.h if a else None, b.h if b else None, salt_a, salt_b, colours))
+
+    def set_openings(self, lines):
+        """sc_selfplay_set_openings: game k of a match handle starts from line opening_of_game(k, len(lines), colours); a line
+        is a list of UCI strings or uint16 moves (empty: the start position).  Raises EngineError with .status, the per-line
+        codes (0 ok, -(j+1): move j is not legal, 1: the line's last position ends the game), when the call is refused."""
+        lines = [_moves(ln)[:len(ln)] for ln in lines]
+        off = np.zeros(len(lines) + 1, np.uint32)
+        off[1:] = np.cumsum([ln.size for ln in lines])
+        mv = np.ascontiguousarray(np.concatenate(lines + [np.zeros(1, np.uint16)]), np.uint16)
+        status = np.zeros(max(len(lines), 1), np.int32)
+        rc = self.L.sc_selfplay_set_openings(self.h, len(lines), _p(mv), _p(off), _p(status))
+        if rc != 0:
+            e = EngineError(f"libsc_engine error {rc}: {self.L.sc_last_error().decode()}")
+            e.code, e.status = rc, [int(x) for x in status[:len(lines)]]
+            raise e
+
+    def get_opening(self, game):
+        """sc_selfplay_get_opening: the line handle-local game `game` starts from, as UCI strings"""
+        n = _count(self.L.sc_selfplay_get_opening(self.h, game, None, 0))
+        buf = np.zeros(max(n, 1), np.uint16)
+        _count(self.L.sc_selfplay_get_opening(self.h, game, _p(buf), n))
+        return [move_uci(m) for m in buf[:n]]
 
     def match_tally(self):
         """sc_selfplay_match_tally: the games finished so far, by the player that was White and by result"""
@@ -293,16 +315,45 @@ def elo(total, wins, losses):
     return 400 * math.log(s / (1 - s), 10)
 
 
+def opening_of_game(k, n_lines, colours):
+    """the line handle-local game k starts from (sc_selfplay_set_openings): with alternating colours games 2j and 2j + 1 share
+    line j % n_lines, so every line is played once with each player as White; otherwise game k plays line k % n_lines"""
+    return ((k >> 1) if colours else k) % n_lines
+
+
+def read_openings(path):
+    """An opening file -> list of lines (lists of UCI strings).  One line per opening: UCI moves separated by blanks; `#` starts
+    a comment (a line that holds nothing but a comment is skipped); an empty line is the start position."""
+    import re
+    lines = []
+    with open(path) as f:
+        for no, raw in enumerate(f, 1):
+            text = raw.split("#", 1)[0]
+            if "#" in raw and not text.strip():
+                continue
+            toks = text.split()
+            for t in toks:
+                if not re.fullmatch(r"[a-h][1-8][a-h][1-8][nbrq]?", t):
+                    raise ValueError(f"{path}:{no}: '{t}' is not a UCI move")
+            lines.append(toks)
+    return lines
+
+
 def play_match(a, b, n_games=100, rollout=100, cpuct=1.5, temperature=0.0, temperature_switch=0, num_steps=200, seed=0,
-               swap=True, concurrency=None):
+               swap=True, concurrency=None, openings=None):
     """Batched `scripts/leader-board:44-54`: n_games with engine `a` as White and `b` as Black, then (swap) the same
     number with the colours exchanged; every game is `play`'s loop (src/play.rs:241-343: no noise, outcome after every
     ply, at most 200 plies, random tie-break).  -> dict(results per colour assignment, a's score, Elo of a over b).
     concurrency=C: all games in ONE handle of min(C, games) recycled slots (SelfPlay.set_match): a finished game's slot goes
     on with the next game, `a` is White in the handle's even games (as_white) and, with swap, `b` in the odd ones (as_black);
-    results come from the device's tally.  None: one lockstep handle of n_games slots per colour assignment."""
+    results come from the device's tally.  None: one lockstep handle of n_games slots per colour assignment.
+    openings: lines (SelfPlay.set_openings) the games start from -- with swap each line is played once with each engine as White;
+    needs the recycled form (concurrency None: one slot per game)."""
+    if openings is not None and concurrency is None:
+        concurrency = 2 * n_games if swap else n_games
     if concurrency is not None:
-        return _play_match_recycled(a, b, n_games, rollout, cpuct, temperature, temperature_switch, num_steps, seed, swap, int(concurrency))
+        return _play_match_recycled(a, b, n_games, rollout, cpuct, temperature, temperature_switch, num_steps, seed, swap, int(concurrency),
+                                    openings)
     out = {"as_white": None, "as_black": None}
     tot = win = lost = 0
     # Both colour assignments play at the same time: each handle launches on the stream of its White engine, so the two sets of
@@ -348,7 +399,7 @@ def play_match(a, b, n_games=100, rollout=100, cpuct=1.5, temperature=0.0, tempe
     return out
 
 
-def _play_match_recycled(a, b, n_games, rollout, cpuct, temperature, temperature_switch, num_steps, seed, swap, concurrency):
+def _play_match_recycled(a, b, n_games, rollout, cpuct, temperature, temperature_switch, num_steps, seed, swap, concurrency, openings=None):
     total = 2 * n_games if swap else n_games
     if concurrency < 1:
         raise ValueError("play_match: concurrency must be positive")
@@ -356,6 +407,8 @@ def _play_match_recycled(a, b, n_games, rollout, cpuct, temperature, temperature
                   temperature=temperature, temperature_switch=temperature_switch, with_noise=False, outcome_gate=-1, seed=seed,
                   tie_random=True)
     sp.set_match(a, b, colours=1 if swap else 0)
+    if openings is not None:
+        sp.set_openings(openings)
     while True:
         sp.enqueue(2 * rollout)                  # two plies per look at the statistics
         if sp.stats()["games_active"] == 0:
