@@ -26,6 +26,7 @@
  */
 #ifndef SC_ENGINE_H
 #define SC_ENGINE_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -48,6 +49,7 @@ const char* sc_last_error(void);
  *   _get_trace / _write_trace_json refuse with this code; sc_selfplay_get_stats still answers (the flags).  Destroy the handle;
  *   handles created afterwards on that device use the two-launch step, which has no hand-off between workgroups. */
 #define SC_ERR_HANDOFF (-5)
+#define SC_ERR_CAPACITY (-4)   /* sc_san_tokenize: the token buffer is too small */
 int sc_device_count(void);
 /* Launch-path state of the HIP runtime in this process, bit mask.  The engine's three launches per simulation step are
  * ~6 % faster with kernel arguments in device memory (HIP_FORCE_DEV_KERNARG=1), which the HIP runtime reads ONCE, when
@@ -166,6 +168,46 @@ int sc_encode_steps_device(sc_engine* engine_or_null, int device_id, int n_games
                            const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int layout,
                            void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
                            int32_t* n_legal, int32_t* status);
+
+/* ------------------------------------------------------------------ games written as SAN movetext (PGN, the reference's sample.csv) */
+/* One game's movetext -> one token per half-move, on the host (no GPU is needed).  A token holds the SAN characters of the
+ * half-move, character k in byte k of the uint64 (little-endian), zero-padded, at most 7 of them, with the suffix run of + # ! ?
+ * stripped: "Nbd2", "exd8=Q", "O-O-O".  Skipped: move numbers ("12.", "12...", glued "1.e4"), {...} comments, ; comments to the
+ * end of the line, (...) variations (nested; comments inside them are opaque), $n NAGs, [...] header tags, annotation glyphs
+ * standing alone.  The text ends at a result token (1-0, 0-1, 1/2-1/2, *) or after `len` bytes; it need not be zero-terminated.
+ * Anything else -- a word of more than 7 characters after stripping, a closing bracket that closes nothing -- is stored as the
+ * reserved value 0xFFFFFFFFFFFFFFFF, which sc_encode_san_device reports as malformed at that ply: the token count stays the
+ * number of half-moves of the text.
+ * *n_tokens = that count.  If it exceeds cap the call returns SC_ERR_CAPACITY; the first cap tokens are written and nothing past
+ * them (tokens may be NULL with cap 0: a count query). */
+int sc_san_tokenize(const char* text, size_t len, uint64_t* tokens, uint32_t cap, uint32_t* n_tokens);
+
+/* SAN tokens -> moves and training tensors in one call: the reference's ValidationDataset (py/dataset.py:90-128, python-chess's
+ * read_game + parse_san, then chess_encode_steps on a trace whose children are the legal moves with count 1 on the move played
+ * and 0 elsewhere) for a batch of games from the start position.
+ *   tokens / tok_off   host, as moves / move_off of sc_encode_steps_device: the tokens of game g are tokens[tok_off[g] ..
+ *                      tok_off[g+1]), P = tok_off[n_games]; at most 4000 per game
+ * The parser runs on the device, one wavefront per game, against the generated legal moves.  Grammar: python-chess's SAN pattern
+ * with upper-case pieces, [NBRQK]?[a-h]?[1-8]?[x-]?[a-h][1-8](=?[NBRQ])?, and O-O / O-O-O written with the letter O or the digit
+ * 0.  A legal move answers to a token when its destination and promotion piece (none = none) are the token's, the moving piece
+ * is the named one (a pawn when none is named) and its origin file and / or rank is what the token gives; castling is the king's
+ * move from the e-file to the g- / c-file of the mover's back rank.  Over-specified disambiguation is accepted; the capture mark
+ * is not verified (python-chess does not either).  Since only LEGAL moves are candidates, "Nd2" is unique when the other knight
+ * is pinned.  Claimable draws do not end a game (read_game plays on too).
+ * Outputs, device pointers, any may be NULL except status; pointer checks, layouts, stream contract and scratch arena as
+ * sc_encode_steps_device; the parsed moves reach the encoder in device memory, nothing returns to the host in between.
+ *   boards, meta, legal_idx, n_legal   as sc_encode_steps_device for the parsed moves
+ *   dist, dist_legal   float32(1 / (1 + 1e-5)) at the move played, 0 elsewhere: bit-identical to sc_encode_steps_device given
+ *                      those children
+ *   moves   uint16 [P]: the parsed moves (a call with only moves and status is plain "SAN -> moves": no encoder work is enqueued)
+ *   status  int32 [n_games]: 0 ok; -(i+1): token i names no legal move (any token after mate or stalemate does); 100000 + i:
+ *           token i answers to more than one legal move; 200000 + i: token i is malformed or the reserved value.  The first
+ *           failing ply of a game wins and the other games of the call are not affected; outputs of a game at and after its
+ *           failing ply are unspecified.
+ * Returns 0, or < 0 as every entry point (-3: no HIP device). */
+int sc_encode_san_device(sc_engine* engine_or_null, int device_id, int n_games, const uint64_t* tokens, const uint32_t* tok_off,
+                         int apply_mirror, int layout, void* stream, void* boards, void* meta, float* dist, float* dist_legal,
+                         uint16_t* legal_idx, int32_t* n_legal, uint16_t* moves, int32_t* status);
 
 /* ------------------------------------------------------------------ network on device tensors: forward, losses, agreement */
 /* sc_forward_batch on DEVICE pointers: boards int8 [n][8][8][112] and meta int32 [n][7] as layout 0 of sc_encode_steps_device

@@ -1,4 +1,4 @@
-// encode_steps.hip -- host side of libsc_engine.so: training tensors (sc_encode_steps, sc_encode_steps_device).
+// encode_steps.hip -- host side of libsc_engine.so: training tensors (sc_encode_steps, sc_encode_steps_device, sc_encode_san_device).
 //
 // libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) for a batch of recorded games; see include/sc_engine.h.
 // One encoder, encode_device_core, writes device buffers on a stream.  sc_encode_steps_device / sc_selfplay_encode_traces hand
@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "host_common.hpp"
+#include "san_tokens.hpp"
 
 static thread_local float g_encode_ms[2] = {0.f, 0.f};   // last sc_encode_steps of this thread: kernels (HIP events), whole call
 
@@ -60,10 +61,12 @@ int check_device_outputs(const DevEncodeOut& o, int dev) {
 
 // ply_off: host, n_games + 1 (the plies of game g are [ply_off[g], ply_off[g+1])).  Host path: moves / child_mv / child_n /
 // child_off are host arrays as sc_encode_steps takes them; ring path (ring != nullptr): the moves and children are read from the
-// trace ring rows on the device.
+// trace ring rows on the device; SAN path (san != nullptr): the moves are parsed on the device from the host's tokens (k_san_parse
+// also writes the games' status), every ply's children are its legal moves with count 1 on the move played, and the parsed moves
+// stay in the arena between the two halves: nothing comes back to the host.
 int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
                        const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
-                       hipStream_t st) {
+                       hipStream_t st, const SanSrc* san) {
     const uint32_t P = ply_off[n_games];
     // the game records of one group of games: (games in the group) x (longest game of the group + 2) <= REC_BUDGET, so one long
     // game among many short ones does not size the buffer for all of them (80 B per record: 80 MiB)
@@ -87,11 +90,12 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
         max_rec = std::max(max_rec, (size_t)(g1 - g0) * (mx + 2));
         g0 = g1;
     }
-    const bool has_ring = ring != nullptr;
-    const uint32_t nchild = has_ring ? 0 : child_off[P];
+    const bool has_ring = ring != nullptr, has_csr = !ring && !san;
+    const uint32_t nchild = has_csr ? child_off[P] : 0;
     const uint32_t cap = std::max<uint32_t>(std::min(CH, P), 1);
     uint32_t *d_off, *d_hoff, *d_plen, *d_pgame, *d_src, *d_coff, *d_cn;
     uint16_t *d_moves, *d_lm, *d_cmv;
+    uint64_t* d_tok;
     sc::Position* d_hist;
     int32_t *d_meta, *d_nl, *d_rows;
     ArenaLayout L;
@@ -106,9 +110,10 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
     L.add(&d_nl, (size_t)cap);
     L.add(&d_rows, (size_t)n_games, has_ring);
     L.add(&d_src, (size_t)P, has_ring);
-    L.add(&d_coff, (size_t)P + 1, !has_ring);
-    L.add(&d_cmv, (size_t)nchild, !has_ring);
-    L.add(&d_cn, (size_t)nchild, !has_ring);
+    L.add(&d_coff, (size_t)P + 1, has_csr);
+    L.add(&d_cmv, (size_t)nchild, has_csr);
+    L.add(&d_cn, (size_t)nchild, has_csr);
+    L.add(&d_tok, (size_t)P, san != nullptr);
     std::lock_guard<std::mutex> lk(g_enc_mu);
     EncArena& A = g_enc_arena[dev];
     if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
@@ -125,6 +130,10 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
     HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
     if (ring) {
         HIPOK(hipMemcpyAsync(d_rows, ring->rows, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
+    } else if (san) {
+        if (P) HIPOK(hipMemcpyAsync(d_tok, san->tokens, (size_t)P * 8, hipMemcpyHostToDevice, st));
+        scl::san_parse(n_games, d_tok, d_off, d_moves, o.status, st);
+        if (P && san->moves_out) HIPOK(hipMemcpyAsync(san->moves_out, d_moves, (size_t)P * 2, hipMemcpyDeviceToDevice, st));
     } else {
         if (P) HIPOK(hipMemcpyAsync(d_moves, moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
         HIPOK(hipMemcpyAsync(d_coff, child_off, ((size_t)P + 1) * 4, hipMemcpyHostToDevice, st));
@@ -133,11 +142,13 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
             HIPOK(hipMemcpyAsync(d_cn, child_n, (size_t)nchild * 4, hipMemcpyHostToDevice, st));
         }
     }
-    HIPOK(hipMemsetAsync(o.status, 0x7f, (size_t)n_games * 4, st));   // sc::STATUS_NONE: no failing ply yet
+    if (!san) HIPOK(hipMemsetAsync(o.status, 0x7f, (size_t)n_games * 4, st));   // sc::STATUS_NONE: no failing ply yet
     const size_t bsz = o.layout == 1 ? 4 : 1, msz = 4;
+    const bool rows_wanted = o.boards || o.meta || o.dist || o.dist_legal || o.legal_idx || o.n_legal;
     for (const Group& gr : groups) {
         const uint32_t p0 = ply_off[gr.g0], p1 = ply_off[gr.g0 + gr.ng];
         if (p1 == p0) continue;
+        if (san && !rows_wanted) break;   // SAN -> moves alone
         scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, d_rows, ring ? ring->p->num_steps : 0,
                        ring ? ring->p->t_move : nullptr, d_moves, d_src, st);
         scl::replay_games(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st);
@@ -146,6 +157,12 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
             scl::encode_plies(o.layout, (int)n, d_hist, d_hoff + c0, d_plen + c0,
                               o.boards ? static_cast<char*>(o.boards) + (size_t)c0 * 7168 * bsz : nullptr, d_meta, d_lm,
                               o.legal_idx ? o.legal_idx + (size_t)c0 * 224 : nullptr, d_nl, st);
+            if (san) {
+                scl::san_dist((int)n, d_lm, d_nl, d_moves + c0, apply_mirror, d_meta, o.layout,
+                              o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr, o.dist ? o.dist + (size_t)c0 * 4672 : nullptr,
+                              o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr, o.n_legal ? o.n_legal + c0 : nullptr, st);
+                continue;
+            }
             scl::steps_dist((int)n, d_lm, d_nl, d_moves + c0, ring ? ring->p->t_cmove : d_cmv,
                             ring ? reinterpret_cast<const uint32_t*>(ring->p->t_cn) : d_cn, ring ? nullptr : d_coff + c0,
                             ring ? d_src + c0 : nullptr, ring ? ring->p->t_nchild : nullptr, d_pgame + c0, d_plen + c0, apply_mirror,
@@ -154,12 +171,12 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
                             o.n_legal ? o.n_legal + c0 : nullptr, o.status, st);
         }
     }
-    scl::status_final(n_games, o.status, st);
+    if (!san) scl::status_final(n_games, o.status, st);
     HIPOK(hipGetLastError());
     return 0;
 }
 
-// the host trace arrays of sc_encode_steps / sc_encode_steps_device
+// the host trace arrays of sc_encode_steps / sc_encode_steps_device (child_off == nullptr: the offsets of sc_encode_san_device)
 static int check_traces(int n_games, const uint32_t* move_off, const uint32_t* child_off) {
     uint32_t maxlen = 0;
     for (int g = 0; g < n_games; g++) {
@@ -167,7 +184,7 @@ static int check_traces(int n_games, const uint32_t* move_off, const uint32_t* c
         maxlen = std::max(maxlen, move_off[g + 1] - move_off[g]);
     }
     if (maxlen > 4000) return fail("move list too long");
-    for (uint32_t p = 0; p < move_off[n_games]; p++)
+    for (uint32_t p = 0; child_off && p < move_off[n_games]; p++)
         if (child_off[p + 1] < child_off[p] || child_off[p + 1] - child_off[p] > 224) return fail("child_off: more than 224 children or not monotonic");
     return 0;
 }
@@ -190,6 +207,31 @@ int sc_encode_steps_device(sc_engine* e, int device_id, int n_games, const uint1
     if (child_off[total] && (!child_mv || !child_n)) return fail("bad argument");
     return encode_device_core(dev, n_games, move_off, moves, child_mv, child_n, child_off, nullptr, apply_mirror, o,
                               static_cast<hipStream_t>(stream));
+}
+
+int sc_encode_san_device(sc_engine* e, int device_id, int n_games, const uint64_t* tokens, const uint32_t* tok_off, int apply_mirror,
+                         int layout, void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
+                         int32_t* n_legal, uint16_t* moves, int32_t* status) {
+    if (n_games < 0 || !tok_off || !status) return fail("bad argument");
+    TRY(use_device(e, device_id));
+    const int dev = e ? e->device : device_id;
+    const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
+    TRY(check_device_outputs(o, dev));
+    TRY(check_device_ptrs({{moves, "moves"}}, dev));
+    if (n_games == 0) return 0;
+    TRY(check_traces(n_games, tok_off, nullptr));
+    if (tok_off[n_games] && !tokens) return fail("bad argument");
+    const SanSrc san{tokens, moves};
+    return encode_device_core(dev, n_games, tok_off, nullptr, nullptr, nullptr, nullptr, nullptr, apply_mirror, o,
+                              static_cast<hipStream_t>(stream), &san);
+}
+
+int sc_san_tokenize(const char* text, size_t len, uint64_t* tokens, uint32_t cap, uint32_t* n_tokens) {
+    if ((!text && len) || (!tokens && cap) || !n_tokens) return fail("bad argument");
+    const size_t n = scsan::san_tokenize(text, len, tokens, cap);
+    *n_tokens = (uint32_t)std::min<size_t>(n, UINT32_MAX);
+    if (n > cap) return fail("sc_san_tokenize: " + std::to_string(n) + " tokens, room for " + std::to_string(cap), SC_ERR_CAPACITY);
+    return 0;
 }
 
 namespace {

@@ -175,12 +175,17 @@ struct RingSrc {
     const int32_t* rows;   // host: ring row of each requested game
     const sc::SpParams* p;
 };
+// SAN tokens as the encoder's source (sc_encode_san_device): parsed on the device into the call's move list
+struct SanSrc {
+    const uint64_t* tokens;   // host: one per ply
+    uint16_t* moves_out;      // device [P] or null: a copy of the parsed moves
+};
 // pointers the kernels of a call read or write must be device memory of `dev`; null entries are skipped
 int check_device_ptrs(std::initializer_list<std::pair<const void*, const char*>> ptrs, int dev);
 int check_device_outputs(const DevEncodeOut& o, int dev);
 int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
                        const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
-                       hipStream_t st);
+                       hipStream_t st, const SanSrc* san = nullptr);
 
 // ------------------------------------------------------------------ self-play (selfplay.hip, selfplay_io.hip)
 struct sc_selfplay {

@@ -40,6 +40,11 @@ void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const
                 const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
                 float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s);
 void status_final(int n, int32_t* status, hipStream_t s);
+// san_kernels.hip: SAN tokens -> moves and the parser's status per game (sc_encode_san_device), and steps_dist for rows whose
+// children are the legal moves with count 1 on the played move
+void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status, hipStream_t s);
+void san_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, int apply_mirror, const int32_t* meta_s,
+              int layout, void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out, hipStream_t s);
 // nn_kernels.hip
 const char* nn_init();  // sets kernel attributes; returns error text or nullptr
 size_t tower_lds_bytes(int C);

@@ -16,6 +16,9 @@ reference's usage:
   gather_batch_torch,            <->  DataLoader(ConcatDataset([ChessDataset ...]), shuffle=True, drop_last=True) + _prepare
   ReplayBuffer                        (scripts/train.py:331-353): shuffled trainer-layout minibatches from the compact tensors
 
+  scamd.san (not re-exported)    <->  ValidationDataset (py/dataset.py:90-128): games as SAN movetext (sample.csv, PGN) -> moves and
+                                      training tensors, resolved against the legal moves on the GPU
+
 There is NO CPU fallback: importing works anywhere (so the C ABI can be checked), but every
 compute entry point raises EngineError when the HIP library or a GPU is missing.
 """

@@ -99,6 +99,8 @@ ABI = {
     "sc_encode_steps_last_timing": (_i, [C.POINTER(_f), C.POINTER(_f)]),
     "sc_encode_steps": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_encode_steps_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_san_tokenize": (_i, [C.c_char_p, C.c_size_t, _vp, C.c_uint32, _vp]),
+    "sc_encode_san_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_selfplay_encode_traces": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_forward_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sc_score_positions": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,133 @@
+"""Games written as SAN movetext (PGN files, the reference's py/validation/sample.csv) -> moves and training tensors on the GPU
+(csrc/san_tokens.cpp, csrc/san_kernels.hip, sc_encode_san_device): the reference's ValidationDataset (py/dataset.py:90-128)
+without python-chess.  The rules exist on the GPU only, so SAN is resolved there, against the generated legal moves."""
+import csv
+import ctypes as C
+import re
+
+import numpy as np
+
+from .binding import _check, _p, _stream, _torch, _tp, lib
+from .training import _device_outputs, _finish_outputs
+
+TOKEN_RESERVED = np.uint64(0xFFFFFFFFFFFFFFFF)
+ERR_CAPACITY = -4   # SC_ERR_CAPACITY
+_WINNER = {"white": 1.0, "black": -1.0, "draw": 0.0, None: 0.0, "": 0.0}
+_RESULT = {"1-0": "white", "0-1": "black", "1/2-1/2": "draw"}
+
+
+def tokenize(text):
+    """One game's movetext -> uint64 array, one token per half-move (sc_san_tokenize; no GPU needed): the SAN characters,
+    first character in the lowest byte, without check / annotation suffixes; 0xFFFFFFFFFFFFFFFF where a half-move does not fit."""
+    L = lib()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    n = C.c_uint32(0)
+    out = np.zeros(len(raw) // 3 + 8, np.uint64)
+    rc = L.sc_san_tokenize(raw, len(raw), _p(out), out.size, C.byref(n))
+    if rc == ERR_CAPACITY:
+        out = np.zeros(n.value, np.uint64)
+        rc = L.sc_san_tokenize(raw, len(raw), _p(out), out.size, C.byref(n))
+    _check(rc)
+    return out[:n.value].copy()
+
+
+def token_text(tok):
+    """the characters of a token (for messages)"""
+    return "<reserved>" if int(tok) == int(TOKEN_RESERVED) else int(tok).to_bytes(8, "little").rstrip(b"\0").decode("latin-1")
+
+
+def pack_tokens(games):
+    """games: movetext strings or token arrays -> (tokens uint64 [P], tok_off uint32 [n + 1])"""
+    toks = [tokenize(g) if isinstance(g, (str, bytes)) else np.ascontiguousarray(g, np.uint64) for g in games]
+    off = np.zeros(len(toks) + 1, np.uint32)
+    off[1:] = np.cumsum([t.size for t in toks])
+    flat = np.concatenate(toks) if toks and off[-1] else np.zeros(0, np.uint64)
+    return flat, off
+
+
+def encode_san_torch(games, winners=None, *, device, layout="reference", dist="legal", apply_mirror=False, engine=None):
+    """SAN games -> training tensors on the GPU in one call (sc_encode_san_device): every ply a row, dist one-hot on the move
+    played (1 / (1 + 1e-5) there, as chess_encode_steps makes of a count of 1).
+    games: movetext strings (tokenize) or token arrays, or the pair pack_tokens returns; winners: per game "white" / "black" /
+    "draw" / None (read_games_csv's and read_pgn's second column).
+    -> the dict encode_steps_torch returns (boards, meta, dist, dist_legal, legal_idx, n_legal, ply_off, status; layout and dist
+    as there; outcome float32 [P] is White's result of the ply's game from winners, 0 without, negated under apply_mirror as
+    everywhere) plus moves (torch int16 [P]: the move encoding, which stays below 2^15).  status: 0; -(i+1): token i names no legal move;
+    100000 + i: it is ambiguous; 200000 + i: it is malformed.  score_torch, compare_torch, gather_batch_torch and
+    ReplayBuffer.add take the dict as it is."""
+    torch = _torch()
+    L = lib()
+    if isinstance(games, tuple) and len(games) == 2 and all(isinstance(a, np.ndarray) for a in games):
+        flat, off = np.ascontiguousarray(games[0], np.uint64), np.ascontiguousarray(games[1], np.uint32)
+    else:
+        flat, off = pack_tokens(games)
+    n = off.size - 1
+    P = int(off[n])
+    if winners is not None and len(winners) != n:
+        raise ValueError(f"{len(winners)} winners for {n} games")
+    dev = engine.device if engine is not None else device
+    out, args = _device_outputs(torch, dev, P, n, layout, dist)
+    moves = torch.empty(max(P, 1), dtype=torch.int16, device=torch.device("cuda", dev))
+    _check(L.sc_encode_san_device(engine.h if engine else None, dev, n, _p(flat if flat.size else np.zeros(1, np.uint64)), _p(off),
+                                  int(bool(apply_mirror)), args[0], _stream(torch, dev), *args[1:-1], _tp(moves), args[-1]))
+    oc = np.zeros(n, np.float32) if winners is None else np.asarray([_WINNER[w.lower() if isinstance(w, str) else w] for w in winners], np.float32)
+    res = _finish_outputs(torch, out, off, oc, apply_mirror, dev)
+    res["moves"] = moves[:P]
+    return res
+
+
+def read_games_csv(path, limit=None):
+    """The `moves` and `winner` columns of a game table like the reference's py/validation/sample.csv (its own use: limit=10)
+    -> (list of movetext strings, list of winners)"""
+    games, winners = [], []
+    with open(path, newline="") as f:
+        for row in csv.DictReader(f):
+            if limit is not None and len(games) >= limit:
+                break
+            games.append(row["moves"])
+            winners.append(row["winner"])
+    return games, winners
+
+
+_TAG = re.compile(r'^\s*\[\s*(\w+)\s+"((?:[^"\\]|\\.)*)"\s*\]\s*$')
+
+
+def read_pgn(path):
+    """A PGN file -> (list of movetext strings, list of winners from [Result]): parse_pgn of its text"""
+    with open(path, encoding="utf-8", errors="replace") as f:
+        return parse_pgn(f.read())
+
+
+def parse_pgn(src):
+    """PGN text -> (list of movetext strings, list of winners from [Result]).  A game is a block of header tags and the movetext
+    behind it; movetext without headers is a game too.  This library plays from the start position only: a game with a [FEN] or
+    a [SetUp "1"] header raises ValueError, which names the game."""
+    games, winners = [], []
+    tags, body = {}, []
+
+    def close():
+        mt = "\n".join(body).strip()
+        if mt or tags:
+            k = len(games) + 1
+            name = f"game {k} ({tags.get('White', '?')} - {tags.get('Black', '?')})"
+            if "FEN" in tags or tags.get("SetUp") == "1":
+                raise ValueError(f"{name}: starts from a set-up position ([FEN] / [SetUp \"1\"]); only games from the start position can be read")
+            games.append(mt)
+            winners.append(_RESULT.get(tags.get("Result")))
+
+    for ln in src.splitlines():
+        m = _TAG.match(ln)
+        if m and not (body and _open_comment("\n".join(body))):
+            if body:   # a header block after movetext: the next game
+                close()
+                tags, body = {}, []
+            tags[m.group(1)] = m.group(2)
+        elif ln.strip() or body:
+            body.append(ln)
+    close()
+    return games, winners
+
+
+def _open_comment(movetext):
+    """is a {...} comment still open at the end of this movetext? (a tag-like line inside a comment is comment text)"""
+    return movetext.rfind("{") > movetext.rfind("}")

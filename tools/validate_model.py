@@ -3,9 +3,13 @@ reference's scripts/validate_model.py, on the GPU engine (sc_compare_engines): d
 network may replace the one it came from.
 
     python tools/validate_model.py -t TRACE.json [TRACE.json ...] --model1 [N_RES_BLOCKS:]A.scw --model2 [N_RES_BLOCKS:]B.scw
+                                   [--games-csv GAMES.csv [--limit N]] [--pgn GAMES.pgn]
                                    [--precision1 {bf16,fp8}] [--precision2 {bf16,fp8}] [--losses] [--device N]
 
-TRACE.json: the trace files this library writes (SelfPlay.write_trace / lib/sc-selfplay; the reference's format).  Models are
+TRACE.json: the trace files this library writes (SelfPlay.write_trace / lib/sc-selfplay; the reference's format).  --games-csv: a
+game table with `moves` (SAN movetext) and `winner` columns, as the reference's py/validation/sample.csv (its ValidationDataset
+reads the first 10 rows: --limit 10); --pgn: a PGN file of games from the start position.  Those games are read on the GPU
+(scamd.san.encode_san_torch): every ply a position, the visit shares one-hot on the move played.  The sources add up.  Models are
 .scw blobs (tools/scw.py, tools/ckpt_to_scw.py); an SCW2 blob carries its own precision.  Prints the policy difference (total
 variation per position) and the value difference as mean / std / max / min, and with --losses the validation losses of each
 model on the traces' visit shares and outcomes (train.py's val_*_loss1 / val_*_loss2).  torch must be importable: the
@@ -21,6 +25,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("-t", "--trace", type=str, nargs="+", action="extend")
+    ap.add_argument("--games-csv", type=str, help="game table with `moves` (SAN) and `winner` columns")
+    ap.add_argument("--limit", type=int, default=None, help="read only the first N rows of --games-csv")
+    ap.add_argument("--pgn", type=str, help="PGN file (games from the start position)")
     ap.add_argument("--model1", required=True, type=str, help="[n_res_blocks:]path of an .scw blob")
     ap.add_argument("--model2", required=True, type=str)
     prec_help = "precision an SCW1 (fp32) blob is run in; ignored for an SCW2 blob, which is the fp8 export and says so itself"
@@ -51,10 +58,10 @@ def load_trace(path):
 
 def main(argv=None):
     args = parser().parse_args(argv)
-    if not args.trace:
+    if not args.trace and not args.games_csv and not args.pgn:
         print("No trace file specified.")
         return 0
-    import torch  # noqa: F401  (first: libsc_engine.so then binds to the HIP runtime torch loaded)
+    import torch  # (first: libsc_engine.so then binds to the HIP runtime torch loaded)
     sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
     import scamd
 
@@ -62,15 +69,32 @@ def main(argv=None):
     for nb, path in specs:   # before any engine exists
         if nb is not None and nb != eng_blocks(path):
             raise SystemExit(f"{path}: the blob holds {eng_blocks(path)} residual blocks, the model spec says {nb}")
-    games, wins = zip(*(load_trace(p) for p in args.trace))
+    import scamd.san
+    san_games, san_winners = [], []
+    if args.games_csv:
+        san_games, san_winners = scamd.san.read_games_csv(args.games_csv, args.limit)
+    if args.pgn:
+        g, w = scamd.san.read_pgn(args.pgn)
+        san_games, san_winners = san_games + g, san_winners + w
     engines = []
     try:
         for (nb, path), prec in zip(specs, (args.precision1, args.precision2)):
             engines.append(scamd.Engine(weights=path, device=args.device, precision=prec))
-        t = scamd.encode_steps_torch(list(games), layout="reference", dist="legal", engine=engines[0], outcomes=list(wins))
-        if (t["status"] != 0).any():
-            bad = [(args.trace[g], int(s)) for g, s in enumerate(t["status"]) if s]
-            raise SystemExit(f"traces that do not replay (sc_encode_steps status codes): {bad}")
+        parts = []
+        if args.trace:
+            games, wins = zip(*(load_trace(p) for p in args.trace))
+            t = scamd.encode_steps_torch(list(games), layout="reference", dist="legal", engine=engines[0], outcomes=list(wins))
+            if (t["status"] != 0).any():
+                bad = [(args.trace[g], int(s)) for g, s in enumerate(t["status"]) if s]
+                raise SystemExit(f"traces that do not replay (sc_encode_steps status codes): {bad}")
+            parts.append(t)
+        if san_games:
+            t = scamd.san.encode_san_torch(san_games, san_winners, device=args.device, engine=engines[0])
+            if (t["status"] != 0).any():
+                bad = [(g + 1, int(s)) for g, s in enumerate(t["status"]) if s]
+                raise SystemExit(f"games that do not parse (game number, sc_encode_san_device status code): {bad}")
+            parts.append(t)
+        t = parts[0] if len(parts) == 1 else {k: torch.cat([q[k] for q in parts]) for k in ("boards", "meta", "dist_legal", "legal_idx", "n_legal", "outcome")}
         print("Running inference...")
         r = scamd.compare_torch(engines[0], engines[1], t)
         print("policy difference:", {k: r["tv_" + k] for k in ("mean", "std", "max", "min")})
