@@ -108,7 +108,8 @@ int sc_engine_synchronize(sc_engine*);
 int sc_forward_debug(sc_engine*, int n, const int8_t* boards, const int32_t* meta, int stage, float* out);
 
 /* Rules + encoder on the GPU: replaces python-chess (src/chess.rs:665-803) and _encode
- * (src/chess.rs:845-877) for positions given as move lists from the start position.
+ * (src/chess.rs:845-877) for positions given as move lists from the start position (from any position:
+ * sc_encode_positions_from).
  * For position i (moves[move_off[i]..move_off[i+1])):
  *   boards[i], meta[i]                      the NN input
  *   legal_moves[i][..], legal_idx[i][..]    legal moves in python-chess generation order and their
@@ -208,6 +209,79 @@ int sc_san_tokenize(const char* text, size_t len, uint64_t* tokens, uint32_t cap
 int sc_encode_san_device(sc_engine* engine_or_null, int device_id, int n_games, const uint64_t* tokens, const uint32_t* tok_off,
                          int apply_mirror, int layout, void* stream, void* boards, void* meta, float* dist, float* dist_legal,
                          uint16_t* legal_idx, int32_t* n_legal, uint16_t* moves, int32_t* status);
+
+/* ------------------------------------------------------------------ positions given as FEN / EPD: a base for every entry point */
+/* FEN or EPD text -> the raw fields of a position, on the host (no GPU is needed, the rules code is not called).  Every read is
+ * bounded by `len`; the text need not be zero-terminated.  Fields are separated by runs of white space.  Grammar: python-chess's
+ * Board.set_fen for standard chess --
+ *   1 board     eight ranks separated by '/', each of digits 1-8 and letters of pnbrqkPNBRQK that sum to 8, no two digits in a row
+ *   2 turn      w | b
+ *   3 castling  - | up to two of KQ, then up to two of kq, no letter twice (Shredder / X-FEN file letters: refused, no Chess960)
+ *   4 ep        - | [a-h][36]
+ *   5, 6 clocks present when the fifth AND the sixth word are integers (-?[0-9]+): halfmove 0..65535, fullmove 0..65535 with 0 read
+ *               as 1.  Anything else behind the fourth field -- EPD operations such as "bm Qh5;" -- is ignored: halfmove 0, fullmove 1.
+ * Returns 0, or -(number of the failing field, 1..6) with *out zeroed; a missing field fails as that field (an empty text: -1).
+ * castling: bit 0 K, 1 Q, 2 k, 3 q as written (not yet checked against the board); ep: the square as written (a1 = 0) or -1;
+ * occ[1] White's men, occ[0] Black's; pcs by piece type p n b r q k.  Whether the position can be played is decided on the device
+ * (sc_positions_from_fen). */
+struct sc_fen_fields {
+    uint64_t pcs[6];
+    uint64_t occ[2];
+    int32_t turn;      /* 1 White, 0 Black */
+    int32_t castling;
+    int32_t ep;
+    int32_t halfmove;
+    int32_t fullmove;
+    int32_t reserved;
+};
+typedef struct sc_fen_fields sc_fen_fields;
+int sc_fen_parse(const char* text, size_t len, sc_fen_fields* out);
+
+/* A set of n positions in device memory, validated there: the base of a move list wherever an entry point ends in _from.
+ * fens[i]: zero-terminated FEN / EPD text, or NULL for the start position.  One wavefront per position writes its record in the
+ * form the library keeps everywhere: castling rights cleaned (king and rook on their squares), the ep square kept only if
+ * python-chess's _valid_ep_square holds (the right rank for the side to move, an enemy pawn in front of it, the square and the
+ * one behind it empty; otherwise dropped, which is no error), the transposition key, no flags.  Status of position i:
+ *      0  playable
+ *      1  the game is already over here: no legal move, or outcome(claim_draw=True) is set (insufficient material, halfmove >= 100 ...)
+ *     -1  not exactly one king per side
+ *     -2  a pawn on rank 1 or 8
+ *     -3  the side that is NOT to move is in check
+ *     -4  material no game can reach: more than 16 men or 8 pawns of a colour, or more promoted pieces than missing pawns
+ *     -5  more than two checkers
+ *     -6  the fields contradict each other (a square with two pieces, or a piece without a colour): sc_fen_parse never writes such
+ *   -(100 + f)  sc_fen_parse refused field f
+ * The checks run in that order, before the move generator sees the position; the first failing one wins, the other positions of
+ * the call are not affected, and the call still returns the set (0), so that a suite reader can report every bad line at once.
+ * The record of a refused position is the start position's; no consumer reads it.  status (host, may be NULL) int32 [n].
+ * Consumers refuse (-1, sc_last_error) an entry whose status is negative, and one whose status is 1 wherever a search would
+ * start from it.  sc_positions_fen: python-chess's Board.fen() of entry i -- the ep square is printed only if a legal en-passant
+ * capture exists, found on the device when the set was made -- returns the length, writes at most cap bytes with the final zero;
+ * < 0 for an entry whose status is negative.  Returns < 0 as every entry point (-3: no HIP device). */
+typedef struct sc_positions sc_positions;
+int sc_positions_from_fen(int device_id, int n, const char* const* fens, sc_positions** out, int32_t* status);
+void sc_positions_destroy(sc_positions*);
+int sc_positions_count(const sc_positions*);
+int sc_positions_status(const sc_positions*, int i);
+int sc_positions_fen(const sc_positions*, int i, char* buf, int cap);
+
+/* sc_encode_positions with a base per position: position i is bases[base_idx[i]] followed by its moves; base_idx[i] < 0, or
+ * base_idx == NULL, or bases == NULL: the start position, and the outputs are those of sc_encode_positions.  History planes
+ * older than the base are zero; repetitions and the fifty-move count start at the base (its halfmove clock counts).  A base whose
+ * status is 1 is encoded like any other (its outcome says why the game is over). */
+int sc_encode_positions_from(sc_engine* engine_or_null, int device_id, int n, const sc_positions* bases, const int32_t* base_idx,
+                             const uint16_t* moves, const uint32_t* move_off, int8_t* boards, int32_t* meta, uint16_t* legal_moves,
+                             uint16_t* legal_idx, int32_t* n_legal, int32_t* outcome);
+/* sc_encode_steps_device / sc_encode_san_device with a base per game (base_idx host int32 [n_games], as above): the plies of game g
+ * start at its base.  The set must live on the call's device and stay alive until the stream's work is done. */
+int sc_encode_steps_device_from(sc_engine* engine_or_null, int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx,
+                                const uint16_t* moves, const uint32_t* move_off, const uint16_t* child_mv, const uint32_t* child_n,
+                                const uint32_t* child_off, int apply_mirror, int layout, void* stream, void* boards, void* meta,
+                                float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, int32_t* status);
+int sc_encode_san_device_from(sc_engine* engine_or_null, int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx,
+                              const uint64_t* tokens, const uint32_t* tok_off, int apply_mirror, int layout, void* stream, void* boards,
+                              void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, uint16_t* moves,
+                              int32_t* status);
 
 /* ------------------------------------------------------------------ network on device tensors: forward, losses, agreement */
 /* sc_forward_batch on DEVICE pointers: boards int8 [n][8][8][112] and meta int32 [n][7] as layout 0 of sc_encode_steps_device
@@ -401,6 +475,23 @@ int sc_selfplay_match_tally(sc_selfplay*, int64_t out[8]);
 int sc_selfplay_set_openings(sc_selfplay*, int n_lines, const uint16_t* moves, const uint32_t* move_off, int32_t* status);
 /* the line of handle-local game `game` (pure function of the table and the rule above): returns its length, writes up to cap moves */
 int sc_selfplay_get_opening(sc_selfplay*, int game, uint16_t* moves, int cap);
+/* Opening lines that start from bases: line i is entry base_idx[i] of `bases` (base_idx[i] < 0: the start position) followed by
+ * its 0..600 moves; base_idx host int32 [n_lines].  bases == NULL or base_idx == NULL: sc_selfplay_set_openings.  Whether a base
+ * can be played was decided when the set was made (an entry whose status is not 0 is refused: -1, the handle is as before, and
+ * status[i] carries the entry's status); the moves are checked as there.
+ * Start rule: the first searched ply belongs to the side to move of the line's last position -- for a line from the start
+ * position that is player white(k) ^ (L & 1), for a base with Black to move and no moves it is Black's player.  The tally stays
+ * by White's player, the trace holds the searched plies only, and num_steps, temperature_switch and outcome_gate count from the
+ * first searched ply.  The game's chain holds one or two empty records in front of a base where the start rule needs them (they
+ * encode as zero planes, and no repetition scan passes the base): the slot's ply is the chain index of its position, not a move
+ * count.
+ * sc_selfplay_get_opening_fen: the base of the line of handle-local game `game` as sc_positions_fen prints it; returns its
+ * length, 0 (and an empty text) for a line from the start position.
+ * sc_selfplay_write_trace_json writes such a game's base as "fen": "..." behind "steps" and in front of "opening";
+ * sc_selfplay_encode_traces refuses the game, as it refuses every game that did not start from the start position. */
+int sc_selfplay_set_openings_from(sc_selfplay*, int n_lines, const sc_positions* bases, const int32_t* base_idx, const uint16_t* moves,
+                                  const uint32_t* move_off, int32_t* status);
+int sc_selfplay_get_opening_fen(sc_selfplay*, int game, char* buf, int cap);
 int sc_selfplay_timing(sc_selfplay*, int reset, float* ms_total, float* ms_nn, int64_t* nn_launches);
 /* Kernel launches per simulation step this handle uses with SC_EVAL_NET (steps bracketed for sc_selfplay_timing always use 3):
  * 1 = the fused step kernel with value_head.ffn.0 inside (whole 64-slot blocks, every workgroup resident, and no other
@@ -454,7 +545,8 @@ int sc_selfplay_get_slot(sc_selfplay*, int slot, int32_t* ply, int32_t* sim, int
 /* replace the root noise used by the NEXT simulation of `slot` (external_noise mode); noise[n] */
 int sc_selfplay_set_noise(sc_selfplay*, int slot, const float* noise, int n);
 int sc_selfplay_get_noise(sc_selfplay*, int slot, float* noise, int cap);
-/* start slot from a given move list instead of the initial position (sc_search / chess_play_new, src/lib.rs:161-232) */
+/* start slot from a given move list instead of the initial position (sc_search / chess_play_new, src/lib.rs:161-232); from a
+ * position given as FEN: sc_selfplay_set_position_from */
 int sc_selfplay_set_position(sc_selfplay*, int slot, const uint16_t* moves, int n_moves);
 /* per-call search options of chess_play_mcts(state, rollout, cpuct, noise) (src/lib.rs:233-247): applies to the
  * simulations enqueued after the call */
@@ -469,6 +561,21 @@ int sc_selfplay_set_search(sc_selfplay*, float cpuct, float epsilon, int with_no
  * sc_selfplay_enqueue_sims + sc_selfplay_get_tree). */
 int sc_search(sc_engine*, const uint16_t* moves, int n_moves, int rollout, float cpuct, int with_noise, uint64_t seed, int cap,
               uint16_t* child_move, int32_t* child_n, float* child_q, float* child_prior, float* root_q);
+
+/* The same from a base (sc_positions_from_fen): entry i of `bases` followed by `moves`.  bases == NULL: the start position, and
+ * the call is its sibling without _from.  An entry whose status is not 0 is refused (-1): nothing can be searched from a position
+ * that cannot be played or where the game is over.
+ * sc_selfplay_set_position_from: hist[0] of the slot is the base; the slot's ply and start ply stay counts of the moves AFTER the
+ * base, history planes older than the base are zero, repetitions and the fifty-move count start at the base.  The moves are not
+ * checked, as with sc_selfplay_set_position (sc_encode_positions_from reports an illegal one).
+ * sc_selfplay_get_fen: python-chess's Board.fen() of the slot's current position (the root of its tree), whatever the slot
+ * started from; the ep square is printed only if a legal en-passant capture exists, which a lane of a small kernel decides.
+ * Returns the length, writes at most cap bytes with the final zero. */
+int sc_selfplay_set_position_from(sc_selfplay*, int slot, const sc_positions* bases, int i, const uint16_t* moves, int n_moves);
+int sc_search_from(sc_engine*, const sc_positions* bases, int i, const uint16_t* moves, int n_moves, int rollout, float cpuct,
+                   int with_noise, uint64_t seed, int cap, uint16_t* child_move, int32_t* child_n, float* child_q, float* child_prior,
+                   float* root_q);
+int sc_selfplay_get_fen(sc_selfplay*, int slot, char* buf, int cap);
 
 /* test aid: find_max (src/mcts.rs:78-88, Iterator::max_by: the LAST maximum wins) as the descent computes it, on n <= 256
  * caller-provided finite values: out[0] = the one-round form used for nodes with <= 64 children (-2 if n > 64),

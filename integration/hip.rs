@@ -90,6 +90,10 @@ pub struct ScEngine {
 pub struct ScSelfplay {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct ScPositions {
+    _p: [u8; 0],
+}
 
 extern "C" {
     fn sc_last_error() -> *const c_char;
@@ -128,6 +132,20 @@ extern "C" {
     fn sc_search(e: *mut ScEngine, moves: *const u16, n_moves: c_int, rollout: c_int, cpuct: f32, with_noise: c_int, seed: u64,
                  cap: c_int, child_move: *mut u16, child_n: *mut i32, child_q: *mut f32, child_prior: *mut f32,
                  root_q: *mut f32) -> c_int;
+    // positions given as FEN (BoardState::from_fen, src/chess.rs:680; play.rs:105): a validated set on the GPU, then the base of a
+    // move list for the encoder, a search or a match line
+    fn sc_positions_from_fen(device_id: c_int, n: c_int, fens: *const *const c_char, out: *mut *mut ScPositions, status: *mut i32) -> c_int;
+    fn sc_positions_destroy(ps: *mut ScPositions);
+    fn sc_positions_status(ps: *const ScPositions, i: c_int) -> c_int;
+    fn sc_positions_fen(ps: *const ScPositions, i: c_int, buf: *mut c_char, cap: c_int) -> c_int;
+    fn sc_encode_positions_from(e: *mut ScEngine, device_id: c_int, n: c_int, bases: *const ScPositions, base_idx: *const i32,
+                                moves: *const u16, move_off: *const u32, boards: *mut i8, meta: *mut i32, legal_moves: *mut u16,
+                                legal_idx: *mut u16, n_legal: *mut i32, outcome: *mut i32) -> c_int;
+    fn sc_search_from(e: *mut ScEngine, bases: *const ScPositions, i: c_int, moves: *const u16, n_moves: c_int, rollout: c_int,
+                      cpuct: f32, with_noise: c_int, seed: u64, cap: c_int, child_move: *mut u16, child_n: *mut i32,
+                      child_q: *mut f32, child_prior: *mut f32, root_q: *mut f32) -> c_int;
+    fn sc_selfplay_set_openings_from(sp: *mut ScSelfplay, n_lines: c_int, bases: *const ScPositions, base_idx: *const i32,
+                                     moves: *const u16, move_off: *const u32, status: *mut i32) -> c_int;
 }
 
 fn last_error() -> String {

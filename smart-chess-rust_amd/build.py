@@ -42,7 +42,7 @@ def build(force=False, verbose=False):
     for src, extra in (("mcts_kernels.hip", ["-ffp-contract=off"]), ("encode_kernels.hip", ["-ffp-contract=off"]),
                        ("nn_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
                        ("score_kernels.hip", ["-ffp-contract=off"]),
-                       ("batch_kernels.hip", []), ("san_kernels.hip", []), ("engine.hip", []), ("encode_steps.hip", []), ("device_calls.hip", []),
+                       ("batch_kernels.hip", []), ("san_kernels.hip", []), ("fen_kernels.hip", []), ("positions.hip", []), ("engine.hip", []), ("encode_steps.hip", []), ("device_calls.hip", []),
                        ("selfplay.hip", []), ("selfplay_io.hip", [])):
         s = os.path.join(CSRC, src)
         o = os.path.join(BUILD, src.replace(".hip", ".o"))
@@ -51,11 +51,12 @@ def build(force=False, verbose=False):
             if verbose and out.strip():
                 print(out)
         objs.append(o)
-    # the SAN tokenizer: plain C++ (no HIP in it), so that the same unit also builds into a stand-alone program
-    s, o = os.path.join(CSRC, "san_tokens.cpp"), os.path.join(BUILD, "san_tokens.o")
-    if force or _newer(o, [s] + hdrs):
-        _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-fvisibility=hidden", "-c", s, "-o", o])
-    objs.append(o)
+    # the SAN tokenizer and the FEN reader: plain C++ (no HIP in them), so that the same units also build into stand-alone programs
+    for name in ("san_tokens", "fen_text"):
+        s, o = os.path.join(CSRC, name + ".cpp"), os.path.join(BUILD, name + ".o")
+        if force or _newer(o, [s] + hdrs):
+            _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-fPIC", "-fvisibility=hidden", "-c", s, "-o", o])
+        objs.append(o)
     so = os.path.join(LIB, "libsc_engine.so")
     if force or _newer(so, objs):
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", so] + objs + ["-Wl,-rpath,/opt/rocm/lib"])

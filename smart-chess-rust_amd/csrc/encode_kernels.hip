@@ -6,15 +6,16 @@
 
 namespace sc {
 // ------------------------------------------------------------------ sc_encode_positions
-// One wave per position: replay the move list from the start position (validating every move
-// against the legal-move generator), then produce the NN input, the legal moves + action indices
+// One wave per position: replay the move list from the start position, or from record base_idx[g] of `bases` where that is
+// given (bases != nullptr and base_idx[g] >= 0: a validated record of fen_kernels.hip), validating every move
+// against the legal-move generator, then produce the NN input, the legal moves + action indices
 // and outcome(claim_draw=True).  hist scratch: [n][hist_cap] Positions.
 // move_len (optional): position g replays moves[move_off[g] .. move_off[g] + move_len[g]) -- prefixes of one game
 // share their start (used by the training-tensor encoder: one position per ply).
 __global__ __launch_bounds__(64) void k_encode_positions(int n_pos, const uint16_t* moves, const uint32_t* move_off,
                                                          const uint32_t* move_len, Position* hist_all, int hist_cap, int8_t* boards, int32_t* meta,
                                                          uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
-                                                         int32_t* outcome) {
+                                                         int32_t* outcome, const Position* bases, const int32_t* base_idx) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n_pos) return;
     __shared__ __attribute__((aligned(16))) int8_t s_stage[7168];
@@ -24,8 +25,13 @@ __global__ __launch_bounds__(64) void k_encode_positions(int n_pos, const uint16
     const uint16_t* mv = moves + move_off[g];
     int nm = move_len ? (int)move_len[g] : (int)(move_off[g + 1] - move_off[g]);
     Position cur;
-    set_startpos(cur);
-    cur.key = position_key(cur);
+    const int bi = bases ? uniform(base_idx[g]) : -1;
+    if (bi >= 0) {
+        cur = uniform(bases[bi]);   // (its key is set, its flags are clear)
+    } else {
+        set_startpos(cur);
+        cur.key = position_key(cur);
+    }
     if (lane == 0) hist[0] = cur;
     __syncthreads();
     int status = 0;
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(64) void k_encode_positions(int n_pos, const uint16
 // or on a non-pawn -- and leaves the position unchanged for those (the ply is then reported as illegal by the per-ply check,
 // and the game's later plies are unspecified, include/sc_engine.h).
 __global__ __launch_bounds__(64) void k_replay_raw(int n_games, const uint16_t* moves, const uint32_t* move_off, Position* hist_all,
-                                                   int hist_cap) {
+                                                   int hist_cap, const Position* bases, const int32_t* base_idx) {
     // the only sequential part: one wave per game, board updates only (make_move_board: ~10 % of what a full make_move + repetition
     // scan per ply cost when this kernel did everything -- 1.9 us per ply, 194 us for 100-ply games)
     const int g = blockIdx.x, lane = threadIdx.x;
@@ -98,7 +104,9 @@ __global__ __launch_bounds__(64) void k_replay_raw(int n_games, const uint16_t* 
     const uint16_t* mv = moves + move_off[g];
     const int nm = (int)(move_off[g + 1] - move_off[g]);
     Position cur;
-    set_startpos(cur);
+    const int bi = bases ? uniform(base_idx[g]) : -1;   // the game's base record (fen_kernels.hip), else the start position
+    if (bi >= 0) cur = uniform(bases[bi]);
+    else set_startpos(cur);
     cur.key = 0;
     cur.flags = 0;
     if (lane == 0) hist[0] = cur;
@@ -337,9 +345,9 @@ __global__ __launch_bounds__(256) void k_status_final(int n, int32_t* status) {
 namespace scl {
 void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
                       int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
-                      int32_t* outcome, hipStream_t s) {
+                      int32_t* outcome, hipStream_t s, const sc::Position* d_bases, const int32_t* d_base_idx) {
     hipLaunchKernelGGL(sc::k_encode_positions, dim3(n_pos), dim3(64), 0, s, n_pos, d_moves, d_move_off, d_move_len, d_hist, hist_cap,
-                       boards, meta, legal_mv, legal_idx, n_legal, outcome);
+                       boards, meta, legal_mv, legal_idx, n_legal, outcome, d_bases, d_base_idx);
 }
 void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
                const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s) {
@@ -348,9 +356,10 @@ void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, u
                        d_rows, num_steps, t_move, d_moves, d_src);
 }
 void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
-                  const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s) {
+                  const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s, const sc::Position* d_bases,
+                  const int32_t* d_base_idx) {
     if (n_games <= 0 || n_plies <= 0) return;
-    hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap);
+    hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap, d_bases, d_base_idx);
     hipLaunchKernelGGL(sc::k_ply_keys, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen, d_ply_moves);
     hipLaunchKernelGGL(sc::k_ply_rep, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen);
 }

@@ -66,7 +66,7 @@ int check_device_outputs(const DevEncodeOut& o, int dev) {
 // stay in the arena between the two halves: nothing comes back to the host.
 int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
                        const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
-                       hipStream_t st, const SanSrc* san) {
+                       hipStream_t st, const SanSrc* san, const BaseSrc* base) {
     const uint32_t P = ply_off[n_games];
     // the game records of one group of games: (games in the group) x (longest game of the group + 2) <= REC_BUDGET, so one long
     // game among many short ones does not size the buffer for all of them (80 B per record: 80 MiB)
@@ -97,7 +97,7 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
     uint16_t *d_moves, *d_lm, *d_cmv;
     uint64_t* d_tok;
     sc::Position* d_hist;
-    int32_t *d_meta, *d_nl, *d_rows;
+    int32_t *d_meta, *d_nl, *d_rows, *d_bidx;
     ArenaLayout L;
     L.add(&d_off, (size_t)n_games + 1);
     L.add(&d_moves, (size_t)P);
@@ -114,6 +114,7 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
     L.add(&d_cmv, (size_t)nchild, has_csr);
     L.add(&d_cn, (size_t)nchild, has_csr);
     L.add(&d_tok, (size_t)P, san != nullptr);
+    L.add(&d_bidx, (size_t)n_games, base != nullptr);
     std::lock_guard<std::mutex> lk(g_enc_mu);
     EncArena& A = g_enc_arena[dev];
     if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
@@ -128,11 +129,13 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
     guard.armed = true;
     L.bind(A.buf.p);
     HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
+    if (base) HIPOK(hipMemcpyAsync(d_bidx, base->idx, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
+    const sc::Position* d_bases = base ? base->rec : nullptr;
     if (ring) {
         HIPOK(hipMemcpyAsync(d_rows, ring->rows, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
     } else if (san) {
         if (P) HIPOK(hipMemcpyAsync(d_tok, san->tokens, (size_t)P * 8, hipMemcpyHostToDevice, st));
-        scl::san_parse(n_games, d_tok, d_off, d_moves, o.status, st);
+        scl::san_parse(n_games, d_tok, d_off, d_moves, o.status, st, d_bases, d_bidx);
         if (P && san->moves_out) HIPOK(hipMemcpyAsync(san->moves_out, d_moves, (size_t)P * 2, hipMemcpyDeviceToDevice, st));
     } else {
         if (P) HIPOK(hipMemcpyAsync(d_moves, moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
@@ -151,7 +154,8 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
         if (san && !rows_wanted) break;   // SAN -> moves alone
         scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, d_rows, ring ? ring->p->num_steps : 0,
                        ring ? ring->p->t_move : nullptr, d_moves, d_src, st);
-        scl::replay_games(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st);
+        scl::replay_games(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st,
+                          d_bases, d_bases ? d_bidx + gr.g0 : nullptr);
         for (uint32_t c0 = p0; c0 < p1; c0 += CH) {
             const uint32_t n = std::min(CH, p1 - c0);
             scl::encode_plies(o.layout, (int)n, d_hist, d_hoff + c0, d_plen + c0,
@@ -195,9 +199,19 @@ int sc_encode_steps_device(sc_engine* e, int device_id, int n_games, const uint1
                            const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off, int apply_mirror, int layout,
                            void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
                            int32_t* n_legal, int32_t* status) {
+    return sc_encode_steps_device_from(e, device_id, n_games, nullptr, nullptr, moves, move_off, child_mv, child_n, child_off, apply_mirror,
+                                       layout, stream, boards, meta, dist, dist_legal, legal_idx, n_legal, status);
+}
+
+int sc_encode_steps_device_from(sc_engine* e, int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx,
+                                const uint16_t* moves, const uint32_t* move_off, const uint16_t* child_mv, const uint32_t* child_n,
+                                const uint32_t* child_off, int apply_mirror, int layout, void* stream, void* boards, void* meta,
+                                float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, int32_t* status) {
     if (n_games < 0 || !move_off || !child_off || !status) return fail("bad argument");
     TRY(use_device(e, device_id));
     const int dev = e ? e->device : device_id;
+    BaseSrc base{nullptr, base_idx};
+    TRY(positions_bases(bases, base_idx, n_games, dev, false, "sc_encode_steps_device_from", &base.rec));
     const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
     TRY(check_device_outputs(o, dev));
     if (n_games == 0) return 0;
@@ -206,15 +220,25 @@ int sc_encode_steps_device(sc_engine* e, int device_id, int n_games, const uint1
     if (total && !moves) return fail("bad argument");
     if (child_off[total] && (!child_mv || !child_n)) return fail("bad argument");
     return encode_device_core(dev, n_games, move_off, moves, child_mv, child_n, child_off, nullptr, apply_mirror, o,
-                              static_cast<hipStream_t>(stream));
+                              static_cast<hipStream_t>(stream), nullptr, base.rec ? &base : nullptr);
 }
 
 int sc_encode_san_device(sc_engine* e, int device_id, int n_games, const uint64_t* tokens, const uint32_t* tok_off, int apply_mirror,
                          int layout, void* stream, void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx,
                          int32_t* n_legal, uint16_t* moves, int32_t* status) {
+    return sc_encode_san_device_from(e, device_id, n_games, nullptr, nullptr, tokens, tok_off, apply_mirror, layout, stream, boards, meta, dist,
+                                     dist_legal, legal_idx, n_legal, moves, status);
+}
+
+int sc_encode_san_device_from(sc_engine* e, int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx,
+                              const uint64_t* tokens, const uint32_t* tok_off, int apply_mirror, int layout, void* stream, void* boards,
+                              void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, uint16_t* moves,
+                              int32_t* status) {
     if (n_games < 0 || !tok_off || !status) return fail("bad argument");
     TRY(use_device(e, device_id));
     const int dev = e ? e->device : device_id;
+    BaseSrc base{nullptr, base_idx};
+    TRY(positions_bases(bases, base_idx, n_games, dev, false, "sc_encode_san_device_from", &base.rec));
     const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
     TRY(check_device_outputs(o, dev));
     TRY(check_device_ptrs({{moves, "moves"}}, dev));
@@ -223,7 +247,7 @@ int sc_encode_san_device(sc_engine* e, int device_id, int n_games, const uint64_
     if (tok_off[n_games] && !tokens) return fail("bad argument");
     const SanSrc san{tokens, moves};
     return encode_device_core(dev, n_games, tok_off, nullptr, nullptr, nullptr, nullptr, nullptr, apply_mirror, o,
-                              static_cast<hipStream_t>(stream), &san);
+                              static_cast<hipStream_t>(stream), &san, base.rec ? &base : nullptr);
 }
 
 int sc_san_tokenize(const char* text, size_t len, uint64_t* tokens, uint32_t cap, uint32_t* n_tokens) {

@@ -322,9 +322,18 @@ int sc_predict_batch_argmax(sc_engine* e, int n, const int8_t* boards, const int
 
 int sc_encode_positions(sc_engine* e, int device_id, int n, const uint16_t* moves, const uint32_t* move_off, int8_t* boards,
                         int32_t* meta, uint16_t* legal_moves, uint16_t* legal_idx, int32_t* n_legal, int32_t* outcome) {
+    return sc_encode_positions_from(e, device_id, n, nullptr, nullptr, moves, move_off, boards, meta, legal_moves, legal_idx, n_legal, outcome);
+}
+
+// ... from a base per position (a set of validated records, positions.hip); without bases the call above
+int sc_encode_positions_from(sc_engine* e, int device_id, int n, const sc_positions* bases, const int32_t* base_idx, const uint16_t* moves,
+                             const uint32_t* move_off, int8_t* boards, int32_t* meta, uint16_t* legal_moves, uint16_t* legal_idx,
+                             int32_t* n_legal, int32_t* outcome) {
     if (n < 0 || !move_off) return fail("bad argument");
     if (n == 0) return 0;
     TRY(use_device(e, device_id));
+    const sc::Position* d_bases = nullptr;
+    TRY(positions_bases(bases, base_idx, n, e ? e->device : device_id, false, "sc_encode_positions_from", &d_bases));
     uint32_t total = move_off[n];
     uint32_t maxlen = 0;
     for (int i = 0; i < n; i++) {
@@ -339,10 +348,11 @@ int sc_encode_positions(sc_engine* e, int device_id, int n, const uint16_t* move
     uint32_t* d_off;
     sc::Position* d_hist;
     int8_t* d_boards;
-    int32_t *d_meta, *d_nl, *d_out;
+    int32_t *d_meta, *d_nl, *d_out, *d_bidx;
     ArenaLayout L;
     L.add(&d_moves, (size_t)total + 1);
     L.add(&d_off, (size_t)n + 1);
+    L.add(&d_bidx, (size_t)n, d_bases != nullptr);
     L.add(&d_hist, (size_t)n * hist_cap);
     L.add(&d_boards, (size_t)n * 7168);
     L.add(&d_meta, (size_t)n * 7);
@@ -359,7 +369,8 @@ int sc_encode_positions(sc_engine* e, int device_id, int n, const uint16_t* move
     HIPOK(hipMemcpyAsync(d_off, move_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
     HIPOK(hipMemsetAsync(d_lm, 0, (size_t)n * 448, st));   // rows are zero past n_legal (each region is padded to 256 B:
     HIPOK(hipMemsetAsync(d_li, 0, (size_t)n * 448, st));   // the two tables are not adjacent in general)
-    scl::encode_positions(n, d_moves, d_off, nullptr, d_hist, hist_cap, d_boards, d_meta, d_lm, d_li, d_nl, d_out, st);
+    if (d_bases) HIPOK(hipMemcpyAsync(d_bidx, base_idx, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    scl::encode_positions(n, d_moves, d_off, nullptr, d_hist, hist_cap, d_boards, d_meta, d_lm, d_li, d_nl, d_out, st, d_bases, d_bidx);
     HIPOK(hipGetLastError());
     if (boards) HIPOK(hipMemcpyAsync(boards, d_boards, (size_t)n * 7168, hipMemcpyDeviceToHost, st));
     if (meta) HIPOK(hipMemcpyAsync(meta, d_meta, (size_t)n * 7 * 4, hipMemcpyDeviceToHost, st));

@@ -159,6 +159,28 @@ scnn::Fc1Args fc1_args(const sc_engine* e, int n, const scnn::bf16_t* hval, floa
 void enqueue_forward(sc_engine* e, int n, const int8_t* boards, const int32_t* meta, int meta_stride, const uint16_t* lidx,
                      const int32_t* nlegal, float* prior, float* value, float* logp, float* dbg, int dbg_stage, hipStream_t s);
 
+// ------------------------------------------------------------------ positions given as FEN (positions.hip)
+// n validated records in device memory (fen_kernels.hip) and the host's copy of them, their status and the ep bit of Board.fen()
+struct sc_positions {
+    int device = 0;
+    int n = 0;
+    sc::Position* d_rec = nullptr;
+    std::vector<sc::Position> rec;
+    std::vector<int32_t> status;
+    std::vector<int32_t> ep_legal;
+};
+// The bases of a call that takes them: checks the set's device and every index of idx[0..n) (host; < 0: no base) against the
+// set -- a negative status is refused, and with for_search a status of 1 too -- and returns the records.  bases == nullptr or
+// idx == nullptr: *d_rec = nullptr (no bases)
+int positions_bases(const sc_positions* bases, const int32_t* idx, int n, int dev, bool for_search, const char* who, const sc::Position** d_rec);
+// Board.fen() of a record
+std::string position_fen(const sc::Position& p, bool ep_legal);
+// the bases of an encoder call: the records (device) and the base index of every game (host, n_games; < 0: none)
+struct BaseSrc {
+    const sc::Position* rec;
+    const int32_t* idx;
+};
+
 // ------------------------------------------------------------------ training tensors on the device (encode_steps.hip)
 struct DevEncodeOut {
     int layout;
@@ -185,7 +207,7 @@ int check_device_ptrs(std::initializer_list<std::pair<const void*, const char*>>
 int check_device_outputs(const DevEncodeOut& o, int dev);
 int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
                        const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
-                       hipStream_t st, const SanSrc* san = nullptr);
+                       hipStream_t st, const SanSrc* san = nullptr, const BaseSrc* base = nullptr);
 
 // ------------------------------------------------------------------ self-play (selfplay.hip, selfplay_io.hip)
 struct sc_selfplay {
@@ -218,6 +240,7 @@ struct sc_selfplay {
     sc::MatchLines open_lines{nullptr, nullptr, 0};
     std::vector<uint16_t> open_moves;
     std::vector<uint32_t> open_move_off;   // [n + 1]
+    std::vector<std::string> open_fens;    // [n] or empty: the base of each line as Board.fen() prints it, "" for the start position
     scnn::bf16_t* d_hval = nullptr;  // value-head features of the current leaves [n_slots][64][256]
     float* d_vpart = nullptr;        // split-K partials of value_head.ffn.0 [ksplit][n_slots][128]
     // streaming drain (sc_selfplay_poll): per trace-ring row, the game id last reported to the host (+1; 0 = none)
@@ -252,5 +275,7 @@ int sp_latch(sc_selfplay* sp);   // called with the stream idle: looks at the de
 int sp_quiesce(sc_selfplay* sp, bool latch);
 // the opening line of handle-local game `game` (sc_selfplay_set_openings): its length, *moves = its first move; 0 without lines
 int sp_opening(const sc_selfplay* sp, int game, const uint16_t** moves);
+// the base of that line (sc_selfplay_set_openings_from) as FEN text, or null for a line from the start position
+const char* sp_opening_fen(const sc_selfplay* sp, int game);
 
 #pragma GCC visibility pop

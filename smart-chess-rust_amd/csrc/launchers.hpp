@@ -7,6 +7,8 @@
 #include "score_types.hpp"
 #include "batch_types.hpp"
 
+struct sc_fen_fields;   // include/sc_engine.h
+
 namespace scl {
 // mcts_kernels.hip (compiled with -ffp-contract=off)
 void init_slots(const sc::SpParams& p, const sc::MatchLines& lines, hipStream_t s);
@@ -15,16 +17,18 @@ void synth_eval(const sc::SpParams& p, hipStream_t s);
 void debug_find_max(const float* d_u, int n, int* d_out, hipStream_t s);
 void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc, const float* d_temperature, const float* d_u, int tie_random,
                         const float* d_w, const int32_t* d_w_off, int w_max, int32_t* d_choice, float* d_total, hipStream_t s);
-void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s);
+void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s, const sc::Position* d_base = nullptr);
 void match_boundary(const sc::SpParams& p, const sc::MatchLines& lines, hipStream_t s);   // match recycling: count the games that ended, start the next ones
 // sc_selfplay_set_openings: replay and check n_lines move lists into their records (rec_off as sc::MatchLines::off) -> status [n_lines]
+// d_bases / d_base_idx (or null): line i starts from record d_base_idx[i] of d_bases where that is >= 0, behind as many empty
+// records as rec_off leaves room for in front of it (sc_selfplay_set_openings_from)
 void open_lines(int n_lines, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_tab, const uint32_t* d_rec_off,
-                int32_t* d_status, hipStream_t s);
+                int32_t* d_status, hipStream_t s, const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
 void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s);   // [n_slots][2][4] -> [8]
 // encode_kernels.hip (compiled with -ffp-contract=off)
 void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
                       int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
-                      int32_t* outcome, hipStream_t s);
+                      int32_t* outcome, hipStream_t s, const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
 // training tensors (sc_encode_steps, sc_encode_steps_device, sc_selfplay_encode_traces): see encode_kernels.hip
 void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
                const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s);
@@ -32,7 +36,8 @@ void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, u
 // d_hoff / d_plen / d_ply_moves are the group's plies (record offset of the ply's game, moves played before the ply, the ply's
 // move = d_moves + p0)
 void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
-                  const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s);
+                  const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s,
+                  const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);   // base of each game of the group, or null
 void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
                   int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s);
 void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
@@ -42,9 +47,13 @@ void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const
 void status_final(int n, int32_t* status, hipStream_t s);
 // san_kernels.hip: SAN tokens -> moves and the parser's status per game (sc_encode_san_device), and steps_dist for rows whose
 // children are the legal moves with count 1 on the played move
-void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status, hipStream_t s);
+void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status, hipStream_t s,
+               const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
 void san_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, int apply_mirror, const int32_t* meta_s,
               int layout, void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out, hipStream_t s);
+// fen_kernels.hip: raw FEN fields -> validated records and their status (sc_positions_from_fen); the ep bit of Board.fen()
+void fen_positions(int n, const sc_fen_fields* d_fields, const int32_t* d_syntax, sc::Position* d_out, int32_t* d_status, hipStream_t s);
+void fen_ep_legal(int n, const sc::Position* d_rec, int32_t* d_ep_legal, hipStream_t s);
 // nn_kernels.hip
 const char* nn_init();  // sets kernel attributes; returns error text or nullptr
 size_t tower_lds_bytes(int C);

@@ -17,8 +17,9 @@
 // all games run in lockstep on --games slots, as before.
 // --openings FILE starts game k from line k of FILE (sc_selfplay_set_openings; with --swap both games of a pair from the same line,
 // each network White once).  One line per opening: UCI moves separated by blanks; `#` starts a comment (a line that holds nothing
-// but a comment is skipped); an empty line is the start position.  The games then run on recycled slots (--concurrency, default
-// one slot per game).
+// but a comment is skipped); an empty line is the start position; a line whose first word is `fen` is
+// `fen <the 4 or 6 fields> [moves m1 m2 ...]` and starts from that position (sc_selfplay_set_openings_from).  The games then run on
+// recycled slots (--concurrency, default one slot per game).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -106,8 +107,11 @@ static unsigned parse_uci(const std::string& t) {
     return (unsigned)((t[1] - '1') * 8 + (t[0] - 'a')) | (unsigned)((t[3] - '1') * 8 + (t[2] - 'a')) << 6 | promo << 12;
 }
 
-// the opening file: moves and offsets as sc_selfplay_set_openings takes them, and the file's line number of every opening
-static bool read_openings(const std::string& path, std::vector<uint16_t>& moves, std::vector<uint32_t>& off, std::vector<int>& line_no) {
+// the opening file: moves and offsets as sc_selfplay_set_openings takes them, and the file's line number of every opening.  A line
+// whose first word is `fen` is `fen <the 4 or 6 fields> [moves m1 m2 ...]` (the UCI `position` convention): fens holds its FEN text,
+// "" for every other line; the text's syntax is checked here (sc_fen_parse needs no GPU)
+static bool read_openings(const std::string& path, std::vector<uint16_t>& moves, std::vector<uint32_t>& off, std::vector<int>& line_no,
+                          std::vector<std::string>& fens) {
     std::ifstream f(path);
     if (!f) {
         fprintf(stderr, "cannot open %s\n", path.c_str());
@@ -118,9 +122,21 @@ static bool read_openings(const std::string& path, std::vector<uint16_t>& moves,
     for (int no = 1; std::getline(f, raw); no++) {
         const size_t hash = raw.find('#');
         std::istringstream text(raw.substr(0, hash));
-        std::string tok;
+        std::string tok, fen;
         size_t n = 0;
+        bool in_fen = false, first = true;
         while (text >> tok) {
+            if (first && tok == "fen") {
+                in_fen = true;
+                first = false;
+                continue;
+            }
+            first = false;
+            if (in_fen) {
+                if (tok == "moves") in_fen = false;
+                else fen += (fen.empty() ? "" : " ") + tok;
+                continue;
+            }
             const unsigned m = parse_uci(tok);
             if (m == 0xffff) {
                 fprintf(stderr, "%s:%d: '%s' is not a UCI move\n", path.c_str(), no, tok.c_str());
@@ -129,9 +145,17 @@ static bool read_openings(const std::string& path, std::vector<uint16_t>& moves,
             moves.push_back((uint16_t)m);
             n++;
         }
-        if (n == 0 && hash != std::string::npos) continue;   // a comment line
+        if (n == 0 && fen.empty() && hash != std::string::npos) continue;   // a comment line
+        if (!fen.empty()) {
+            sc_fen_fields ff;
+            if (sc_fen_parse(fen.data(), fen.size(), &ff)) {
+                fprintf(stderr, "%s:%d: '%s': %s\n", path.c_str(), no, fen.c_str(), sc_last_error());
+                return false;
+            }
+        }
         off.push_back((uint32_t)moves.size());
         line_no.push_back(no);
+        fens.push_back(fen);
     }
     if (line_no.empty()) {
         fprintf(stderr, "%s: no opening lines\n", path.c_str());
@@ -176,7 +200,8 @@ int main(int argc, char** argv) {
     std::vector<uint16_t> op_moves;
     std::vector<uint32_t> op_off;
     std::vector<int> op_line_no;
-    if (!a.openings.empty() && !read_openings(a.openings, op_moves, op_off, op_line_no)) return 2;
+    std::vector<std::string> op_fens;
+    if (!a.openings.empty() && !read_openings(a.openings, op_moves, op_off, op_line_no, op_fens)) return 2;
     if (a.swap == a.swap_output.empty()) {
         fprintf(stderr, "--swap and --swap-output go together\n");
         return 2;
@@ -218,9 +243,20 @@ int main(int argc, char** argv) {
     if (!rc && !a.openings.empty()) {
         std::vector<int32_t> status(op_line_no.size(), 0);
         op_moves.push_back(0);   // (never an empty array)
-        rc = sc_selfplay_set_openings(sp, (int)op_line_no.size(), op_moves.data(), op_off.data(), status.data());
+        // lines that start from a FEN: one validated set of their positions, a base index per line
+        std::vector<const char*> texts;
+        std::vector<int32_t> base_idx(op_line_no.size(), -1);
+        for (size_t i = 0; i < op_fens.size(); i++)
+            if (!op_fens[i].empty()) {
+                base_idx[i] = (int32_t)texts.size();
+                texts.push_back(op_fens[i].c_str());
+            }
+        sc_positions* bases = nullptr;
+        if (!texts.empty()) rc = sc_positions_from_fen(0, (int)texts.size(), texts.data(), &bases, nullptr);
+        if (!rc) rc = sc_selfplay_set_openings_from(sp, (int)op_line_no.size(), bases, base_idx.data(), op_moves.data(), op_off.data(), status.data());
         for (size_t i = 0; i < status.size(); i++)
             if (status[i]) fprintf(stderr, "%s:%d: opening refused, status %d\n", a.openings.c_str(), op_line_no[i], status[i]);
+        sc_positions_destroy(bases);   // (the handle keeps its own records of the lines)
     }
     if (!rc) rc = sc_selfplay_run(sp, 0);
     if (rc) {

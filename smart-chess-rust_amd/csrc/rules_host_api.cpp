@@ -97,6 +97,18 @@ int sct_set_fen(sct_state* s, const char* fen) {
     return 0;
 }
 int sct_turn(const sct_state* s) { return s->hist.back().turn; }
+// the current position's fields, for the tests of the FEN reader: out = pcs[6], occ[2], then turn, castling, ep, halfmove, fullmove
+void sct_get_fields(const sct_state* s, uint64_t* out /*13*/) {
+    const Position& p = s->hist.back();
+    for (int t = 0; t < 6; t++) out[t] = p.pcs[t];
+    out[6] = p.occ[0];
+    out[7] = p.occ[1];
+    out[8] = p.turn;
+    out[9] = p.castling;
+    out[10] = (uint64_t)(int64_t)p.ep;
+    out[11] = p.halfmove;
+    out[12] = p.fullmove;
+}
 void sct_push(sct_state* s, uint16_t m) {
     Position p = s->hist.back();
     make_move(p, m);

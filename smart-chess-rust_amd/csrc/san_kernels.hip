@@ -87,7 +87,8 @@ __device__ __forceinline__ bool san_match(const Position& p, const SanTok& d, mo
 // than one; 200000 + i: it is malformed or the reserved value.  The first failing ply wins; the game's moves from that ply on
 // are written as 0, which no walk plays.  Claimable draws do not stop the parse (python-chess's read_game goes on too).
 __global__ __launch_bounds__(64) void k_san_parse(int n_games, const uint64_t* __restrict__ tokens, const uint32_t* __restrict__ tok_off,
-                                                  uint16_t* __restrict__ moves, int32_t* __restrict__ status) {
+                                                  uint16_t* __restrict__ moves, int32_t* __restrict__ status,
+                                                  const Position* __restrict__ bases, const int32_t* __restrict__ base_idx) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n_games) return;
     __shared__ move_t s_moves[MAXC];
@@ -96,7 +97,9 @@ __global__ __launch_bounds__(64) void k_san_parse(int n_games, const uint64_t* _
     const uint64_t* tk = tokens + p0;
     uint16_t* out = moves + p0;
     Position cur;
-    set_startpos(cur);
+    const int bi = bases ? uniform(base_idx[g]) : -1;   // the game's base record (fen_kernels.hip), else the start position
+    if (bi >= 0) cur = uniform(bases[bi]);
+    else set_startpos(cur);
     cur.key = 0;
     cur.flags = 0;
     int st = 0, j = 0;
@@ -175,9 +178,10 @@ __global__ __launch_bounds__(64) void k_san_dist(int n, const uint16_t* legal_mv
 }  // namespace sc
 
 namespace scl {
-void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status, hipStream_t s) {
+void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status, hipStream_t s,
+               const sc::Position* d_bases, const int32_t* d_base_idx) {
     if (n_games <= 0) return;
-    hipLaunchKernelGGL(sc::k_san_parse, dim3(n_games), dim3(64), 0, s, n_games, d_tokens, d_tok_off, d_moves, d_status);
+    hipLaunchKernelGGL(sc::k_san_parse, dim3(n_games), dim3(64), 0, s, n_games, d_tokens, d_tok_off, d_moves, d_status, d_bases, d_base_idx);
 }
 void san_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, int apply_mirror, const int32_t* meta_s,
               int layout, void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out, hipStream_t s) {

@@ -102,6 +102,11 @@ int sp_opening(const sc_selfplay* sp, int game, const uint16_t** moves) {
     if (moves) *moves = sp->open_moves.data() + sp->open_move_off[i];
     return (int)(sp->open_move_off[i + 1] - sp->open_move_off[i]);
 }
+const char* sp_opening_fen(const sc_selfplay* sp, int game) {
+    if (sp->open_lines.n <= 0 || sp->open_fens.empty()) return nullptr;
+    const size_t i = (size_t)((sp->p.match_colours ? game >> 1 : game) % sp->open_lines.n);
+    return sp->open_fens[i].empty() ? nullptr : sp->open_fens[i].c_str();
+}
 
 // The weights of the end-of-ply move choice (mcts::step, src/mcts.rs:313-315): w[n] = powf((float)n, 1.0f / temperature) for
 // n = 0..n_max, computed HERE, by the host libm -- the function the reference's f32::powf is.  The kernels read the table
@@ -468,19 +473,56 @@ int sc_selfplay_set_match(sc_selfplay* sp, sc_engine* a, sc_engine* b, uint64_t 
 // records into the slot (k_match_boundary).  Nothing has run on the handle yet: as sc_selfplay_set_match does, the slots' initial
 // draw is taken back and made again, now with the lines.
 int sc_selfplay_set_openings(sc_selfplay* sp, int n_lines, const uint16_t* moves, const uint32_t* move_off, int32_t* status) {
+    return sc_selfplay_set_openings_from(sp, n_lines, nullptr, nullptr, moves, move_off, status);
+}
+
+// ... with a base per line.  The start rule lives in k_match_boundary, which reads it off the line's record count: the first
+// searched ply of a line of `len + 1` records belongs to player white(k) ^ (len & 1), and a line of one record is not copied at all
+// (the slot already holds the start position).  That kernel stays as it is.  A base makes the host choose the record count
+// instead: `pad` empty records in front of the base, so that len = pad + L is odd exactly when Black is to move in the line's
+// last position, and at least 1 -- one record for a base with Black to move, two for a base with White to move and no moves.
+// k_open_lines writes them (no men, no flags: zero planes) and marks the base F_IRREV, where every repetition scan stops.
+int sc_selfplay_set_openings_from(sc_selfplay* sp, int n_lines, const sc_positions* bases, const int32_t* base_idx, const uint16_t* moves,
+                                  const uint32_t* move_off, int32_t* status) {
     if (!sp) return fail("null handle");
     if (sp->poisoned) return sp_refuse(sp);
     if (!sp->p.match_recycle) return fail("set_openings needs a handle set up by sc_selfplay_set_match");
     if (sp->sim_steps_enqueued != 0) return fail("set_openings must precede the first enqueue");
     if (n_lines < 1 || !move_off) return fail("set_openings: bad argument");
     sc::SpParams& p = sp->p;
+    if (!bases || !base_idx) {
+        bases = nullptr;
+        base_idx = nullptr;
+    }
+    if (bases) {
+        if (bases->device != sp->device) return fail("set_openings: the positions live on another device than the handle");
+        if (status) std::fill(status, status + n_lines, 0);
+        int bad = -1;
+        for (int i = 0; i < n_lines; i++) {
+            const int b = base_idx[i];
+            if (b >= bases->n) return fail("set_openings: base index " + std::to_string(b) + " of " + std::to_string(bases->n) + " positions");
+            if (b >= 0 && bases->status[(size_t)b] != 0) {
+                if (status) status[i] = bases->status[(size_t)b];
+                if (bad < 0) bad = i;
+            }
+        }
+        if (bad >= 0)
+            return fail("set_openings: the base of line " + std::to_string(bad) + " has status " + std::to_string(bases->status[(size_t)base_idx[bad]]) +
+                        (bases->status[(size_t)base_idx[bad]] < 0 ? " (it cannot be played)" : " (the game is over there)"));
+    }
     std::vector<uint32_t> rec_off((size_t)n_lines + 1, 0);
     for (int i = 0; i < n_lines; i++) {
         if (move_off[i + 1] < move_off[i]) return fail("set_openings: move_off must not decrease");
         const uint32_t len = move_off[i + 1] - move_off[i];
-        if (len > 600 || (int64_t)len + 1 > (int64_t)p.hist_cap)
+        uint32_t pad = 0;
+        if (bases && base_idx[i] >= 0) {
+            const bool black_last = (bases->rec[(size_t)base_idx[i]].turn == sc::BLACK) != ((len & 1) != 0);
+            pad = ((len & 1) != 0) == black_last ? 0 : 1;
+            if (pad + len == 0) pad = 2;
+        }
+        if (len > 600 || (int64_t)pad + len + 1 > (int64_t)p.hist_cap)
             return fail("set_openings: line " + std::to_string(i) + " has " + std::to_string(len) + " plies (at most 600)");
-        rec_off[(size_t)i + 1] = rec_off[(size_t)i] + len + 1;
+        rec_off[(size_t)i + 1] = rec_off[(size_t)i] + pad + len + 1;
         if ((size_t)rec_off[(size_t)i + 1] * sizeof(sc::Position) > ((size_t)1 << 30))
             return fail("set_openings: the lines' position records exceed 1 GiB");
     }
@@ -490,8 +532,12 @@ int sc_selfplay_set_openings(sc_selfplay* sp, int n_lines, const uint16_t* moves
     HIPOK(hipSetDevice(sp->device));
     ScopedDev<uint16_t> d_moves;
     ScopedDev<uint32_t> d_moff, d_roff;
-    ScopedDev<int32_t> d_status;
+    ScopedDev<int32_t> d_status, d_bidx;
     ScopedDev<sc::Position> d_tab;
+    if (bases) {
+        HIPOK(d_bidx.alloc((size_t)n_lines));
+        HIPOK(hipMemcpy(d_bidx.p, base_idx, (size_t)n_lines * 4, hipMemcpyHostToDevice));
+    }
     HIPOK(d_moves.alloc(n_moves));
     HIPOK(d_moff.alloc((size_t)n_lines + 1));
     HIPOK(d_roff.alloc((size_t)n_lines + 1));
@@ -500,7 +546,7 @@ int sc_selfplay_set_openings(sc_selfplay* sp, int n_lines, const uint16_t* moves
     if (n_moves) HIPOK(hipMemcpy(d_moves.p, moves, n_moves * 2, hipMemcpyHostToDevice));
     HIPOK(hipMemcpy(d_moff.p, move_off, ((size_t)n_lines + 1) * 4, hipMemcpyHostToDevice));
     HIPOK(hipMemcpy(d_roff.p, rec_off.data(), ((size_t)n_lines + 1) * 4, hipMemcpyHostToDevice));
-    scl::open_lines(n_lines, d_moves.p, d_moff.p, d_tab.p, d_roff.p, d_status.p, sp->stream);
+    scl::open_lines(n_lines, d_moves.p, d_moff.p, d_tab.p, d_roff.p, d_status.p, sp->stream, bases ? bases->d_rec : nullptr, d_bidx.p);
     HIPOK(hipGetLastError());
     HIPOK(hipStreamSynchronize(sp->stream));
     std::vector<int32_t> st((size_t)n_lines);
@@ -535,7 +581,26 @@ int sc_selfplay_set_openings(sc_selfplay* sp, int n_lines, const uint16_t* moves
     if (n_moves > first) sp->open_moves.assign(moves + first, moves + n_moves);
     sp->open_move_off.resize((size_t)n_lines + 1);
     for (int i = 0; i <= n_lines; i++) sp->open_move_off[(size_t)i] = move_off[i] - (uint32_t)first;
+    sp->open_fens.clear();
+    if (bases) {
+        sp->open_fens.resize((size_t)n_lines);
+        for (int i = 0; i < n_lines; i++)
+            if (base_idx[i] >= 0) sp->open_fens[(size_t)i] = position_fen(bases->rec[(size_t)base_idx[i]], bases->ep_legal[(size_t)base_idx[i]] != 0);
+    }
     return 0;
+}
+
+int sc_selfplay_get_opening_fen(sc_selfplay* sp, int game, char* buf, int cap) {
+    if (!sp) return fail("null handle");
+    if (game < 0 || game >= sp->cfg.n_games || cap < 0 || (cap > 0 && !buf)) return fail("bad argument");
+    const char* fen = sp_opening_fen(sp, game);
+    const std::string s = fen ? fen : "";
+    if (cap > 0) {
+        const size_t k = std::min(s.size(), (size_t)cap - 1);
+        memcpy(buf, s.data(), k);
+        buf[k] = 0;
+    }
+    return (int)s.size();
 }
 
 int sc_selfplay_get_opening(sc_selfplay* sp, int game, uint16_t* moves, int cap) {

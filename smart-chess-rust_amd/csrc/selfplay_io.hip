@@ -131,7 +131,7 @@ int sc_selfplay_encode_traces(sc_selfplay* sp, int n, const int32_t* games, int 
     for (int i = 0; i < n; i++) {
         const int g = games[i];
         if (g < 0 || g >= p.total_games) return fail("bad argument: game index out of range");
-        if (sp_opening(sp, g, nullptr) > 0)
+        if (sp_opening(sp, g, nullptr) > 0 || sp_opening_fen(sp, g))
             return fail("encode_traces: game " + std::to_string(g) + " started from an opening line (sc_selfplay_set_openings): training tensors "
                         "need the plies from the start position");
         const int row = g % p.trace_cap;
@@ -179,11 +179,12 @@ int sc_selfplay_write_trace_json(sc_selfplay* sp, int game, const char* path) {
     TRY(sc_selfplay_get_trace(sp, game, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data()));
     const uint16_t* line = nullptr;
     const int len = sp_opening(sp, game, &line);
-    if (len == 0) return sc_trace_write_json(path, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data());
-    // a game that started from an opening line: a third key, "opening", behind the reference's two
+    const char* fen = sp_opening_fen(sp, game);
+    if (len == 0 && !fen) return sc_trace_write_json(path, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data());
+    // a game that started from an opening line: a third key, "opening", behind the reference's two; from a base: "fen" in front of it
     if (!path) return fail("bad argument");
     const std::string js = sctrace::trace_to_json(info.n_steps, info.has_outcome, info.termination, info.winner, sm.data(), sq.data(), co.data(),
-                                                  cm.data(), cn.data(), cq.data(), cu.data(), line, len);
+                                                  cm.data(), cn.data(), cq.data(), cu.data(), line, len, fen);
     FILE* f = fopen(path, "wb");
     if (!f) return fail(std::string("cannot open ") + path);
     const size_t w = fwrite(js.data(), 1, js.size(), f);
@@ -250,7 +251,17 @@ int sc_selfplay_get_noise(sc_selfplay* sp, int slot, float* noise, int cap) {
 }
 
 int sc_selfplay_set_position(sc_selfplay* sp, int slot, const uint16_t* moves, int n_moves) {
+    return sc_selfplay_set_position_from(sp, slot, nullptr, 0, moves, n_moves);
+}
+
+int sc_selfplay_set_position_from(sc_selfplay* sp, int slot, const sc_positions* bases, int i, const uint16_t* moves, int n_moves) {
     if (!sp || slot < 0 || slot >= sp->p.n_slots || n_moves < 0 || n_moves > 590) return fail("bad argument");
+    const sc::Position* d_base = nullptr;
+    if (bases) {
+        TRY(positions_bases(bases, &i, 1, sp->device, true, "sc_selfplay_set_position_from", &d_base));
+        if (i < 0) return fail("sc_selfplay_set_position_from: bad base index");
+        d_base += i;
+    }
     TRY(sp_quiesce(sp, false));
     {
         sc::GameCtl c;
@@ -260,16 +271,50 @@ int sc_selfplay_set_position(sc_selfplay* sp, int slot, const uint16_t* moves, i
     ScopedDev<uint16_t> d_moves;
     HIPOK(d_moves.alloc((size_t)n_moves));
     if (n_moves) HIPOK(hipMemcpy(d_moves.p, moves, (size_t)n_moves * 2, hipMemcpyHostToDevice));
-    scl::set_position(sp->p, slot, d_moves.p, n_moves, sp->stream);
+    scl::set_position(sp->p, slot, d_moves.p, n_moves, sp->stream, d_base);
     HIPOK(hipGetLastError());
     HIPOK(hipStreamSynchronize(sp->stream));
     return 0;
+}
+
+// Board.fen() of the slot's current position: the record is the last of the slot's chain; a lane of k_fen_ep_legal decides whether
+// the ep square is printed, the text is formatted here
+int sc_selfplay_get_fen(sc_selfplay* sp, int slot, char* buf, int cap) {
+    if (!sp || slot < 0 || slot >= sp->p.n_slots || cap < 0 || (cap > 0 && !buf)) return fail("bad argument");
+    TRY(sp_quiesce(sp, false));
+    sc::GameCtl c;
+    HIPOK(hipMemcpy(&c, sp->p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
+    if (c.status != sc::ST_ACTIVE && c.status != sc::ST_FINISHED) return fail("sc_selfplay_get_fen: the slot holds no game");
+    if (c.ply < 0 || c.ply >= sp->p.hist_cap) return fail("sc_selfplay_get_fen: the slot's ply is outside its chain");
+    const sc::Position* d_rec = sp->p.hist + (size_t)slot * sp->p.hist_cap + c.ply;
+    ScopedDev<int32_t> d_epl;
+    HIPOK(d_epl.alloc(1));
+    scl::fen_ep_legal(1, d_rec, d_epl.p, sp->stream);
+    HIPOK(hipGetLastError());
+    HIPOK(hipStreamSynchronize(sp->stream));
+    sc::Position rec;
+    int32_t epl = 0;
+    HIPOK(hipMemcpy(&rec, d_rec, sizeof rec, hipMemcpyDeviceToHost));
+    HIPOK(hipMemcpy(&epl, d_epl.p, 4, hipMemcpyDeviceToHost));
+    const std::string s = position_fen(rec, epl != 0);
+    if (cap > 0) {
+        const size_t k = std::min(s.size(), (size_t)cap - 1);
+        memcpy(buf, s.data(), k);
+        buf[k] = 0;
+    }
+    return (int)s.size();
 }
 
 // One search from a given position: the body of NNPlayer::bestmove (src/play.rs:241-252) / chess_play_mcts
 // (src/lib.rs:233-247) as a single call; see include/sc_engine.h
 int sc_search(sc_engine* e, const uint16_t* moves, int n_moves, int rollout, float cpuct, int with_noise, uint64_t seed,
               int cap, uint16_t* child_move, int32_t* child_n, float* child_q, float* child_prior, float* root_q) {
+    return sc_search_from(e, nullptr, 0, moves, n_moves, rollout, cpuct, with_noise, seed, cap, child_move, child_n, child_q, child_prior, root_q);
+}
+
+int sc_search_from(sc_engine* e, const sc_positions* bases, int base_i, const uint16_t* moves, int n_moves, int rollout, float cpuct,
+                   int with_noise, uint64_t seed, int cap, uint16_t* child_move, int32_t* child_n, float* child_q, float* child_prior,
+                   float* root_q) {
     if (!e || rollout < 1 || rollout >= 60000 || cap < 0) return fail("bad argument");
     // one cached handle per engine, rebuilt only when a call asks for more simulations than its node pools hold; every call starts
     // from a fresh one-node tree (sc_selfplay_set_position) with its own options and seed, so the result is that of a new handle
@@ -308,7 +353,7 @@ int sc_search(sc_engine* e, const uint16_t* moves, int n_moves, int rollout, flo
         HIPOK(hipMemcpy(reinterpret_cast<char*>(sp->p.cnt) + offsetof(sc::Counters, err), &zero, 4, hipMemcpyHostToDevice));
     }
     if (rc) return rc;
-    rc = sc_selfplay_set_position(sp, 0, moves, n_moves);
+    rc = sc_selfplay_set_position_from(sp, 0, bases, base_i, moves, n_moves);
     if (!rc) rc = sc_selfplay_enqueue_sims(sp, rollout);
     int n_children = 0;
     if (!rc) {

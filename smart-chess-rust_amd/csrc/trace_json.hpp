@@ -84,7 +84,7 @@ static const char* TERMINATION_NAMES[] = {"", "Checkmate", "Stalemate", "Insuffi
 inline std::string trace_to_json(int n_steps, int has_outcome, int termination, int winner, const uint16_t* step_move,
                                  const float* step_q, const int32_t* child_off, const uint16_t* child_move,
                                  const int32_t* child_n, const float* child_q, const float* child_uct, const uint16_t* opening = nullptr,
-                                 int n_opening = 0) {
+                                 int n_opening = 0, const char* fen = nullptr) {
     std::string o;
     o.reserve((size_t)n_steps * 4096 + 256);
     char mv[8];
@@ -137,6 +137,13 @@ inline std::string trace_to_json(int n_steps, int has_outcome, int termination, 
     }
     // (no reference counterpart) the opening line a match game started from, sc_selfplay_set_openings: "steps" holds the searched
     // plies only.  Absent for a game from the start position: the file is then the reference's, byte for byte.
+    // ... and, in front of it, the position the line started from when that is not the start position (sc_selfplay_set_openings_from);
+    // FEN text holds no character that JSON escapes
+    if (fen) {
+        o += ",\n  \"fen\": \"";
+        o += fen;
+        o += "\"";
+    }
     if (n_opening > 0) {
         o += ",\n  \"opening\": [\n";
         for (int i = 0; i < n_opening; i++) {

@@ -72,6 +72,20 @@ ABI = {
     "sc_engine_synchronize": (_i, [_vp]),
     "sc_forward_debug": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
     "sc_encode_positions": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_fen_parse": (_i, [C.c_char_p, C.c_size_t, _vp]),
+    "sc_positions_from_fen": (_i, [_i, _i, _vp, C.POINTER(_vp), _vp]),
+    "sc_positions_destroy": (None, [_vp]),
+    "sc_positions_count": (_i, [_vp]),
+    "sc_positions_status": (_i, [_vp, _i]),
+    "sc_positions_fen": (_i, [_vp, _i, C.c_char_p, _i]),
+    "sc_encode_positions_from": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_encode_steps_device_from": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_encode_san_device_from": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_selfplay_set_position_from": (_i, [_vp, _i, _vp, _i, _vp, _i]),
+    "sc_search_from": (_i, [_vp, _vp, _i, _vp, _i, _i, _f, _i, C.c_uint64, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sc_selfplay_get_fen": (_i, [_vp, _i, C.c_char_p, _i]),
+    "sc_selfplay_set_openings_from": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sc_selfplay_get_opening_fen": (_i, [_vp, _i, C.c_char_p, _i]),
     "sc_selfplay_create": (_i, [_vp, _i, C.POINTER(SelfplayConfig), C.POINTER(_vp)]),
     "sc_selfplay_destroy": (None, [_vp]),
     "sc_selfplay_enqueue_sims": (_i, [_vp, _i]),

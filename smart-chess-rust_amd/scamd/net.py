@@ -82,11 +82,16 @@ class Engine(_Handle):
         return [pri[off[i]:off[i + 1]] for i in range(n)], value
 
 
-def encode_positions(move_lists, device=0, engine=None):
-    """Rules + encoder on the GPU for positions given as move lists (uint16 moves or UCI strings)."""
+def encode_positions(move_lists, device=0, engine=None, fens=None):
+    """Rules + encoder on the GPU for positions given as move lists (uint16 moves or UCI strings).
+    fens: per move list the position it starts from (sc_encode_positions_from) -- FEN strings, None for the start position -- or
+    a scamd.fen.Positions of as many entries; history planes older than a base are zero."""
+    from .fen import bases_of
     L = lib()
     ml = [list(g) for g in move_lists]
     n = len(ml)
+    dev = engine.device if engine is not None else device
+    pos, bidx, owned = bases_of(fens, n, dev)
     off = np.zeros(n + 1, np.uint32)
     off[1:] = np.cumsum([len(g) for g in ml])
     flat = _moves([m for g in ml for m in g])
@@ -96,8 +101,16 @@ def encode_positions(move_lists, device=0, engine=None):
     li = np.zeros((n, MAX_MOVES), np.uint16)
     nl = np.zeros(n, np.int32)
     oc = np.zeros((n, 4), np.int32)
-    _check(L.sc_encode_positions(engine.h if engine else None, device, n, _p(flat), _p(off), _p(boards), _p(meta), _p(lm),
-                                 _p(li), _p(nl), _p(oc)))
+    try:
+        if pos is None:
+            _check(L.sc_encode_positions(engine.h if engine else None, device, n, _p(flat), _p(off), _p(boards), _p(meta), _p(lm),
+                                         _p(li), _p(nl), _p(oc)))
+        else:
+            _check(L.sc_encode_positions_from(engine.h if engine else None, device, n, pos.h, _p(bidx), _p(flat), _p(off), _p(boards),
+                                              _p(meta), _p(lm), _p(li), _p(nl), _p(oc)))
+    finally:
+        if owned:
+            pos.close()
     return dict(boards=boards, meta=meta, legal_moves=[lm[i, :nl[i]].copy() for i in range(n)],
                 legal_idx=[li[i, :nl[i]].copy() for i in range(n)], n_legal=nl, termination=oc[:, 0], winner=oc[:, 1],
                 is_check=oc[:, 2], status=oc[:, 3])
@@ -114,10 +127,10 @@ class ChessHip:
     def __init__(self, engine):
         self.engine = engine
 
-    def predict(self, moves, argmax=False):
+    def predict(self, moves, argmax=False, fen=None):
         """-> (steps, priors, value): steps = legal moves (uint16) in python-chess order; empty at game end,
-        with value = +1 White won / -1 Black won / 0 (torch.rs:98-106)."""
-        enc = encode_positions([moves], engine=self.engine)
+        with value = +1 White won / -1 Black won / 0 (torch.rs:98-106).  fen: the position the moves start from"""
+        enc = encode_positions([moves], engine=self.engine, fens=None if fen is None else [fen])
         if enc["status"][0] < 0:
             raise EngineError(f"illegal move at index {-enc['status'][0] - 1}")
         if enc["n_legal"][0] == 0:

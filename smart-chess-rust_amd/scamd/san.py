@@ -45,7 +45,7 @@ def pack_tokens(games):
     return flat, off
 
 
-def encode_san_torch(games, winners=None, *, device, layout="reference", dist="legal", apply_mirror=False, engine=None):
+def encode_san_torch(games, winners=None, *, device, layout="reference", dist="legal", apply_mirror=False, engine=None, fens=None):
     """SAN games -> training tensors on the GPU in one call (sc_encode_san_device): every ply a row, dist one-hot on the move
     played (1 / (1 + 1e-5) there, as chess_encode_steps makes of a count of 1).
     games: movetext strings (tokenize) or token arrays, or the pair pack_tokens returns; winners: per game "white" / "black" /
@@ -54,7 +54,10 @@ def encode_san_torch(games, winners=None, *, device, layout="reference", dist="l
     as there; outcome float32 [P] is White's result of the ply's game from winners, 0 without, negated under apply_mirror as
     everywhere) plus moves (torch int16 [P]: the move encoding, which stays below 2^15).  status: 0; -(i+1): token i names no legal move;
     100000 + i: it is ambiguous; 200000 + i: it is malformed.  score_torch, compare_torch, gather_batch_torch and
-    ReplayBuffer.add take the dict as it is."""
+    ReplayBuffer.add take the dict as it is.
+    fens: per game the position it starts from (read_pgn(setup=True)'s third list: FEN strings, None for the start position), or
+    a scamd.fen.Positions of as many entries (sc_encode_san_device_from)."""
+    from .fen import bases_of
     torch = _torch()
     L = lib()
     if isinstance(games, tuple) and len(games) == 2 and all(isinstance(a, np.ndarray) for a in games):
@@ -68,8 +71,20 @@ def encode_san_torch(games, winners=None, *, device, layout="reference", dist="l
     dev = engine.device if engine is not None else device
     out, args = _device_outputs(torch, dev, P, n, layout, dist)
     moves = torch.empty(max(P, 1), dtype=torch.int16, device=torch.device("cuda", dev))
-    _check(L.sc_encode_san_device(engine.h if engine else None, dev, n, _p(flat if flat.size else np.zeros(1, np.uint64)), _p(off),
-                                  int(bool(apply_mirror)), args[0], _stream(torch, dev), *args[1:-1], _tp(moves), args[-1]))
+    pos, bidx, owned = bases_of(fens, n, dev)
+    tok = flat if flat.size else np.zeros(1, np.uint64)
+    if pos is None:
+        _check(L.sc_encode_san_device(engine.h if engine else None, dev, n, _p(tok), _p(off), int(bool(apply_mirror)), args[0],
+                                      _stream(torch, dev), *args[1:-1], _tp(moves), args[-1]))
+    else:
+        try:
+            _check(L.sc_encode_san_device_from(engine.h if engine else None, dev, n, pos.h, _p(bidx), _p(tok), _p(off), int(bool(apply_mirror)),
+                                               args[0], _stream(torch, dev), *args[1:-1], _tp(moves), args[-1]))
+            if owned:
+                torch.cuda.current_stream(dev).synchronize()   # the kernels read the set's records
+        finally:
+            if owned:
+                pos.close()
     oc = np.zeros(n, np.float32) if winners is None else np.asarray([_WINNER[w.lower() if isinstance(w, str) else w] for w in winners], np.float32)
     res = _finish_outputs(torch, out, off, oc, apply_mirror, dev)
     res["moves"] = moves[:P]
@@ -92,17 +107,19 @@ def read_games_csv(path, limit=None):
 _TAG = re.compile(r'^\s*\[\s*(\w+)\s+"((?:[^"\\]|\\.)*)"\s*\]\s*$')
 
 
-def read_pgn(path):
-    """A PGN file -> (list of movetext strings, list of winners from [Result]): parse_pgn of its text"""
+def read_pgn(path, setup=False):
+    """A PGN file -> (list of movetext strings, list of winners from [Result]): parse_pgn of its text; with setup=True a third
+    list, the games' [FEN] headers"""
     with open(path, encoding="utf-8", errors="replace") as f:
-        return parse_pgn(f.read())
+        return parse_pgn(f.read(), setup=setup)
 
 
-def parse_pgn(src):
+def parse_pgn(src, setup=False):
     """PGN text -> (list of movetext strings, list of winners from [Result]).  A game is a block of header tags and the movetext
-    behind it; movetext without headers is a game too.  This library plays from the start position only: a game with a [FEN] or
-    a [SetUp "1"] header raises ValueError, which names the game."""
-    games, winners = [], []
+    behind it; movetext without headers is a game too.  By default only games from the start position are read: a game with a
+    [FEN] or a [SetUp "1"] header raises ValueError, which names the game.  setup=True reads those too and returns a third list:
+    per game the text of its [FEN] header, None for a game from the start position (encode_san_torch's fens=)."""
+    games, winners, fens = [], [], []
     tags, body = {}, []
 
     def close():
@@ -110,10 +127,13 @@ def parse_pgn(src):
         if mt or tags:
             k = len(games) + 1
             name = f"game {k} ({tags.get('White', '?')} - {tags.get('Black', '?')})"
-            if "FEN" in tags or tags.get("SetUp") == "1":
+            if ("FEN" in tags or tags.get("SetUp") == "1") and not setup:
                 raise ValueError(f"{name}: starts from a set-up position ([FEN] / [SetUp \"1\"]); only games from the start position can be read")
+            if tags.get("SetUp") == "1" and "FEN" not in tags:
+                raise ValueError(f"{name}: [SetUp \"1\"] without a [FEN] header")
             games.append(mt)
             winners.append(_RESULT.get(tags.get("Result")))
+            fens.append(tags.get("FEN"))
 
     for ln in src.splitlines():
         m = _TAG.match(ln)
@@ -125,7 +145,7 @@ def parse_pgn(src):
         elif ln.strip() or body:
             body.append(ln)
     close()
-    return games, winners
+    return (games, winners, fens) if setup else (games, winners)
 
 
 def _open_comment(movetext):

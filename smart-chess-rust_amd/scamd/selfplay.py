@@ -44,16 +44,30 @@ class SelfPlay(_Handle):
 
     def set_openings(self, lines):
         """sc_selfplay_set_openings: game k of a match handle starts from line opening_of_game(k, len(lines), colours); a line
-        is a list of UCI strings or uint16 moves (empty: the start position).  Raises EngineError with .status, the per-line
-        codes (0 ok, -(j+1): move j is not legal, 1: the line's last position ends the game), when the call is refused."""
+        is a list of UCI strings or uint16 moves (empty: the start position), or a pair (fen, moves): the moves start from that
+        position (sc_selfplay_set_openings_from).  Raises EngineError with .status, the per-line codes (0 ok, -(j+1): move j is
+        not legal, 1: the line's last position ends the game; for a base that cannot be used, its scamd.fen.Positions status),
+        when the call is refused."""
+        from .fen import bases_of
+        fens = [ln[0] if _is_fen_line(ln) else None for ln in lines]
+        lines = [ln[1] if _is_fen_line(ln) else ln for ln in lines]
         lines = [_moves(ln)[:len(ln)] for ln in lines]
         off = np.zeros(len(lines) + 1, np.uint32)
         off[1:] = np.cumsum([ln.size for ln in lines])
         mv = np.ascontiguousarray(np.concatenate(lines + [np.zeros(1, np.uint16)]), np.uint16)
         status = np.zeros(max(len(lines), 1), np.int32)
-        rc = self.L.sc_selfplay_set_openings(self.h, len(lines), _p(mv), _p(off), _p(status))
+        pos, bidx, owned = bases_of(fens, len(lines), self.device)
+        try:
+            if pos is None:
+                rc = self.L.sc_selfplay_set_openings(self.h, len(lines), _p(mv), _p(off), _p(status))
+            else:
+                rc = self.L.sc_selfplay_set_openings_from(self.h, len(lines), pos.h, _p(bidx), _p(mv), _p(off), _p(status))
+            err = self.L.sc_last_error().decode() if rc != 0 else ""
+        finally:
+            if owned:
+                pos.close()   # (the handle keeps its own records of the lines)
         if rc != 0:
-            e = EngineError(f"libsc_engine error {rc}: {self.L.sc_last_error().decode()}")
+            e = EngineError(f"libsc_engine error {rc}: {err}")
             e.code, e.status = rc, [int(x) for x in status[:len(lines)]]
             raise e
 
@@ -63,6 +77,18 @@ class SelfPlay(_Handle):
         buf = np.zeros(max(n, 1), np.uint16)
         _count(self.L.sc_selfplay_get_opening(self.h, game, _p(buf), n))
         return [move_uci(m) for m in buf[:n]]
+
+    def get_opening_fen(self, game):
+        """sc_selfplay_get_opening_fen: the position the line of handle-local game `game` starts from, None for the start position"""
+        buf = C.create_string_buffer(128)
+        n = _count(self.L.sc_selfplay_get_opening_fen(self.h, game, buf, 128))
+        return buf.value.decode() if n else None
+
+    def fen(self, slot):
+        """sc_selfplay_get_fen: python-chess's Board.fen() of the slot's current position"""
+        buf = C.create_string_buffer(128)
+        _count(self.L.sc_selfplay_get_fen(self.h, slot, buf, 128))
+        return buf.value.decode()
 
     def match_tally(self):
         """sc_selfplay_match_tally: the games finished so far, by the player that was White and by result"""
@@ -198,8 +224,19 @@ class SelfPlay(_Handle):
         _check(self.L.sc_selfplay_get_noise(self.h, slot, _p(out), MAX_MOVES))
         return out[:n]
 
-    def set_position(self, slot, moves):
-        _check(self.L.sc_selfplay_set_position(self.h, slot, _p(_moves(moves)), len(moves)))
+    def set_position(self, slot, moves, fen=None):
+        """sc_selfplay_set_position(_from): the slot starts from `moves` played from the start position, or from `fen`: a FEN
+        string, or (scamd.fen.Positions, index) to share one validated set among many calls"""
+        if fen is None:
+            _check(self.L.sc_selfplay_set_position(self.h, slot, _p(_moves(moves)), len(moves)))
+            return
+        from .fen import Positions
+        pos, i = fen if isinstance(fen, tuple) else (Positions([fen], self.device), 0)
+        try:
+            _check(self.L.sc_selfplay_set_position_from(self.h, slot, pos.h, i, _p(_moves(moves)), len(moves)))
+        finally:
+            if not isinstance(fen, tuple):
+                pos.close()
 
 
 def enqueue_interleaved(handles, n_sims):
@@ -208,14 +245,24 @@ def enqueue_interleaved(handles, n_sims):
     _check(lib().sc_selfplay_enqueue_interleaved(arr, len(handles), n_sims))
 
 
-def search(engine, moves, rollout, cpuct=2.5, noise=False, seed=0):
-    """sc_search: one search from the position after `moves` -> (root_q, [(uci, N, Q, prior), ...])"""
+def search(engine, moves, rollout, cpuct=2.5, noise=False, seed=0, fen=None):
+    """sc_search(_from): one search from the position after `moves`, played from the start position or from `fen`
+    -> (root_q, [(uci, N, Q, prior), ...])"""
     mv = _moves(moves)
     cm, cn = np.zeros(MAX_MOVES, np.uint16), np.zeros(MAX_MOVES, np.int32)
     cq, cp = np.zeros(MAX_MOVES, np.float32), np.zeros(MAX_MOVES, np.float32)
     rq = C.c_float(0)
-    n = _count(lib().sc_search(engine.h, _p(mv), len(moves), rollout, cpuct, int(bool(noise)), seed, MAX_MOVES, _p(cm), _p(cn), _p(cq),
-                               _p(cp), C.byref(rq)))
+    if fen is None:
+        n = _count(lib().sc_search(engine.h, _p(mv), len(moves), rollout, cpuct, int(bool(noise)), seed, MAX_MOVES, _p(cm), _p(cn), _p(cq),
+                                   _p(cp), C.byref(rq)))
+    else:
+        from .fen import Positions
+        pos = Positions([fen], engine.device)
+        try:
+            n = _count(lib().sc_search_from(engine.h, pos.h, 0, _p(mv), len(moves), rollout, cpuct, int(bool(noise)), seed, MAX_MOVES,
+                                            _p(cm), _p(cn), _p(cq), _p(cp), C.byref(rq)))
+        finally:
+            pos.close()
     return rq.value, [(move_uci(cm[i]), int(cn[i]), float(cq[i]), float(cp[i])) for i in range(n)]
 
 
@@ -226,18 +273,35 @@ class Play:
     python-chess board object; the tree keeps only the current subtree (the reference also keeps the never revisited
     siblings of played moves), so `dump_search_tree()` shows the played line as a chain of single children."""
 
-    def __init__(self, engine, initial_moves=(), evaluator="net", seed=0):
+    def __init__(self, engine, initial_moves=(), fen=None, evaluator="net", seed=0):
+        """fen: the position `initial_moves` start from (a FEN string; None: the start position)"""
         self.engine = engine
         self.moves = [m if isinstance(m, str) else move_uci(m) for m in initial_moves]
         self._seed = seed
+        self._base = None
+        self._black_base = 0
+        if fen is not None:
+            from .fen import Positions
+            self._base = Positions([fen], engine.device if engine is not None else 0).check(for_search=True)
+            self.base_fen = self._base.fen(0)
+            self._black_base = int(self.base_fen.split()[1] == "b")
         # rollout_num is the per-ply budget of the self-play driver: huge here, plies advance only through step()
         self.sp = SelfPlay(engine, n_slots=1, n_games=1, rollout_num=60000, num_steps=4000, with_noise=False, outcome_gate=1 << 30,
                            evaluator=evaluator, seed=seed)
         self._rng = np.random.default_rng(seed)
-        self.sp.set_position(0, self.moves)
+        self._set_position()
+
+    def _set_position(self):
+        self.sp.set_position(0, self.moves, fen=None if self._base is None else (self._base, 0))
 
     def close(self):
         self.sp.close()
+        if self._base is not None:
+            self._base.close()
+
+    def fen(self):
+        """python-chess's Board.fen() of the current position (sc_selfplay_get_fen)"""
+        return self.sp.fen(0)
 
     def mcts(self, rollout, cpuct=2.5, noise=False):
         """chess_play_mcts: `rollout` more simulations on the current tree (epsilon 0.15 as lib.rs:243)"""
@@ -270,7 +334,7 @@ class Play:
     def apply_move(self, mov):
         """chess_play_apply_move: play `mov` and continue from a fresh node"""
         self.moves.append(mov if isinstance(mov, str) else move_uci(mov))
-        self.sp.set_position(0, self.moves)
+        self._set_position()
 
     def inspect(self):
         """chess_play_inspect -> (None, move stack newest first, q_value of the current node, [(move, N, Q), ...])"""
@@ -281,29 +345,31 @@ class Play:
 
     def dump_search_tree(self):
         """chess_play_dump_search_tree: nested dicts with serde's field names (src/mcts.rs:43-56: step, depth, q,
-        num_act, children); step = [uci or None, colour of the side to move at the node]"""
+        num_act, children); step = [uci or None, colour of the side to move at the node]; depth counts from the base, whose
+        side to move is the root's colour"""
         t = self.sp.tree(0)
         d0 = len(self.moves)
+        bb = self._black_base
 
         def node(i, depth, mv):
-            colour = "White" if depth % 2 == 0 else "Black"
+            colour = "White" if (depth + bb) % 2 == 0 else "Black"
             fc, nc = int(t["first_child"][i]), int(t["n_child"][i])
             kids = [node(fc + k, depth + 1, move_uci(t["move"][fc + k])) for k in range(nc)] if fc >= 0 else []
             return {"step": [mv, colour], "depth": depth, "q": float(t["q"][i]), "num_act": int(t["n"][i]), "children": kids}
         cur = node(0, d0, self.moves[-1] if self.moves else None) if t["n"].size else None
         for d in range(d0 - 1, -1, -1):   # the played line above the current node
-            cur = {"step": [self.moves[d - 1] if d > 0 else None, "White" if d % 2 == 0 else "Black"], "depth": d, "q": 0.0,
+            cur = {"step": [self.moves[d - 1] if d > 0 else None, "White" if (d + bb) % 2 == 0 else "Black"], "depth": d, "q": 0.0,
                    "num_act": 0, "children": [cur]}
         return cur
 
     def inference(self):
         """chess_play_inference -> (legal moves, priors, value) of the current position (Game::predict)"""
-        steps, pri, val = ChessHip(self.engine).predict(self.moves)
+        steps, pri, val = ChessHip(self.engine).predict(self.moves, fen=None if self._base is None else self.base_fen)
         return [move_uci(m) for m in steps], pri, val
 
     def encode(self):
         """chess_play_encode -> (boards int8[8,8,112], meta int32[7])"""
-        e = encode_positions([self.moves], engine=self.engine)
+        e = encode_positions([self.moves], engine=self.engine, fens=None if self._base is None else [self.base_fen])
         return e["boards"][0], e["meta"][0]
 
 
@@ -321,9 +387,15 @@ def opening_of_game(k, n_lines, colours):
     return ((k >> 1) if colours else k) % n_lines
 
 
+def _is_fen_line(ln):
+    """an opening line given as (fen, moves)"""
+    return isinstance(ln, tuple) and len(ln) == 2 and isinstance(ln[0], str) and "/" in ln[0] and not isinstance(ln[1], str)
+
+
 def read_openings(path):
     """An opening file -> list of lines (lists of UCI strings).  One line per opening: UCI moves separated by blanks; `#` starts
-    a comment (a line that holds nothing but a comment is skipped); an empty line is the start position."""
+    a comment (a line that holds nothing but a comment is skipped); an empty line is the start position.  A line whose first word
+    is `fen` is `fen <the 4 or 6 fields> [moves m1 m2 ...]`, the UCI `position` convention, and yields (fen, [uci, ...])."""
     import re
     lines = []
     with open(path) as f:
@@ -332,10 +404,21 @@ def read_openings(path):
             if "#" in raw and not text.strip():
                 continue
             toks = text.split()
+            fen = None
+            if toks and toks[0] == "fen":
+                cut = toks.index("moves") if "moves" in toks else len(toks)
+                fen, toks = " ".join(toks[1:cut]), toks[cut + 1:]
+                if len(fen.split()) not in (4, 6):
+                    raise ValueError(f"{path}:{no}: a FEN of 4 or 6 fields is expected behind 'fen'")
+                from .fen import parse_fen
+                try:
+                    parse_fen(fen)
+                except ValueError as e:
+                    raise ValueError(f"{path}:{no}: {e}") from None
             for t in toks:
                 if not re.fullmatch(r"[a-h][1-8][a-h][1-8][nbrq]?", t):
                     raise ValueError(f"{path}:{no}: '{t}' is not a UCI move")
-            lines.append(toks)
+            lines.append(toks if fen is None else (fen, toks))
     return lines
 
 

@@ -8,7 +8,7 @@ network may replace the one it came from.
 
 TRACE.json: the trace files this library writes (SelfPlay.write_trace / lib/sc-selfplay; the reference's format).  --games-csv: a
 game table with `moves` (SAN movetext) and `winner` columns, as the reference's py/validation/sample.csv (its ValidationDataset
-reads the first 10 rows: --limit 10); --pgn: a PGN file of games from the start position.  Those games are read on the GPU
+reads the first 10 rows: --limit 10); --pgn: a PGN file of games, from the start position or from a [FEN] header.  Those games are read on the GPU
 (scamd.san.encode_san_torch): every ply a position, the visit shares one-hot on the move played.  The sources add up.  Models are
 .scw blobs (tools/scw.py, tools/ckpt_to_scw.py); an SCW2 blob carries its own precision.  Prints the policy difference (total
 variation per position) and the value difference as mean / std / max / min, and with --losses the validation losses of each
@@ -27,7 +27,7 @@ def parser():
     ap.add_argument("-t", "--trace", type=str, nargs="+", action="extend")
     ap.add_argument("--games-csv", type=str, help="game table with `moves` (SAN) and `winner` columns")
     ap.add_argument("--limit", type=int, default=None, help="read only the first N rows of --games-csv")
-    ap.add_argument("--pgn", type=str, help="PGN file (games from the start position)")
+    ap.add_argument("--pgn", type=str, help="PGN file (games from the start position or from a [FEN] header)")
     ap.add_argument("--model1", required=True, type=str, help="[n_res_blocks:]path of an .scw blob")
     ap.add_argument("--model2", required=True, type=str)
     prec_help = "precision an SCW1 (fp32) blob is run in; ignored for an SCW2 blob, which is the fp8 export and says so itself"
@@ -70,12 +70,13 @@ def main(argv=None):
         if nb is not None and nb != eng_blocks(path):
             raise SystemExit(f"{path}: the blob holds {eng_blocks(path)} residual blocks, the model spec says {nb}")
     import scamd.san
-    san_games, san_winners = [], []
+    san_games, san_winners, san_fens = [], [], []
     if args.games_csv:
         san_games, san_winners = scamd.san.read_games_csv(args.games_csv, args.limit)
+        san_fens = [None] * len(san_games)
     if args.pgn:
-        g, w = scamd.san.read_pgn(args.pgn)
-        san_games, san_winners = san_games + g, san_winners + w
+        g, w, fens = scamd.san.read_pgn(args.pgn, setup=True)   # games from a [FEN] position are read too
+        san_games, san_winners, san_fens = san_games + g, san_winners + w, san_fens + fens
     engines = []
     try:
         for (nb, path), prec in zip(specs, (args.precision1, args.precision2)):
@@ -89,7 +90,7 @@ def main(argv=None):
                 raise SystemExit(f"traces that do not replay (sc_encode_steps status codes): {bad}")
             parts.append(t)
         if san_games:
-            t = scamd.san.encode_san_torch(san_games, san_winners, device=args.device, engine=engines[0])
+            t = scamd.san.encode_san_torch(san_games, san_winners, device=args.device, engine=engines[0], fens=san_fens)
             if (t["status"] != 0).any():
                 bad = [(g + 1, int(s)) for g, s in enumerate(t["status"]) if s]
                 raise SystemExit(f"games that do not parse (game number, sc_encode_san_device status code): {bad}")
