@@ -116,7 +116,9 @@ __device__ inline float u01_open(uint64_t& st) {
 // U^(1/0.3).  The draw happens for every child at EVERY simulation, on the critical path of the descent, so it uses
 // the hardware transcendentals (v_log / v_exp / v_cos / v_sqrt, ~1 ulp) instead of the correctly rounded library
 // routines (10x the instructions): the reference's noise comes from thread_rng, parity is distributional
-// (tests: test_root_noise_is_dirichlet).
+// (tests: test_root_noise_is_dirichlet for the marginal's moments; tests/test_gpu_noise.py holds every sample of both
+// builds to the float64 replay of tests/noise_ref.py, whose law tests/test_noise_ref.py checks -- measured there, the
+// four functions together stay inside the error bound of correctly rounded ones, 0.5 ulp each).
 __device__ inline float gamma03(uint64_t st) {
 #pragma clang fp contract(off)   // exact f32 like the reference, in either translation unit (top of this file)
     // raw hardware transcendentals only (v_log_f32 = log2, v_exp_f32 = 2^x): both units must draw the same noise (top of this file)
