@@ -283,6 +283,31 @@ int sc_encode_san_device_from(sc_engine* engine_or_null, int device_id, int n_ga
                               void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, uint16_t* moves,
                               int32_t* status);
 
+/* ------------------------------------------------------------------ moves written as SAN movetext and PGN */
+/* Moves -> SAN tokens on the device, the inverse of sc_encode_san_device: python-chess's Board.san() for every ply of a batch of
+ * games.  moves / move_off: host, as sc_encode_steps_device takes them (at most 4000 plies per game); tokens uint64 [P] and
+ * status int32 [n_games] are device pointers, both required; pointer checks, stream contract and scratch arena as
+ * sc_encode_steps_device.  One wavefront per ply renders its move against the generated legal moves of the position before it
+ * and takes the check mark from those of the position after it.
+ *   tokens[p]  sc_san_tokenize's format (character k in byte k, zero-padded) WITH the suffix: "Nbd2", "exd8=Q#", "O-O-O+", at most
+ *              7 characters.  Disambiguation is python-chess's: among the other LEGAL moves of a piece of the same kind to the same
+ *              square -- none: nothing; one on the origin's rank: the file letter; one on the origin's file: the rank digit;
+ *              neither: the file letter.  Pawns: the origin file when they capture (en passant included).  '+' check, '#' mate,
+ *              stalemate has no mark.
+ *   status[g]  0, or -(i+1): move i of the game is not legal there (the first such ply).  The game's tokens from ply i on are 0;
+ *              the other games of the call are not affected.
+ * n_games == 0 and games without plies are valid; nothing is written beyond tokens[P) and status[n_games).
+ * _from: a base per game as sc_encode_steps_device_from.  Returns 0, or < 0 as every entry point (-3: no HIP device). */
+int sc_moves_to_san_device(int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off, void* stream, uint64_t* tokens,
+                           int32_t* status);
+int sc_moves_to_san_device_from(int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx, const uint16_t* moves,
+                                const uint32_t* move_off, void* stream, uint64_t* tokens, int32_t* status);
+/* Tokens -> one line of movetext, on the host (no GPU is needed): "1. e4 e5 2. Nf3" from move number `fullmove`, or with
+ * black_first "12... Nf6 13. d4"; `result` (may be NULL) is appended as the last word; a token of 0 ends the moves.  Returns the
+ * length of the whole text and writes at most cap bytes with the final zero, like sc_positions_fen (cap 0: a length query, buf may
+ * be NULL); < 0: bad argument. */
+int sc_san_format(const uint64_t* tokens, uint32_t n, int fullmove, int black_first, const char* result, char* buf, size_t cap);
+
 /* ------------------------------------------------------------------ network on device tensors: forward, losses, agreement */
 /* sc_forward_batch on DEVICE pointers: boards int8 [n][8][8][112] and meta int32 [n][7] as layout 0 of sc_encode_steps_device
  * leaves them, logp float [n][4672] (may be NULL) and value float [n] in device memory of the engine's GPU.  The same kernels as
@@ -535,6 +560,17 @@ int sc_selfplay_encode_traces(sc_selfplay*, int n, const int32_t* games, int app
 /* Writes the reference's trace JSON (src/trace.rs:23-32; serde_json pretty, keys "outcome","steps").  A game that started from a
  * non-empty opening line (sc_selfplay_set_openings) gets a third key after "steps": "opening": ["e2e4", ...], the line's moves. */
 int sc_selfplay_write_trace_json(sc_selfplay*, int game, const char* path);
+
+/* Finished games as PGN, written (append = 0) or appended to `path`: one sc_moves_to_san_device_from call renders the batch.
+ * games[0..n): handle-local indices.  A game's moves are its opening line (sc_selfplay_get_opening) and the trace's played moves,
+ * from the line's base where it has one (sc_selfplay_get_opening_fen): then [SetUp "1"] and [FEN "..."] are written and the move
+ * numbers start at the base's.  Headers: Event, Round (the game id), White, Black (the names given, "?" for NULL; on a handle with
+ * sc_selfplay_set_match colours = 1 `white` names player a and the odd games carry the names exchanged), Result (* without an
+ * outcome, 1-0, 0-1, 1/2-1/2), Termination (the reference's enum name, with an outcome).  Movetext lines of at most 80 columns, the
+ * result at the end, a blank line behind every game.  Readiness as sc_selfplay_get_trace: returns 1 if a game has not finished,
+ * 2 if its row is gone (2 wins over 1); nothing is written then. */
+int sc_selfplay_write_pgn(sc_selfplay*, int n, const int32_t* games, const char* path, int append, const char* white, const char* black,
+                          const char* event);
 
 /* tests / NNPlayer::bestmove (src/play.rs:241-288) support: current search tree of a slot in
  * allocation order (root = 0; children of a node contiguous).  Arrays may be NULL; returns n_nodes. */

@@ -363,6 +363,11 @@ void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint3
     hipLaunchKernelGGL(sc::k_ply_keys, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen, d_ply_moves);
     hipLaunchKernelGGL(sc::k_ply_rep, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen);
 }
+void replay_walk(int n_games, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap, hipStream_t s,
+                 const sc::Position* d_bases, const int32_t* d_base_idx) {
+    if (n_games <= 0) return;
+    hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap, d_bases, d_base_idx);
+}
 void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
                   int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s) {
     if (n <= 0) return;

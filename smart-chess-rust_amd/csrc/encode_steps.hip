@@ -1,4 +1,5 @@
-// encode_steps.hip -- host side of libsc_engine.so: training tensors (sc_encode_steps, sc_encode_steps_device, sc_encode_san_device).
+// encode_steps.hip -- host side of libsc_engine.so: training tensors (sc_encode_steps, sc_encode_steps_device, sc_encode_san_device)
+// and, on the same walk and arena, moves written as SAN (sc_moves_to_san_device, sc_san_format).
 //
 // libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) for a batch of recorded games; see include/sc_engine.h.
 // One encoder, encode_device_core, writes device buffers on a stream.  sc_encode_steps_device / sc_selfplay_encode_traces hand
@@ -59,24 +60,16 @@ int check_device_outputs(const DevEncodeOut& o, int dev) {
                               {o.legal_idx, "legal_idx"}, {o.n_legal, "n_legal"}, {o.status, "status"}}, dev);
 }
 
-// ply_off: host, n_games + 1 (the plies of game g are [ply_off[g], ply_off[g+1])).  Host path: moves / child_mv / child_n /
-// child_off are host arrays as sc_encode_steps takes them; ring path (ring != nullptr): the moves and children are read from the
-// trace ring rows on the device; SAN path (san != nullptr): the moves are parsed on the device from the host's tokens (k_san_parse
-// also writes the games' status), every ply's children are its legal moves with count 1 on the move played, and the parsed moves
-// stay in the arena between the two halves: nothing comes back to the host.
-int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
-                       const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
-                       hipStream_t st, const SanSrc* san, const BaseSrc* base) {
-    const uint32_t P = ply_off[n_games];
-    // the game records of one group of games: (games in the group) x (longest game of the group + 2) <= REC_BUDGET, so one long
-    // game among many short ones does not size the buffer for all of them (80 B per record: 80 MiB)
+namespace {
+// the game records of one group of games: (games in the group) x (longest game of the group + 2) <= REC_BUDGET, so one long
+// game among many short ones does not size the buffer for all of them (80 B per record: 80 MiB)
+struct Group {
+    int g0, ng, hist_cap;
+};
+std::vector<Group> record_groups(int n_games, const uint32_t* ply_off, size_t* max_rec) {
     const size_t REC_BUDGET = (size_t)1 << 20;
-    const uint32_t CH = 32768;   // plies per launch of the per-ply kernels (bounds their legal-move / meta scratch: 15 MB)
-    struct Group {
-        int g0, ng, hist_cap;
-    };
     std::vector<Group> groups;
-    size_t max_rec = 1;
+    *max_rec = 1;
     for (int g0 = 0; g0 < n_games;) {
         uint32_t mx = ply_off[g0 + 1] - ply_off[g0];
         int g1 = g0 + 1;
@@ -87,9 +80,37 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
             g1++;
         }
         groups.push_back({g0, g1 - g0, (int)mx + 2});
-        max_rec = std::max(max_rec, (size_t)(g1 - g0) * (mx + 2));
+        *max_rec = std::max(*max_rec, (size_t)(g1 - g0) * (mx + 2));
         g0 = g1;
     }
+    return groups;
+}
+// the device's arena for a call that needs `bytes` on stream st (g_enc_mu held): grown if need be, ordered behind the previous call
+int arena_take(EncArena& A, size_t bytes, hipStream_t st) {
+    if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
+    if (bytes > A.buf.cap) {
+        // the previous call's work still reads the old arena
+        TRY(A.buf.grow(bytes, [&A] { return A.used ? hipEventSynchronize(A.ev) : hipSuccess; }));
+        A.used = false;
+    } else if (A.used) {
+        HIPOK(hipStreamWaitEvent(st, A.ev, 0));   // ... possibly on another stream
+    }
+    return 0;
+}
+}  // namespace
+
+// ply_off: host, n_games + 1 (the plies of game g are [ply_off[g], ply_off[g+1])).  Host path: moves / child_mv / child_n /
+// child_off are host arrays as sc_encode_steps takes them; ring path (ring != nullptr): the moves and children are read from the
+// trace ring rows on the device; SAN path (san != nullptr): the moves are parsed on the device from the host's tokens (k_san_parse
+// also writes the games' status), every ply's children are its legal moves with count 1 on the move played, and the parsed moves
+// stay in the arena between the two halves: nothing comes back to the host.
+int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
+                       const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
+                       hipStream_t st, const SanSrc* san, const BaseSrc* base) {
+    const uint32_t P = ply_off[n_games];
+    const uint32_t CH = 32768;   // plies per launch of the per-ply kernels (bounds their legal-move / meta scratch: 15 MB)
+    size_t max_rec = 1;
+    const std::vector<Group> groups = record_groups(n_games, ply_off, &max_rec);
     const bool has_ring = ring != nullptr, has_csr = !ring && !san;
     const uint32_t nchild = has_csr ? child_off[P] : 0;
     const uint32_t cap = std::max<uint32_t>(std::min(CH, P), 1);
@@ -117,14 +138,7 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
     L.add(&d_bidx, (size_t)n_games, base != nullptr);
     std::lock_guard<std::mutex> lk(g_enc_mu);
     EncArena& A = g_enc_arena[dev];
-    if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
-    if (L.bytes > A.buf.cap) {
-        // the previous call's work still reads the old arena
-        TRY(A.buf.grow(L.bytes, [&A] { return A.used ? hipEventSynchronize(A.ev) : hipSuccess; }));
-        A.used = false;
-    } else if (A.used) {
-        HIPOK(hipStreamWaitEvent(st, A.ev, 0));   // ... possibly on another stream
-    }
+    TRY(arena_take(A, L.bytes, st));
     ArenaRelease guard{A, st};
     guard.armed = true;
     L.bind(A.buf.p);
@@ -176,6 +190,50 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint
         }
     }
     if (!san) scl::status_final(n_games, o.status, st);
+    HIPOK(hipGetLastError());
+    return 0;
+}
+
+// The sibling of encode_device_core for sc_moves_to_san_device: the same arena, ordering and record-budget grouping; per group
+// the ply index and the walk alone (a move generation reads neither keys nor repetition flags), then one wavefront per ply
+// (k_san_write, san_write_kernels.hip).  The status keys are k_steps_dist's: filled with 0x7f, folded by atomic min, turned into
+// codes by k_status_final, with the tokens behind a game's first failing ply zeroed in between.
+static int san_write_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const BaseSrc* base, uint64_t* tokens,
+                          int32_t* status, hipStream_t st) {
+    const uint32_t P = ply_off[n_games];
+    size_t max_rec = 1;
+    const std::vector<Group> groups = record_groups(n_games, ply_off, &max_rec);
+    uint32_t *d_off, *d_hoff, *d_plen, *d_pgame;
+    uint16_t* d_moves;
+    sc::Position* d_hist;
+    int32_t* d_bidx;
+    ArenaLayout L;
+    L.add(&d_off, (size_t)n_games + 1);
+    L.add(&d_moves, (size_t)P);
+    L.add(&d_hoff, (size_t)P);
+    L.add(&d_plen, (size_t)P);
+    L.add(&d_pgame, (size_t)P);
+    L.add(&d_hist, max_rec);
+    L.add(&d_bidx, (size_t)n_games, base != nullptr);
+    std::lock_guard<std::mutex> lk(g_enc_mu);
+    EncArena& A = g_enc_arena[dev];
+    TRY(arena_take(A, L.bytes, st));
+    ArenaRelease guard{A, st};
+    guard.armed = true;
+    L.bind(A.buf.p);
+    HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
+    if (base) HIPOK(hipMemcpyAsync(d_bidx, base->idx, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
+    if (P) HIPOK(hipMemcpyAsync(d_moves, moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
+    HIPOK(hipMemsetAsync(status, 0x7f, (size_t)n_games * 4, st));   // sc::STATUS_NONE: no failing ply yet
+    for (const Group& gr : groups) {
+        const uint32_t p0 = ply_off[gr.g0], p1 = ply_off[gr.g0 + gr.ng];
+        if (p1 == p0) continue;
+        scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, nullptr, 0, nullptr, d_moves, nullptr, st);
+        scl::replay_walk(gr.ng, d_moves, d_off + gr.g0, d_hist, gr.hist_cap, st, base ? base->rec : nullptr, base ? d_bidx + gr.g0 : nullptr);
+        scl::san_write((int)(p1 - p0), d_hist, d_hoff + p0, d_plen + p0, d_pgame + p0, d_moves + p0, tokens + p0, status, st);
+    }
+    scl::san_clip((int)P, d_plen, d_pgame, status, tokens, st);
+    scl::status_final(n_games, status, st);
     HIPOK(hipGetLastError());
     return 0;
 }
@@ -250,12 +308,35 @@ int sc_encode_san_device_from(sc_engine* e, int device_id, int n_games, const sc
                               static_cast<hipStream_t>(stream), &san, base.rec ? &base : nullptr);
 }
 
+int sc_moves_to_san_device(int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off, void* stream, uint64_t* tokens,
+                           int32_t* status) {
+    return sc_moves_to_san_device_from(device_id, n_games, nullptr, nullptr, moves, move_off, stream, tokens, status);
+}
+
+int sc_moves_to_san_device_from(int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx, const uint16_t* moves,
+                                const uint32_t* move_off, void* stream, uint64_t* tokens, int32_t* status) {
+    if (n_games < 0 || !move_off || !status || !tokens) return fail("bad argument");
+    TRY(use_device(nullptr, device_id));
+    BaseSrc base{nullptr, base_idx};
+    TRY(positions_bases(bases, base_idx, n_games, device_id, false, "sc_moves_to_san_device_from", &base.rec));
+    TRY(check_device_ptrs({{tokens, "tokens"}, {status, "status"}}, device_id));
+    if (n_games == 0) return 0;
+    TRY(check_traces(n_games, move_off, nullptr));
+    if (move_off[n_games] && !moves) return fail("bad argument");
+    return san_write_core(device_id, n_games, move_off, moves, base.rec ? &base : nullptr, tokens, status, static_cast<hipStream_t>(stream));
+}
+
 int sc_san_tokenize(const char* text, size_t len, uint64_t* tokens, uint32_t cap, uint32_t* n_tokens) {
     if ((!text && len) || (!tokens && cap) || !n_tokens) return fail("bad argument");
     const size_t n = scsan::san_tokenize(text, len, tokens, cap);
     *n_tokens = (uint32_t)std::min<size_t>(n, UINT32_MAX);
     if (n > cap) return fail("sc_san_tokenize: " + std::to_string(n) + " tokens, room for " + std::to_string(cap), SC_ERR_CAPACITY);
     return 0;
+}
+
+int sc_san_format(const uint64_t* tokens, uint32_t n, int fullmove, int black_first, const char* result, char* buf, size_t cap) {
+    if ((!tokens && n) || (!buf && cap) || fullmove < 0) return fail("bad argument");
+    return (int)scsan::san_format(tokens, n, (unsigned)fullmove, black_first != 0, result, buf, cap);
 }
 
 namespace {

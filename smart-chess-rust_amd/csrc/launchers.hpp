@@ -38,6 +38,10 @@ void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, u
 void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
                   const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s,
                   const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);   // base of each game of the group, or null
+// the walk alone: boards, castling rights, ep squares and clocks of every ply (keys and flags stay 0), which is all a move
+// generation reads (sc_moves_to_san_device)
+void replay_walk(int n_games, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap, hipStream_t s,
+                 const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
 void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
                   int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s);
 void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
@@ -51,6 +55,11 @@ void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off,
                const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
 void san_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, int apply_mirror, const int32_t* meta_s,
               int layout, void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out, hipStream_t s);
+// san_write_kernels.hip: moves -> SAN tokens, one wavefront per ply of a walked group (sc_moves_to_san_device); d_status holds
+// k_steps_dist's keys (0x7f-filled, status_final behind it); san_clip zeroes a game's tokens from its first failing ply on
+void san_write(int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, const uint32_t* d_pgame,
+               const uint16_t* d_ply_moves, uint64_t* d_tokens, int32_t* d_status, hipStream_t s);
+void san_clip(int n, const uint32_t* d_plen, const uint32_t* d_pgame, const int32_t* d_status, uint64_t* d_tokens, hipStream_t s);
 // fen_kernels.hip: raw FEN fields -> validated records and their status (sc_positions_from_fen); the ep bit of Board.fen()
 void fen_positions(int n, const sc_fen_fields* d_fields, const int32_t* d_syntax, sc::Position* d_out, int32_t* d_status, hipStream_t s);
 void fen_ep_legal(int n, const sc::Position* d_rec, int32_t* d_ep_legal, hipStream_t s);

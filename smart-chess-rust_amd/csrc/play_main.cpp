@@ -20,6 +20,8 @@
 // but a comment is skipped); an empty line is the start position; a line whose first word is `fen` is
 // `fen <the 4 or 6 fields> [moves m1 m2 ...]` and starts from that position (sc_selfplay_set_openings_from).  The games then run on
 // recycled slots (--concurrency, default one slot per game).
+// --pgn FILE also writes the whole match as one PGN file (sc_selfplay_write_pgn: SAN rendered on the GPU), with --swap both colour
+// assignments in it; White and Black are named after their checkpoint files (net-seed<N> for a random network).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -33,9 +35,9 @@
 
 struct Args {
     std::string white_device, black_device = "<not-specified>", black_type = "stockfish";
-    std::string black_checkpoint = "<not-specified>", white_checkpoint = "<not-specified>", output = "01.json", swap_output, openings;
+    std::string black_checkpoint = "<not-specified>", white_checkpoint = "<not-specified>", output = "01.json", swap_output, openings, pgn;
     int rollout = 60, temperature_switch = 0, games = 1, blocks = 10, channels = 256, concurrency = 0;
-    bool swap = false;
+    bool swap = false, has_pgn = false;
     float temperature = 0.0f, cpuct = 0.0f;
     unsigned long long seed = 0xC0FFEEULL, white_seed = 1, black_seed = 2;
 };
@@ -45,7 +47,7 @@ static void usage() {
             "usage: sc-play --white-device cuda -w|--white-checkpoint W.scw [--black-device cuda] [--black-type nn]\n"
             "               [--black-checkpoint B.scw] [-r|--rollout 60] [--temperature 0] [--temperature-switch 0] [--cpuct 0]\n"
             "               [-o|--output 01.json] [--games 1] [--seed S] [--blocks 10] [--channels 256] [--white-seed 1] [--black-seed 2]\n"
-            "               [--concurrency SLOTS] [--swap --swap-output b_01.json] [--openings FILE]\n");
+            "               [--concurrency SLOTS] [--swap --swap-output b_01.json] [--openings FILE] [--pgn FILE]\n");
 }
 
 static bool parse(int argc, char** argv, Args& a) {
@@ -82,6 +84,7 @@ static bool parse(int argc, char** argv, Args& a) {
         else if (k == "--swap" && !has) a.swap = true;
         else if (k == "--swap-output") a.swap_output = val();
         else if (k == "--openings") a.openings = val();
+        else if (k == "--pgn") { a.pgn = val(); a.has_pgn = true; }
         else if (k == "--seed") a.seed = strtoull(val(), nullptr, 0);
         else if (k == "--blocks") a.blocks = atoi(val());
         else if (k == "--channels") a.channels = atoi(val());
@@ -164,6 +167,13 @@ static bool read_openings(const std::string& path, std::vector<uint16_t>& moves,
     return true;
 }
 
+// a player's name in the PGN: its checkpoint's file name, or net-seed<N> for a random network
+static std::string player_name(const std::string& checkpoint, unsigned long long seed) {
+    if (checkpoint == "<not-specified>") return "net-seed" + std::to_string(seed);
+    const size_t slash = checkpoint.find_last_of('/');
+    return slash == std::string::npos ? checkpoint : checkpoint.substr(slash + 1);
+}
+
 static std::string out_name(const Args& a, const std::string& pattern, int game_number) {
     std::string t = pattern;
     size_t p = t.find("{}");
@@ -204,6 +214,11 @@ int main(int argc, char** argv) {
     if (!a.openings.empty() && !read_openings(a.openings, op_moves, op_off, op_line_no, op_fens)) return 2;
     if (a.swap == a.swap_output.empty()) {
         fprintf(stderr, "--swap and --swap-output go together\n");
+        return 2;
+    }
+    if (a.has_pgn && (a.pgn.empty() || a.pgn[0] == '-')) {
+        fprintf(stderr, "--pgn needs a file name\n");
+        usage();
         return 2;
     }
     if (recycle && a.concurrency < 0) {
@@ -265,9 +280,11 @@ int main(int argc, char** argv) {
     }
     // [0]: the games with --white-checkpoint's network as White, [1] (--swap): as Black; White won / Black won / draw / no outcome
     long long res[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    std::vector<int32_t> finished;
     for (int g = 0; g < total; g++) {
         sc_trace_info info{};
         if (sc_selfplay_get_trace(sp, g, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) continue;
+        finished.push_back(g);
         const int set = a.swap ? (int)(info.game_id & 1) : 0;
         res[set][!info.has_outcome ? 3 : info.winner == 1 ? 0 : info.winner == 0 ? 1 : 2]++;
         const int number = (int)(a.swap ? info.game_id / 2 : info.game_id) + 1;
@@ -276,6 +293,12 @@ int main(int argc, char** argv) {
             fprintf(stderr, "%s\n", sc_last_error());
             rc = 1;
         }
+    }
+    if (a.has_pgn && sc_selfplay_write_pgn(sp, (int)finished.size(), finished.data(), a.pgn.c_str(), 0,
+                                           player_name(a.white_checkpoint, a.white_seed).c_str(),
+                                           player_name(a.black_checkpoint, a.black_seed).c_str(), "sc-play match")) {
+        fprintf(stderr, "%s\n", sc_last_error());
+        rc = 1;
     }
     if (!recycle) {
         // Total/WhiteWin/BlackWin is the input format of scripts/elo.py

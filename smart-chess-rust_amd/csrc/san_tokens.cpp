@@ -1,5 +1,6 @@
-// san_tokens.cpp -- the host tokenizer of SAN movetext (san_tokens.hpp).  Every read is bounded by `len`: the text need not be
-// zero-terminated, and a text cut off anywhere (inside a comment, a variation, a tag, a token) ends the game there.
+// san_tokens.cpp -- the host tokenizer of SAN movetext and its inverse, the formatter (san_tokens.hpp).  Every read of the
+// tokenizer is bounded by `len`: the text need not be zero-terminated, and a text cut off anywhere (inside a comment, a variation,
+// a tag, a token) ends the game there.  Every write of the formatter is bounded by `cap`.
 #include "san_tokens.hpp"
 
 namespace scsan {
@@ -104,6 +105,43 @@ size_t san_tokenize(const char* t, size_t len, uint64_t* tokens, size_t cap) {
         }
     }
     return n;
+}
+
+size_t san_format(const uint64_t* tokens, size_t n, unsigned fullmove, bool black_first, const char* result, char* buf, size_t cap) {
+    size_t len = 0;
+    auto put = [&](char c) {
+        if (len + 1 < cap) buf[len] = c;   // (the last byte is the final zero's)
+        len++;
+    };
+    bool black = black_first;
+    for (size_t i = 0; i < n && tokens[i]; i++) {
+        if (len) put(' ');
+        if (!black || i == 0) {
+            char d[12];
+            int k = 0;
+            for (unsigned v = fullmove; k == 0 || v; v /= 10) d[k++] = (char)('0' + v % 10);
+            while (k) put(d[--k]);
+            put('.');
+            if (black) {
+                put('.');
+                put('.');
+            }
+            put(' ');
+        }
+        for (int b = 0; b < 8; b++) {
+            const char c = (char)((tokens[i] >> (8 * b)) & 0xff);
+            if (!c) break;
+            put(c);
+        }
+        if (black) fullmove++;
+        black = !black;
+    }
+    if (result && *result) {
+        if (len) put(' ');
+        for (; *result; result++) put(*result);
+    }
+    if (cap) buf[len < cap ? len : cap - 1] = 0;
+    return len;
 }
 
 }  // namespace scsan

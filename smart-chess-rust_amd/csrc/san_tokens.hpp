@@ -15,4 +15,10 @@ constexpr uint64_t TOKEN_RESERVED = ~0ULL;   // "a half-move stands here, but no
 // of + # ! ? is stripped.  Anything else of more than 7 characters, and a stray closing bracket, becomes TOKEN_RESERVED.
 size_t san_tokenize(const char* text, size_t len, uint64_t* tokens, size_t cap);
 
+// Tokens -> one line of movetext (sc_san_format): "1. e4 e5 2. Nf3", or with black_first "12... Nf6 13. d4"; a token's
+// characters are written as they are (the writer's tokens carry their + / #), a token of 0 ends the text, `result` (or null) is
+// appended as a last word.  Returns the length of the whole text; writes at most cap bytes, the final zero among them (cap 0:
+// nothing, buf may be null).
+size_t san_format(const uint64_t* tokens, size_t n, unsigned fullmove, bool black_first, const char* result, char* buf, size_t cap);
+
 }  // namespace scsan

@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "host_common.hpp"
+#include "san_tokens.hpp"
 #include "trace_json.hpp"
 
 // A row that sc_selfplay_poll has reported and holds (trace_hold) is final, and no kernel writes it until the next poll releases it
@@ -16,6 +17,36 @@ static RowState row_state(const sc_selfplay* sp, int row, uint64_t want_id, cons
     if (h.state == sc::TR_FREE) return sp->reported[(size_t)row] > want_id ? ROW_GONE : ROW_NOT_FINISHED;
     if (h.game_id > want_id) return ROW_GONE;
     return h.game_id < want_id || h.state != sc::TR_DONE ? ROW_NOT_FINISHED : ROW_READY;
+}
+
+// a PGN tag pair; quotes and backslashes of the value escaped
+static std::string pgn_tag(const char* name, const std::string& value) {
+    std::string o = std::string("[") + name + " \"";
+    for (char c : value) {
+        if (c == '"' || c == '\\') o += '\\';
+        o += c;
+    }
+    return o + "\"]\n";
+}
+// one line of movetext -> lines of at most 80 columns, broken at blanks
+static std::string pgn_wrap(const std::string& text) {
+    std::string o;
+    size_t col = 0;
+    for (size_t i = 0; i < text.size();) {
+        size_t e = text.find(' ', i);
+        if (e == std::string::npos) e = text.size();
+        if (col && col + 1 + (e - i) > 80) {
+            o += '\n';
+            col = 0;
+        } else if (col) {
+            o += ' ';
+            col++;
+        }
+        o.append(text, i, e - i);
+        col += e - i;
+        i = e + 1;
+    }
+    return o + "\n";
 }
 
 extern "C" {
@@ -190,6 +221,93 @@ int sc_selfplay_write_trace_json(sc_selfplay* sp, int game, const char* path) {
     const size_t w = fwrite(js.data(), 1, js.size(), f);
     fclose(f);
     if (w != js.size()) return fail("short write");
+    return 0;
+}
+
+// Finished games as PGN: moves = opening line + played moves, rendered by one sc_moves_to_san_device_from call for the batch
+int sc_selfplay_write_pgn(sc_selfplay* sp, int n, const int32_t* games, const char* path, int append, const char* white, const char* black,
+                          const char* event) {
+    if (!sp || n < 0 || (n > 0 && !games) || !path) return fail("bad argument");
+    std::vector<sc_trace_info> info((size_t)std::max(n, 1));
+    std::vector<uint16_t> moves;
+    std::vector<uint32_t> off(1, 0);
+    std::vector<int32_t> base_idx((size_t)std::max(n, 1), -1);
+    std::vector<const char*> fens;
+    int pending = 0;
+    for (int i = 0; i < n; i++) {   // readiness of every game first (2 wins over 1, as sc_selfplay_encode_traces): nothing is written then
+        const int rc = sc_selfplay_get_trace(sp, games[i], &info[(size_t)i], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (rc < 0 || rc == 2) return rc;
+        pending |= rc;
+    }
+    if (pending) return fail("game not finished", 1);
+    for (int i = 0; i < n; i++) {
+        const uint16_t* line = nullptr;
+        const int len = sp_opening(sp, games[i], &line);
+        moves.insert(moves.end(), line, line + len);
+        const size_t at = moves.size();
+        moves.resize(at + (size_t)info[(size_t)i].n_steps + 1);
+        TRY(sc_selfplay_get_trace(sp, games[i], &info[(size_t)i], moves.data() + at, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        moves.resize(at + (size_t)info[(size_t)i].n_steps);
+        off.push_back((uint32_t)moves.size());
+        if (const char* fen = sp_opening_fen(sp, games[i])) {
+            base_idx[(size_t)i] = (int32_t)fens.size();
+            fens.push_back(fen);
+        }
+    }
+    const uint32_t P = off.back();
+    std::vector<uint64_t> tok((size_t)P + 1);
+    std::vector<int32_t> status((size_t)std::max(n, 1), 0);
+    if (n > 0) {
+        struct Bases {
+            sc_positions* h = nullptr;
+            ~Bases() { sc_positions_destroy(h); }
+        } bases;
+        if (!fens.empty()) TRY(sc_positions_from_fen(sp->device, (int)fens.size(), fens.data(), &bases.h, nullptr));
+        ScopedDev<uint64_t> d_tok;
+        ScopedDev<int32_t> d_status;
+        HIPOK(d_tok.alloc(P));
+        HIPOK(d_status.alloc((size_t)n));
+        moves.push_back(0);   // (never an empty array)
+        // on the NULL stream, like the copies of sc_selfplay_get_trace: held rows are written while the handle's stream works on
+        TRY(sc_moves_to_san_device_from(sp->device, n, bases.h, base_idx.data(), moves.data(), off.data(), nullptr, d_tok.p, d_status.p));
+        HIPOK(hipStreamSynchronize(nullptr));
+        if (P) HIPOK(hipMemcpy(tok.data(), d_tok.p, (size_t)P * 8, hipMemcpyDeviceToHost));
+        HIPOK(hipMemcpy(status.data(), d_status.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    std::string text;
+    for (int i = 0; i < n; i++) {
+        const sc_trace_info& t = info[(size_t)i];
+        if (status[(size_t)i]) return fail("write_pgn: game " + std::to_string(games[i]) + ": move " + std::to_string(-status[(size_t)i] - 1) + " is not legal");
+        const bool swapped = sp->p.match_colours && (games[i] & 1);   // the White of game k is player k & 1 (sc_selfplay_set_match)
+        const char* result = !t.has_outcome ? "*" : t.winner == 1 ? "1-0" : t.winner == 0 ? "0-1" : "1/2-1/2";
+        text += pgn_tag("Event", event ? event : "?");
+        text += pgn_tag("Round", std::to_string(t.game_id));
+        text += pgn_tag("White", (swapped ? black : white) ? (swapped ? black : white) : "?");
+        text += pgn_tag("Black", (swapped ? white : black) ? (swapped ? white : black) : "?");
+        text += pgn_tag("Result", result);
+        if (t.has_outcome) text += pgn_tag("Termination", sctrace::TERMINATION_NAMES[t.termination >= 0 && t.termination <= 10 ? t.termination : 0]);
+        int fullmove = 1, black_first = 0;
+        if (base_idx[(size_t)i] >= 0) {
+            const char* fen = fens[(size_t)base_idx[(size_t)i]];
+            sc_fen_fields ff;
+            TRY(sc_fen_parse(fen, strlen(fen), &ff));
+            fullmove = ff.fullmove;
+            black_first = ff.turn == 0;
+            text += pgn_tag("SetUp", "1");
+            text += pgn_tag("FEN", fen);
+        }
+        const uint64_t* tk = tok.data() + off[(size_t)i];
+        const uint32_t nt = off[(size_t)i + 1] - off[(size_t)i];
+        std::string mt(scsan::san_format(tk, nt, (unsigned)fullmove, black_first != 0, result, nullptr, 0) + 1, '\0');
+        scsan::san_format(tk, nt, (unsigned)fullmove, black_first != 0, result, &mt[0], mt.size());
+        mt.pop_back();
+        text += "\n" + pgn_wrap(mt) + "\n";
+    }
+    FILE* f = fopen(path, append ? "ab" : "wb");
+    if (!f) return fail(std::string("cannot open ") + path);
+    const size_t w = fwrite(text.data(), 1, text.size(), f);
+    fclose(f);
+    if (w != text.size()) return fail("short write");
     return 0;
 }
 

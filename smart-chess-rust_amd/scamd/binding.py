@@ -105,6 +105,7 @@ ABI = {
     "sc_selfplay_launches_per_step": (_i, [_vp]),
     "sc_selfplay_get_trace": (_i, [_vp, _i, C.POINTER(TraceInfo), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_selfplay_write_trace_json": (_i, [_vp, _i, C.c_char_p]),
+    "sc_selfplay_write_pgn": (_i, [_vp, _i, _vp, C.c_char_p, _i, C.c_char_p, C.c_char_p, C.c_char_p]),
     "sc_selfplay_get_tree": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_selfplay_get_slot": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_selfplay_set_noise": (_i, [_vp, _i, _vp, _i]),
@@ -115,6 +116,9 @@ ABI = {
     "sc_encode_steps_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_san_tokenize": (_i, [C.c_char_p, C.c_size_t, _vp, C.c_uint32, _vp]),
     "sc_encode_san_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_moves_to_san_device": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sc_moves_to_san_device_from": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_san_format": (_i, [_vp, C.c_uint32, _i, _i, C.c_char_p, C.c_char_p, C.c_size_t]),
     "sc_selfplay_encode_traces": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_forward_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sc_score_positions": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

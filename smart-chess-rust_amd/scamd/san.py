@@ -1,13 +1,14 @@
 """Games written as SAN movetext (PGN files, the reference's py/validation/sample.csv) -> moves and training tensors on the GPU
 (csrc/san_tokens.cpp, csrc/san_kernels.hip, sc_encode_san_device): the reference's ValidationDataset (py/dataset.py:90-128)
-without python-chess.  The rules exist on the GPU only, so SAN is resolved there, against the generated legal moves."""
+without python-chess.  The rules exist on the GPU only, so SAN is resolved there, against the generated legal moves.
+The other direction too: moves -> SAN on the GPU (csrc/san_write_kernels.hip, sc_moves_to_san_device), movetext and PGN files."""
 import csv
 import ctypes as C
 import re
 
 import numpy as np
 
-from .binding import _check, _p, _stream, _torch, _tp, lib
+from .binding import _check, _count, _moves, _p, _stream, _torch, _tp, lib
 from .training import _device_outputs, _finish_outputs
 
 TOKEN_RESERVED = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -151,3 +152,106 @@ def parse_pgn(src, setup=False):
 def _open_comment(movetext):
     """is a {...} comment still open at the end of this movetext? (a tag-like line inside a comment is comment text)"""
     return movetext.rfind("{") > movetext.rfind("}")
+
+
+def moves_to_san(games, fens=None, device=0):
+    """Move lists (UCI strings or move ints) -> (list of lists of SAN strings, status int32 [n]) on the GPU, on torch's current
+    stream (sc_moves_to_san_device): python-chess's Board.san() of every ply, check and mate marks included.  status[g]: 0, or
+    -(i+1): move i of game g is not legal; that game's list ends in front of it.  fens: per game the position it starts from (FEN
+    strings, None for the start position) or a scamd.fen.Positions."""
+    from .fen import bases_of
+    torch = _torch()
+    L = lib()
+    games = [list(g) for g in games]
+    n = len(games)
+    off = np.zeros(n + 1, np.uint32)
+    off[1:] = np.cumsum([len(g) for g in games])
+    P = int(off[n])
+    flat = _moves([m for g in games for m in g])
+    tdev = torch.device("cuda", device)
+    tok = torch.zeros(max(P, 1), dtype=torch.int64, device=tdev)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=tdev)
+    pos, bidx, owned = bases_of(fens, n, device)
+    try:
+        if pos is None:
+            _check(L.sc_moves_to_san_device(device, n, _p(flat), _p(off), _stream(torch, device), _tp(tok), _tp(status)))
+        else:
+            _check(L.sc_moves_to_san_device_from(device, n, pos.h, _p(bidx), _p(flat), _p(off), _stream(torch, device), _tp(tok), _tp(status)))
+        words = tok.cpu().numpy().view(np.uint64)   # (waits for the stream: the set's records have been read)
+        st = status.cpu().numpy()[:n].copy()
+    finally:
+        if owned:
+            pos.close()
+    sans = []
+    for g in range(n):
+        row = []
+        for t in words[off[g]:off[g + 1]]:
+            if not t:
+                break
+            row.append(token_text(t))
+        sans.append(row)
+    return sans, st
+
+
+def _as_tokens(tokens_or_sans):
+    if isinstance(tokens_or_sans, np.ndarray):
+        return np.ascontiguousarray(tokens_or_sans, np.uint64)
+    out = np.zeros(len(tokens_or_sans), np.uint64)
+    for i, w in enumerate(tokens_or_sans):
+        raw = w.encode("latin-1") if isinstance(w, str) else int(w).to_bytes(8, "little")
+        if len(raw) > 8:
+            raise ValueError(f"{w!r} does not fit a token")
+        out[i] = int.from_bytes(raw, "little")
+    return out
+
+
+def movetext(tokens_or_sans, fullmove=1, black_first=False, result=None):
+    """SAN strings or tokens -> one line of movetext (sc_san_format; no GPU needed): "1. e4 e5 2. Nf3", with black_first
+    "12... Nf6 13. d4"; result is appended as the last word; a token of 0 ends the moves."""
+    L = lib()
+    tok = _as_tokens(tokens_or_sans)
+    res = None if result is None else result.encode()
+    need = _count(L.sc_san_format(_p(tok) if tok.size else None, tok.size, int(fullmove), int(bool(black_first)), res, None, 0))
+    buf = C.create_string_buffer(need + 1)
+    _count(L.sc_san_format(_p(tok) if tok.size else None, tok.size, int(fullmove), int(bool(black_first)), res, buf, need + 1))
+    return buf.value.decode("latin-1")
+
+
+def wrap_movetext(text, width=80):
+    """one line of movetext -> lines of at most `width` columns, broken at blanks"""
+    lines, cur = [], ""
+    for w in text.split(" "):
+        if cur and len(cur) + 1 + len(w) > width:
+            lines.append(cur)
+            cur = w
+        else:
+            cur = cur + " " + w if cur else w
+    return "\n".join(lines + [cur])
+
+
+def _tag(name, value):
+    return '[%s "%s"]\n' % (name, str(value).replace("\\", "\\\\").replace('"', '\\"'))
+
+
+def write_pgn(path, games, results=None, headers=None, fens=None, append=False):
+    """Games as lists of SAN strings (moves_to_san's) or token arrays -> a PGN file (no GPU needed).  results: per game "1-0" /
+    "0-1" / "1/2-1/2" / None (written as *); headers: one dict for every game or a list of dicts (Event, Round, White, Black ...;
+    Round defaults to the game's number); fens: per game the FEN it starts from or None: [SetUp "1"] and [FEN] are written and the
+    move numbers follow the FEN.  Movetext lines of at most 80 columns, a blank line behind every game."""
+    from .fen import parse_fen
+    out = []
+    for k, g in enumerate(games):
+        h = dict((headers[k] if isinstance(headers, (list, tuple)) else headers) or {})
+        res = (results[k] if results is not None else None) or "*"
+        fen = fens[k] if fens is not None else None
+        tags = {"Event": h.pop("Event", "?"), "Round": h.pop("Round", k + 1), "White": h.pop("White", "?"), "Black": h.pop("Black", "?"),
+                "Result": res}
+        tags.update(h)
+        fullmove, black_first = 1, False
+        if fen is not None:
+            f = parse_fen(fen)
+            fullmove, black_first = f.fullmove, f.turn == 0
+            tags["SetUp"], tags["FEN"] = "1", fen
+        out.append("".join(_tag(a, b) for a, b in tags.items()) + "\n" + wrap_movetext(movetext(g, fullmove, black_first, res)) + "\n\n")
+    with open(path, "a" if append else "w", encoding="latin-1", newline="\n") as f:
+        f.write("".join(out))

@@ -173,6 +173,13 @@ class SelfPlay(_Handle):
     def write_trace(self, game, path):
         _check(self.L.sc_selfplay_write_trace_json(self.h, game, path.encode()))
 
+    def write_pgn(self, games, path, append=False, white=None, black=None, event=None):
+        """finished games (handle-local indices) as PGN, rendered on the GPU in one call (sc_selfplay_write_pgn)"""
+        games = list(games)
+        g = np.asarray(games or [0], np.int32)
+        names = [None if x is None else x.encode() for x in (white, black, event)]
+        _check(self.L.sc_selfplay_write_pgn(self.h, len(games), _p(g), path.encode(), int(bool(append)), *names))
+
     def stream_traces(self, path_of, chunk=None):
         """The loop of lib/sc-selfplay (src/main.rs:235-238 writes each game's file when it ends): plays every game of the
         handle and writes `path_of(game_id)` as games finish, from a handle created with a trace ring and trace_hold=True.
