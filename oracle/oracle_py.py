@@ -187,6 +187,8 @@ class State:
     def push(self, m):
         if isinstance(m, str):
             m = from_uci(m)
+        if self.L.orc_ply(self.h) >= MAX_PLY:   # orc_state.stack has MAX_PLY records and orc_push does not check
+            raise OverflowError("oracle State: more than %d plies" % MAX_PLY)
         self.L.orc_push(self.h, m)
 
     def pop(self):

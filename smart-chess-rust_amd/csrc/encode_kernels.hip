@@ -6,37 +6,25 @@
 
 namespace sc {
 // ------------------------------------------------------------------ sc_encode_positions
-// One wave per position: replay the move list from the start position, or from record base_idx[g] of `bases` where that is
-// given (bases != nullptr and base_idx[g] >= 0: a validated record of fen_kernels.hip), validating every move
+// One wave per position: replay the move list from the position's start (chain_start), validating every move
 // against the legal-move generator, then produce the NN input, the legal moves + action indices
 // and outcome(claim_draw=True).  hist scratch: [n][hist_cap] Positions.
-// move_len (optional): position g replays moves[move_off[g] .. move_off[g] + move_len[g]) -- prefixes of one game
-// share their start (used by the training-tensor encoder: one position per ply).
-__global__ __launch_bounds__(64) void k_encode_positions(int n_pos, const uint16_t* moves, const uint32_t* move_off,
-                                                         const uint32_t* move_len, Position* hist_all, int hist_cap, int8_t* boards, int32_t* meta,
-                                                         uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
-                                                         int32_t* outcome, const Position* bases, const int32_t* base_idx) {
+__global__ __launch_bounds__(64) void k_encode_positions(GameWalk w, PlyRows rows, int32_t* outcome) {
     const int g = blockIdx.x, lane = threadIdx.x;
-    if (g >= n_pos) return;
+    if (g >= w.n_games) return;
+    int8_t* boards = static_cast<int8_t*>(rows.boards);
     __shared__ __attribute__((aligned(16))) int8_t s_stage[7168];
     __shared__ move_t s_moves[MAXC];
     __shared__ Position s_np;
-    Position* hist = hist_all + (size_t)g * hist_cap;
-    const uint16_t* mv = moves + move_off[g];
-    int nm = move_len ? (int)move_len[g] : (int)(move_off[g + 1] - move_off[g]);
-    Position cur;
-    const int bi = bases ? uniform(base_idx[g]) : -1;
-    if (bi >= 0) {
-        cur = uniform(bases[bi]);   // (its key is set, its flags are clear)
-    } else {
-        set_startpos(cur);
-        cur.key = position_key(cur);
-    }
+    Position* hist = w.hist + (size_t)g * w.hist_cap;
+    const uint16_t* mv = w.moves + w.move_off[g];
+    const int nm = (int)(w.move_off[g + 1] - w.move_off[g]);
+    Position cur = chain_start(w.bases, g, true);
     if (lane == 0) hist[0] = cur;
     __syncthreads();
     int status = 0;
     int played = 0;
-    for (int i = 0; i < nm && i + 1 < hist_cap; i++) {
+    for (int i = 0; i < nm && i + 1 < w.hist_cap; i++) {
         int nlm = 0;
         gen_legal_wave(cur, s_moves, lane, nlm);
         __syncthreads();
@@ -55,11 +43,11 @@ __global__ __launch_bounds__(64) void k_encode_positions(int n_pos, const uint16
     int n = 0;
     bool in_check = gen_legal_wave(cur, s_moves, lane, n);
     __syncthreads();
-    if (legal_mv)
-        for (int i = lane; i < n; i += 64) legal_mv[(size_t)g * MAXC + i] = s_moves[i];
-    if (legal_idx)
-        for (int i = lane; i < n; i += 64) legal_idx[(size_t)g * MAXC + i] = (uint16_t)move_index(s_moves[i], cur.turn);
-    if (n_legal && lane == 0) n_legal[g] = n;
+    if (rows.legal_mv)
+        for (int i = lane; i < n; i += 64) rows.legal_mv[(size_t)g * MAXC + i] = s_moves[i];
+    if (rows.legal_idx)
+        for (int i = lane; i < n; i += 64) rows.legal_idx[(size_t)g * MAXC + i] = (uint16_t)move_index(s_moves[i], cur.turn);
+    if (rows.n_legal && lane == 0) rows.n_legal[g] = n;
     if (boards) {
         __shared__ int32_t s_meta[8];
         __shared__ Position s_hist[8];
@@ -67,11 +55,11 @@ __global__ __launch_bounds__(64) void k_encode_positions(int n_pos, const uint16
         __syncthreads();
         encode_wave(s_hist, played < 7 ? played + 1 : 8, lane, s_stage, boards + (size_t)g * 7168, s_meta);
         __syncthreads();
-        if (meta && lane < 7) meta[(size_t)g * 7 + lane] = s_meta[lane];
-    } else if (meta && lane == 0) {
+        if (rows.meta && lane < 7) rows.meta[(size_t)g * 7 + lane] = s_meta[lane];
+    } else if (rows.meta && lane == 0) {
         int32_t m[7];
         encode_meta(cur, m);
-        for (int k = 0; k < 7; k++) meta[(size_t)g * 7 + k] = m[k];
+        for (int k = 0; k < 7; k++) rows.meta[(size_t)g * 7 + k] = m[k];
     }
     if (outcome) {
         int winner = -1;
@@ -94,24 +82,18 @@ __global__ __launch_bounds__(64) void k_encode_positions(int n_pos, const uint16
 // safely -- no piece of the mover on the from-square, an own piece on the target, a promotion code outside {0, N, B, R, Q}
 // or on a non-pawn -- and leaves the position unchanged for those (the ply is then reported as illegal by the per-ply check,
 // and the game's later plies are unspecified, include/sc_engine.h).
-__global__ __launch_bounds__(64) void k_replay_raw(int n_games, const uint16_t* moves, const uint32_t* move_off, Position* hist_all,
-                                                   int hist_cap, const Position* bases, const int32_t* base_idx) {
+__global__ __launch_bounds__(64) void k_replay_raw(GameWalk w) {
     // the only sequential part: one wave per game, board updates only (make_move_board: ~10 % of what a full make_move + repetition
     // scan per ply cost when this kernel did everything -- 1.9 us per ply, 194 us for 100-ply games)
     const int g = blockIdx.x, lane = threadIdx.x;
-    if (g >= n_games) return;
-    Position* hist = hist_all + (size_t)g * hist_cap;
-    const uint16_t* mv = moves + move_off[g];
-    const int nm = (int)(move_off[g + 1] - move_off[g]);
-    Position cur;
-    const int bi = bases ? uniform(base_idx[g]) : -1;   // the game's base record (fen_kernels.hip), else the start position
-    if (bi >= 0) cur = uniform(bases[bi]);
-    else set_startpos(cur);
-    cur.key = 0;
-    cur.flags = 0;
+    if (g >= w.n_games) return;
+    Position* hist = w.hist + (size_t)g * w.hist_cap;
+    const uint16_t* mv = w.moves + w.move_off[g];
+    const int nm = (int)(w.move_off[g + 1] - w.move_off[g]);
+    Position cur = chain_start(w.bases, g, false);
     if (lane == 0) hist[0] = cur;
     int mv64 = 0;   // the next 64 moves of the game, one per lane: one load per 64 plies instead of a dependent load per ply
-    for (int i = 0; i < nm && i + 1 < hist_cap; i++) {
+    for (int i = 0; i < nm && i + 1 < w.hist_cap; i++) {
         if ((i & 63) == 0) mv64 = (i + lane < nm) ? (int)mv[i + lane] : 0;
         const move_t m = (move_t)__builtin_amdgcn_readlane(mv64, i & 63);
         const int from = mv_from(m), to = mv_to(m), promo = mv_promo(m);
@@ -124,11 +106,11 @@ __global__ __launch_bounds__(64) void k_replay_raw(int n_games, const uint16_t* 
 
 // one wave per ply, after k_replay_raw: the record's key, and F_IRREV of the move that led to it (python-chess is_irreversible on
 // the position before: zeroing, castling rights reduced, or a legal en-passant capture was available)
-__global__ __launch_bounds__(64) void k_ply_keys(int n, Position* hist_all, const uint32_t* hoff, const uint32_t* plen, const uint16_t* ply_move) {
+__global__ __launch_bounds__(64) void k_ply_keys(int n, Position* hist_all, PlyIndex idx, const uint16_t* ply_move) {
     const int q = blockIdx.x, lane = threadIdx.x;
     if (q >= n) return;
-    Position* hist = hist_all + hoff[q];
-    const int i = (int)plen[q];
+    Position* hist = hist_all + idx.hoff[q];
+    const int i = (int)idx.plen[q];
     const Position pos = uniform(hist[i]);
     const bool epl = has_legal_ep(pos);
     const bb_t key = position_key_wave(pos, lane, epl);
@@ -144,11 +126,11 @@ __global__ __launch_bounds__(64) void k_ply_keys(int n, Position* hist_all, cons
     }
 }
 // ... and, with every key and F_IRREV in place, the repetition flags (planes 12 / 13): is_repetition(2) / is_repetition(3)
-__global__ __launch_bounds__(64) void k_ply_rep(int n, Position* hist_all, const uint32_t* hoff, const uint32_t* plen) {
+__global__ __launch_bounds__(64) void k_ply_rep(int n, Position* hist_all, PlyIndex idx) {
     const int q = blockIdx.x, lane = threadIdx.x;
     if (q >= n) return;
-    Position* hist = hist_all + hoff[q];
-    const int i = (int)plen[q];
+    Position* hist = hist_all + idx.hoff[q];
+    const int i = (int)idx.plen[q];
     const HistChain ch{hist};
     const bb_t key0 = uniform(hist[i].key);
     const uint8_t rf = (uint8_t)__builtin_amdgcn_readfirstlane((int)rep_flags_wave(ch, i, key0, lane));
@@ -173,26 +155,24 @@ __global__ __launch_bounds__(64) void k_ply_rep(int n, Position* hist_all, const
 // per ply q of the games [g0, g0 + ng) (plies ply_off[g0] + [0, n)): its game, its index in the game and the record offset of
 // its game in the group's history buffer (group-local: ng * hist_cap records).  From the trace ring (t_move != nullptr) also
 // the ply's move and its ring index row * num_steps + ply, so that the replay reads a packed move list.  One thread per ply.
-__global__ __launch_bounds__(256) void k_ply_index(int n, int g0, int ng, const uint32_t* ply_off, int hist_cap, uint32_t* hoff,
-                                                   uint32_t* plen, uint32_t* pgame, const int32_t* rows, int num_steps,
-                                                   const uint16_t* t_move, uint16_t* moves, uint32_t* src) {
+__global__ __launch_bounds__(256) void k_ply_index(PlyGroup gr, PlyIndex idx, RingPlies ring) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t q = ply_off[g0] + (uint32_t)i;
-    int lo = g0, hi = g0 + ng - 1;   // the last game whose first ply is <= q (a game without plies shares its offset with the next)
+    if (i >= gr.n) return;
+    const uint32_t q = gr.ply_off[gr.g0] + (uint32_t)i;
+    int lo = gr.g0, hi = gr.g0 + gr.ng - 1;   // the last game whose first ply is <= q (a game without plies shares its offset with the next)
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (ply_off[mid] <= q) lo = mid;
+        if (gr.ply_off[mid] <= q) lo = mid;
         else hi = mid - 1;
     }
-    const uint32_t t = q - ply_off[lo];
-    hoff[q] = (uint32_t)(lo - g0) * (uint32_t)hist_cap;
-    plen[q] = t;
-    pgame[q] = (uint32_t)lo;
-    if (t_move) {
-        const uint32_t s = (uint32_t)rows[lo] * (uint32_t)num_steps + t;
-        moves[q] = t_move[s];
-        src[q] = s;
+    const uint32_t t = q - gr.ply_off[lo];
+    idx.hoff[q] = (uint32_t)(lo - gr.g0) * (uint32_t)gr.hist_cap;
+    idx.plen[q] = t;
+    idx.pgame[q] = (uint32_t)lo;
+    if (ring.t_move) {
+        const uint32_t s = (uint32_t)ring.rows[lo] * (uint32_t)ring.num_steps + t;
+        ring.moves[q] = ring.t_move[s];
+        ring.src[q] = s;
     }
 }
 
@@ -202,17 +182,15 @@ __global__ __launch_bounds__(256) void k_ply_index(int n, int g0, int ng, const 
 // reads them); boards and legal_idx are the caller's buffers or nullptr.  Whole rows are written: the entries past n_legal are
 // zero (include/sc_engine.h).
 template <int LAYOUT>
-__global__ __launch_bounds__(64) void k_encode_plies(int n, const Position* hist_all, const uint32_t* hoff, const uint32_t* plen,
-                                                     void* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx,
-                                                     int32_t* n_legal) {
+__global__ __launch_bounds__(64) void k_encode_plies(int n, const Position* hist_all, PlyIndex idx, PlyRows rows) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n) return;
     __shared__ __attribute__((aligned(16))) int8_t s_stage[7168];
     __shared__ move_t s_moves[MAXC];
     __shared__ int32_t s_meta[8];
     __shared__ Position s_hist[8];
-    const HistChain hc{hist_all + hoff[g]};
-    const int played = (int)plen[g];
+    const HistChain hc{hist_all + idx.hoff[g]};
+    const int played = (int)idx.plen[g];
     stage_history(hc, played, lane, s_hist);
     __syncthreads();
     const Position cur = s_hist[0];
@@ -220,13 +198,13 @@ __global__ __launch_bounds__(64) void k_encode_plies(int n, const Position* hist
     gen_legal_wave(cur, s_moves, lane, nl);
     __syncthreads();
     for (int i = lane; i < MAXC; i += 64) {
-        legal_mv[(size_t)g * MAXC + i] = i < nl ? s_moves[i] : (move_t)0;
-        if (legal_idx) legal_idx[(size_t)g * MAXC + i] = i < nl ? (uint16_t)move_index(s_moves[i], cur.turn) : (uint16_t)0;
+        rows.legal_mv[(size_t)g * MAXC + i] = i < nl ? s_moves[i] : (move_t)0;
+        if (rows.legal_idx) rows.legal_idx[(size_t)g * MAXC + i] = i < nl ? (uint16_t)move_index(s_moves[i], cur.turn) : (uint16_t)0;
     }
-    if (lane == 0) n_legal[g] = nl;
-    int8_t* out8 = (LAYOUT == 0 && boards) ? static_cast<int8_t*>(boards) + (size_t)g * 7168 : nullptr;
+    if (lane == 0) rows.n_legal[g] = nl;
+    int8_t* out8 = (LAYOUT == 0 && rows.boards) ? static_cast<int8_t*>(rows.boards) + (size_t)g * 7168 : nullptr;
     encode_wave(s_hist, played < 7 ? played + 1 : 8, lane, s_stage, out8, s_meta);
-    if (LAYOUT == 1 && boards) {
+    if (LAYOUT == 1 && rows.boards) {
         // this lane's own 112 plane bytes (written by this lane above), widened to float, plane by plane
         const uint4* cell16 = reinterpret_cast<const uint4*>(s_stage + lane * 112);
         uint32_t w[28];
@@ -238,101 +216,85 @@ __global__ __launch_bounds__(64) void k_encode_plies(int n, const Position* hist
             w[4 * k + 2] = v.z;
             w[4 * k + 3] = v.w;
         }
-        float* o = static_cast<float*>(boards) + (size_t)g * 7168 + lane;
+        float* o = static_cast<float*>(rows.boards) + (size_t)g * 7168 + lane;
 #pragma unroll
         for (int c = 0; c < 112; c++) o[c * 64] = (float)(int8_t)((w[c >> 2] >> (8 * (c & 3))) & 0xffu);
     }
     __syncthreads();
-    if (lane < 7) meta[(size_t)g * 7 + lane] = s_meta[lane];
+    if (lane < 7) rows.meta[(size_t)g * 7 + lane] = s_meta[lane];
 }
 
-// Children come either as CSR (child_off[q] .. child_off[q+1] into child_mv / child_n) or, with src != nullptr, as the
-// trace ring's padded rows (ply q: row src[q] of MAXC entries, nchild[src[q]] of them).  Writes the (mirrored) meta in the
+// Children come either as CSR or as the trace ring's padded rows (sc::Children).  Writes the (mirrored) meta in the
 // requested layout, the dense dist row, the legal-move row dist_legal[q][i] = share of legal move i (0 past n_legal), n_legal,
 // and folds the ply's failure into status[game] with an atomic min over the key 2 * ply + kind (kind 0: children are not the
 // legal moves, kind 1: the played move is illegal) -- the first failing ply wins, a children mismatch beats an illegal move
 // at the same ply (the reference's precedence); k_status_final turns the keys into sc_encode_steps's codes.
-__global__ __launch_bounds__(64) void k_steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv,
-                                                   const uint16_t* child_mv, const uint32_t* child_n, const uint32_t* child_off,
-                                                   const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
-                                                   const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout,
-                                                   void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out,
-                                                   int32_t* status) {
+__global__ __launch_bounds__(64) void k_steps_dist(int n, PlyMoves pm, Children ch, PlyIndex idx, RowOut o, int32_t* status) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n) return;
     __shared__ move_t s_lm[MAXC];
     __shared__ int s_hit[MAXC];
     __shared__ uint32_t s_cn[MAXC];
-    const int nl = n_legal_s[g];
+    const int nl = pm.n_legal[g];
     size_t c0;
     int nc;
-    if (src) {
-        const uint32_t s = src[g];
+    if (ch.src) {
+        const uint32_t s = ch.src[g];
         c0 = (size_t)s * MAXC;
-        nc = nchild[s];
+        nc = ch.nchild[s];
         nc = nc < 0 ? 0 : nc > MAXC ? MAXC : nc;
     } else {
-        c0 = child_off[g];
-        nc = (int)(child_off[g + 1] - child_off[g]);
+        c0 = ch.off[g];
+        nc = (int)(ch.off[g + 1] - ch.off[g]);
     }
-    const int turn = meta_s[(size_t)g * 7];
-    if (dist) {
-        float4* dz = reinterpret_cast<float4*>(dist + (size_t)g * 4672);
+    const int turn = o.meta_s[(size_t)g * 7];
+    if (o.dist) {
+        float4* dz = reinterpret_cast<float4*>(o.dist + (size_t)g * 4672);
         for (int i = lane; i < 4672 / 4; i += 64) dz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (int i = lane; i < MAXC; i += 64) {
-        s_lm[i] = i < nl ? legal_mv[(size_t)g * MAXC + i] : (move_t)0;
+        s_lm[i] = i < nl ? pm.legal_mv[(size_t)g * MAXC + i] : (move_t)0;
         s_hit[i] = 0;
         s_cn[i] = 0;
     }
     __syncthreads();
-    const move_t nx = next_mv[g];
+    const move_t nx = pm.next_mv[g];
     int has_next = 0, bad = 0;
     uint32_t sum = 0;
     for (int i = lane; i < nl; i += 64) has_next |= (s_lm[i] == nx) ? 1 : 0;
     for (int i = lane; i < nc; i += 64) {
-        const move_t m = child_mv[c0 + i];
+        const move_t m = ch.mv[c0 + i];
         int k = -1;
         for (int j = 0; j < nl; j++)
             if (s_lm[j] == m) k = j;
         if (k < 0) bad = 1;
         else {
             s_hit[k] = 1;     // benign same-value race between duplicates
-            s_cn[k] = child_n[c0 + i];
+            s_cn[k] = ch.n[c0 + i];
         }
-        sum += child_n[c0 + i];
+        sum += ch.n[c0 + i];
     }
     __syncthreads();
     for (int i = lane; i < nl; i += 64) bad |= s_hit[i] ? 0 : 1;   // with nc == nl this also catches duplicate children
     bad |= (nc != nl) ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);   // u32 wrap-around, as the reference's u32 sum in release mode
+    for (int sh = 32; sh > 0; sh >>= 1) sum += __shfl_xor(sum, sh, 64);   // u32 wrap-around, as the reference's u32 sum in release mode
     const float den = (float)sum + 1e-5f;
-    if (dist)
+    if (o.dist)
         for (int i = lane; i < nc; i += 64) {
-            const int idx = move_index(child_mv[c0 + i], turn);
-            if (idx >= 0) dist[(size_t)g * 4672 + idx] = (float)child_n[c0 + i] / den;
+            const int ai = move_index(ch.mv[c0 + i], turn);
+            if (ai >= 0) o.dist[(size_t)g * 4672 + ai] = (float)ch.n[c0 + i] / den;
         }
-    if (dist_legal)
-        for (int i = lane; i < MAXC; i += 64) dist_legal[(size_t)g * MAXC + i] = (i < nl && s_hit[i]) ? (float)s_cn[i] / den : 0.f;
+    if (o.dist_legal)
+        for (int i = lane; i < MAXC; i += 64) o.dist_legal[(size_t)g * MAXC + i] = (i < nl && s_hit[i]) ? (float)s_cn[i] / den : 0.f;
     const bool any_bad = __ballot(bad) != 0, any_next = __ballot(has_next) != 0;
     if (lane == 0) {
-        if (any_bad || !any_next) atomicMin(&status[pgame[g]], (int32_t)(2 * plen[g] + (any_bad ? 0 : 1)));
-        if (n_legal_out) n_legal_out[g] = nl;
+        if (any_bad || !any_next) atomicMin(&status[idx.pgame[g]], (int32_t)(2 * idx.plen[g] + (any_bad ? 0 : 1)));
+        if (o.n_legal) o.n_legal[g] = nl;
     }
-    if (meta_out && lane < 7) {
-        const int32_t* m = meta_s + (size_t)g * 7;
-        int32_t v = m[lane];
-        if (apply_mirror) {   // Board::rotate()
-            const int32_t t = m[0];
-            v = lane == 0 ? 1 - t : lane == 1 ? m[1] + (t == 1 ? 1 : 0) : lane == 2 ? m[4] : lane == 3 ? m[5] : lane == 4 ? m[2] : lane == 5 ? m[3] : v;
-        }
-        if (layout == 1) static_cast<float*>(meta_out)[(size_t)g * 7 + lane] = (float)v;
-        else static_cast<int32_t*>(meta_out)[(size_t)g * 7 + lane] = v;
-    }
+    write_meta_row(o, g, lane);
 }
 
 // status keys (2 * ply + kind, STATUS_NONE when no ply failed) -> 0 / 1000 + ply / -(ply + 1)
-constexpr int32_t STATUS_NONE = 0x7f7f7f7f;   // what a 0x7f byte fill leaves
 __global__ __launch_bounds__(256) void k_status_final(int n, int32_t* status) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -343,46 +305,32 @@ __global__ __launch_bounds__(256) void k_status_final(int n, int32_t* status) {
 }  // namespace sc
 
 namespace scl {
-void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
-                      int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
-                      int32_t* outcome, hipStream_t s, const sc::Position* d_bases, const int32_t* d_base_idx) {
-    hipLaunchKernelGGL(sc::k_encode_positions, dim3(n_pos), dim3(64), 0, s, n_pos, d_moves, d_move_off, d_move_len, d_hist, hist_cap,
-                       boards, meta, legal_mv, legal_idx, n_legal, outcome, d_bases, d_base_idx);
+void encode_positions(const sc::GameWalk& w, const sc::PlyRows& rows, int32_t* outcome, hipStream_t s) {
+    hipLaunchKernelGGL(sc::k_encode_positions, dim3(w.n_games), dim3(64), 0, s, w, rows, outcome);
 }
-void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
-               const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s) {
+void ply_index(const sc::PlyGroup& g, const sc::PlyIndex& idx, const sc::RingPlies& ring, hipStream_t s) {
+    if (g.n <= 0) return;
+    hipLaunchKernelGGL(sc::k_ply_index, dim3((g.n + 255) / 256), dim3(256), 0, s, g, idx, ring);
+}
+void replay_walk(const sc::GameWalk& w, hipStream_t s) {
+    if (w.n_games <= 0) return;
+    hipLaunchKernelGGL(sc::k_replay_raw, dim3(w.n_games), dim3(64), 0, s, w);
+}
+void replay_games(const sc::GameWalk& w, int n_plies, const sc::PlyIndex& idx, const uint16_t* d_ply_moves, hipStream_t s) {
+    if (w.n_games <= 0 || n_plies <= 0) return;
+    replay_walk(w, s);
+    hipLaunchKernelGGL(sc::k_ply_keys, dim3(n_plies), dim3(64), 0, s, n_plies, w.hist, idx, d_ply_moves);
+    hipLaunchKernelGGL(sc::k_ply_rep, dim3(n_plies), dim3(64), 0, s, n_plies, w.hist, idx);
+}
+void encode_plies(int layout, int n, const sc::Position* d_hist, const sc::PlyIndex& idx, const sc::PlyRows& rows, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_ply_index, dim3((n + 255) / 256), dim3(256), 0, s, n, g0, ng, d_ply_off, hist_cap, d_hoff, d_plen, d_pgame,
-                       d_rows, num_steps, t_move, d_moves, d_src);
+    if (layout == 1) hipLaunchKernelGGL(sc::k_encode_plies<1>, dim3(n), dim3(64), 0, s, n, d_hist, idx, rows);
+    else hipLaunchKernelGGL(sc::k_encode_plies<0>, dim3(n), dim3(64), 0, s, n, d_hist, idx, rows);
 }
-void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
-                  const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s, const sc::Position* d_bases,
-                  const int32_t* d_base_idx) {
-    if (n_games <= 0 || n_plies <= 0) return;
-    hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap, d_bases, d_base_idx);
-    hipLaunchKernelGGL(sc::k_ply_keys, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen, d_ply_moves);
-    hipLaunchKernelGGL(sc::k_ply_rep, dim3(n_plies), dim3(64), 0, s, n_plies, d_hist, d_hoff, d_plen);
-}
-void replay_walk(int n_games, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap, hipStream_t s,
-                 const sc::Position* d_bases, const int32_t* d_base_idx) {
-    if (n_games <= 0) return;
-    hipLaunchKernelGGL(sc::k_replay_raw, dim3(n_games), dim3(64), 0, s, n_games, d_moves, d_move_off, d_hist, hist_cap, d_bases, d_base_idx);
-}
-void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
-                  int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s) {
+void steps_dist(int n, const sc::PlyMoves& m, const sc::Children& c, const sc::PlyIndex& idx, const sc::RowOut& o, int32_t* status,
+                hipStream_t s) {
     if (n <= 0) return;
-    if (layout == 1)
-        hipLaunchKernelGGL(sc::k_encode_plies<1>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
-    else
-        hipLaunchKernelGGL(sc::k_encode_plies<0>, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, boards, meta, legal_mv, legal_idx, n_legal);
-}
-void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
-                const uint32_t* child_n, const uint32_t* child_off, const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
-                const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
-                float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_steps_dist, dim3(n), dim3(64), 0, s, n, legal_mv, n_legal_s, next_mv, child_mv, child_n, child_off, src,
-                       nchild, pgame, plen, apply_mirror, meta_s, layout, meta_out, dist, dist_legal, n_legal_out, status);
+    hipLaunchKernelGGL(sc::k_steps_dist, dim3(n), dim3(64), 0, s, n, m, c, idx, o, status);
 }
 void status_final(int n, int32_t* status, hipStream_t s) {
     if (n <= 0) return;

@@ -2,9 +2,9 @@
 // and, on the same walk and arena, moves written as SAN (sc_moves_to_san_device, sc_san_format).
 //
 // libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) for a batch of recorded games; see include/sc_engine.h.
-// One encoder, encode_device_core, writes device buffers on a stream.  sc_encode_steps_device / sc_selfplay_encode_traces hand
-// it the caller's buffers and stream: nothing is staged and nothing waits for the device in the steady state.  sc_encode_steps
-// runs it into staging buffers, slice by slice, and copies out to the caller's host arrays.
+// One encoder, encode_device_core, writes device buffers on a stream from a described source (EncodeSrc); it and san_write_core
+// share one set-up, GameBatch.  sc_encode_steps_device / sc_selfplay_encode_traces hand it the caller's buffers and stream: nothing
+// is staged or waits for the device in the steady state.  sc_encode_steps runs it into staging, slice by slice, and copies out.
 // The scratch of a call lives in a per-device arena that the library keeps and reuses: an event recorded behind each call's
 // work orders the next call after it on the device (hipStreamWaitEvent, whatever its stream); only growing the arena waits
 // on the host, for that previous call, before the old buffer is freed.
@@ -26,12 +26,10 @@ struct EncArena {
 std::mutex g_enc_mu;   // held across a call's enqueue: calls on one device take the arena in turn
 std::map<int, EncArena> g_enc_arena;
 struct ArenaRelease {   // scope guard: on every path out of the call (failures included), later calls wait for what was enqueued
-    EncArena& a;
-    hipStream_t s;
-    bool armed = false;
-    ~ArenaRelease() {
-        if (armed && hipEventRecord(a.ev, s) == hipSuccess) a.used = true;
-    }
+    std::unique_lock<std::mutex> lk;   // (released behind the event's record)
+    EncArena* a = nullptr;             // set once the arena is taken, with the call's stream
+    hipStream_t s = nullptr;
+    ~ArenaRelease() { if (a && hipEventRecord(a->ev, s) == hipSuccess) a->used = true; }
 };
 }  // namespace
 
@@ -63,9 +61,7 @@ int check_device_outputs(const DevEncodeOut& o, int dev) {
 namespace {
 // the game records of one group of games: (games in the group) x (longest game of the group + 2) <= REC_BUDGET, so one long
 // game among many short ones does not size the buffer for all of them (80 B per record: 80 MiB)
-struct Group {
-    int g0, ng, hist_cap;
-};
+struct Group { int g0, ng, hist_cap; };
 std::vector<Group> record_groups(int n_games, const uint32_t* ply_off, size_t* max_rec) {
     const size_t REC_BUDGET = (size_t)1 << 20;
     std::vector<Group> groups;
@@ -85,161 +81,156 @@ std::vector<Group> record_groups(int n_games, const uint32_t* ply_off, size_t* m
     }
     return groups;
 }
-// the device's arena for a call that needs `bytes` on stream st (g_enc_mu held): grown if need be, ordered behind the previous call
-int arena_take(EncArena& A, size_t bytes, hipStream_t st) {
-    if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
-    if (bytes > A.buf.cap) {
-        // the previous call's work still reads the old arena
-        TRY(A.buf.grow(bytes, [&A] { return A.used ? hipEventSynchronize(A.ev) : hipSuccess; }));
-        A.used = false;
-    } else if (A.used) {
-        HIPOK(hipStreamWaitEvent(st, A.ev, 0));   // ... possibly on another stream
+// What every call that walks recorded games sets up (encode_device_core, san_write_core): the record groups, the arena regions all
+// of them use -- a core adds its own to L before open() -- the arena, taken in turn and released behind the call's work, the uploads
+// of the offsets and base indices, the fill of the games' status keys (status_fill or null), per group the ply index and the walk.
+struct GameBatch {
+    const int n_games;
+    const uint32_t* const ply_off;   // host, n_games + 1 (the plies of game g are [ply_off[g], ply_off[g+1]))
+    const uint32_t P;
+    const hipStream_t st;
+    const HostBases host;
+    std::vector<Group> groups;
+    ArenaLayout L;
+    uint32_t* d_off;
+    uint16_t* d_moves;   // [P]: the source's upload, parse or ring copy
+    sc::PlyIndex idx;
+    sc::Position* d_hist;
+    int32_t* d_bidx;
+    sc::Bases bases{nullptr, nullptr};   // on the device, once open
+    ArenaRelease release;
+    GameBatch(int n_games_, const uint32_t* ply_off_, const HostBases& b, hipStream_t st_)
+        : n_games(n_games_), ply_off(ply_off_), P(ply_off_[n_games_]), st(st_), host(b) {
+        size_t max_rec = 1;
+        groups = record_groups(n_games, ply_off, &max_rec);
+        L.add(&d_off, (size_t)n_games + 1);
+        L.add(&d_moves, (size_t)P);
+        L.add(&idx.hoff, (size_t)P);
+        L.add(&idx.plen, (size_t)P);
+        L.add(&idx.pgame, (size_t)P);
+        L.add(&d_hist, max_rec);
+        L.add(&d_bidx, (size_t)n_games, b.rec != nullptr);
     }
-    return 0;
-}
+    int open(int dev) {
+        release.lk = std::unique_lock<std::mutex>(g_enc_mu);
+        EncArena& A = g_enc_arena[dev];   // the device's arena: grown if need be, ordered behind the previous call
+        if (!A.ev) HIPOK(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming));
+        if (L.bytes > A.buf.cap) {
+            // the previous call's work still reads the old arena
+            TRY(A.buf.grow(L.bytes, [&A] { return A.used ? hipEventSynchronize(A.ev) : hipSuccess; }));
+            A.used = false;
+        } else if (A.used) {
+            HIPOK(hipStreamWaitEvent(st, A.ev, 0));   // ... possibly on another stream
+        }
+        release.a = &A;
+        release.s = st;
+        L.bind(A.buf.p);
+        HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
+        bases = {host.rec, d_bidx};
+        if (host.rec) HIPOK(hipMemcpyAsync(d_bidx, host.idx, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    // per group with plies [p0, p1): the index, the walk (with_keys: and the plies' keys and repetition flags), then per_ply(p0, p1)
+    template <class PerPly>
+    int each_group(const sc::RingPlies& ring, bool with_keys, int32_t* status_fill, PerPly per_ply) {
+        if (status_fill) HIPOK(hipMemsetAsync(status_fill, sc::STATUS_FILL_BYTE, (size_t)n_games * 4, st));   // behind the source's uploads
+        for (const Group& gr : groups) {
+            const uint32_t p0 = ply_off[gr.g0], p1 = ply_off[gr.g0 + gr.ng];
+            if (p1 == p0) continue;
+            scl::ply_index({(int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap}, idx, ring, st);
+            const sc::GameWalk w{gr.ng, d_moves, d_off + gr.g0, d_hist, gr.hist_cap, bases.from(gr.g0)};
+            if (with_keys) scl::replay_games(w, (int)(p1 - p0), idx.from(p0), d_moves + p0, st);
+            else scl::replay_walk(w, st);
+            TRY(per_ply(p0, p1));
+        }
+        return 0;
+    }
+};
 }  // namespace
 
-// ply_off: host, n_games + 1 (the plies of game g are [ply_off[g], ply_off[g+1])).  Host path: moves / child_mv / child_n /
-// child_off are host arrays as sc_encode_steps takes them; ring path (ring != nullptr): the moves and children are read from the
-// trace ring rows on the device; SAN path (san != nullptr): the moves are parsed on the device from the host's tokens (k_san_parse
-// also writes the games' status), every ply's children are its legal moves with count 1 on the move played, and the parsed moves
-// stay in the arena between the two halves: nothing comes back to the host.
-int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
-                       const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
-                       hipStream_t st, const SanSrc* san, const BaseSrc* base) {
-    const uint32_t P = ply_off[n_games];
-    const uint32_t CH = 32768;   // plies per launch of the per-ply kernels (bounds their legal-move / meta scratch: 15 MB)
-    size_t max_rec = 1;
-    const std::vector<Group> groups = record_groups(n_games, ply_off, &max_rec);
-    const bool has_ring = ring != nullptr, has_csr = !ring && !san;
-    const uint32_t nchild = has_csr ? child_off[P] : 0;
-    const uint32_t cap = std::max<uint32_t>(std::min(CH, P), 1);
-    uint32_t *d_off, *d_hoff, *d_plen, *d_pgame, *d_src, *d_coff, *d_cn;
-    uint16_t *d_moves, *d_lm, *d_cmv;
+// One encoder for the three kinds of source (EncodeSrc, host_common.hpp).  In the SAN kind k_san_parse also writes the games'
+// status, and the parsed moves stay in the arena between the two halves: nothing comes back to the host.
+int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const EncodeSrc& src, int apply_mirror, const DevEncodeOut& o,
+                       hipStream_t st) {
+    const bool has_ring = src.kind == EncodeSrc::RING, has_csr = src.kind == EncodeSrc::CSR, has_san = src.kind == EncodeSrc::SAN;
+    GameBatch B(n_games, ply_off, src.bases, st);
+    const uint32_t P = B.P, CH = 32768;   // CH: plies per launch of the per-ply kernels (bounds their legal-move / meta scratch: 15 MB)
+    const uint32_t nchild = has_csr ? src.child_off[P] : 0, cap = std::max<uint32_t>(std::min(CH, P), 1);
+    uint32_t *d_src, *d_coff, *d_cn;
+    uint16_t *d_lm, *d_cmv;
     uint64_t* d_tok;
-    sc::Position* d_hist;
-    int32_t *d_meta, *d_nl, *d_rows, *d_bidx;
-    ArenaLayout L;
-    L.add(&d_off, (size_t)n_games + 1);
-    L.add(&d_moves, (size_t)P);
-    L.add(&d_hoff, (size_t)P);
-    L.add(&d_plen, (size_t)P);
-    L.add(&d_pgame, (size_t)P);
-    L.add(&d_hist, max_rec);
-    L.add(&d_lm, (size_t)cap * 224);
-    L.add(&d_meta, (size_t)cap * 7);
-    L.add(&d_nl, (size_t)cap);
-    L.add(&d_rows, (size_t)n_games, has_ring);
-    L.add(&d_src, (size_t)P, has_ring);
-    L.add(&d_coff, (size_t)P + 1, has_csr);
-    L.add(&d_cmv, (size_t)nchild, has_csr);
-    L.add(&d_cn, (size_t)nchild, has_csr);
-    L.add(&d_tok, (size_t)P, san != nullptr);
-    L.add(&d_bidx, (size_t)n_games, base != nullptr);
-    std::lock_guard<std::mutex> lk(g_enc_mu);
-    EncArena& A = g_enc_arena[dev];
-    TRY(arena_take(A, L.bytes, st));
-    ArenaRelease guard{A, st};
-    guard.armed = true;
-    L.bind(A.buf.p);
-    HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
-    if (base) HIPOK(hipMemcpyAsync(d_bidx, base->idx, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
-    const sc::Position* d_bases = base ? base->rec : nullptr;
-    if (ring) {
-        HIPOK(hipMemcpyAsync(d_rows, ring->rows, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
-    } else if (san) {
-        if (P) HIPOK(hipMemcpyAsync(d_tok, san->tokens, (size_t)P * 8, hipMemcpyHostToDevice, st));
-        scl::san_parse(n_games, d_tok, d_off, d_moves, o.status, st, d_bases, d_bidx);
-        if (P && san->moves_out) HIPOK(hipMemcpyAsync(san->moves_out, d_moves, (size_t)P * 2, hipMemcpyDeviceToDevice, st));
+    int32_t *d_meta, *d_nl, *d_rows;
+    B.L.add(&d_lm, (size_t)cap * 224);
+    B.L.add(&d_meta, (size_t)cap * 7);
+    B.L.add(&d_nl, (size_t)cap);
+    B.L.add(&d_rows, (size_t)n_games, has_ring);
+    B.L.add(&d_src, (size_t)P, has_ring);
+    B.L.add(&d_coff, (size_t)P + 1, has_csr);
+    B.L.add(&d_cmv, (size_t)nchild, has_csr);
+    B.L.add(&d_cn, (size_t)nchild, has_csr);
+    B.L.add(&d_tok, (size_t)P, has_san);
+    TRY(B.open(dev));
+    sc::RingPlies ring{};
+    sc::Children ch{};
+    if (has_ring) {
+        HIPOK(hipMemcpyAsync(d_rows, src.rows, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
+        ring = {d_rows, src.p->num_steps, src.p->t_move, B.d_moves, d_src};
+        ch = {src.p->t_cmove, reinterpret_cast<const uint32_t*>(src.p->t_cn), nullptr, d_src, src.p->t_nchild};
+    } else if (has_san) {
+        if (P) HIPOK(hipMemcpyAsync(d_tok, src.tokens, (size_t)P * 8, hipMemcpyHostToDevice, st));
+        scl::san_parse(n_games, d_tok, B.d_off, B.d_moves, o.status, B.bases, st);
+        if (P && src.moves_out) HIPOK(hipMemcpyAsync(src.moves_out, B.d_moves, (size_t)P * 2, hipMemcpyDeviceToDevice, st));
     } else {
-        if (P) HIPOK(hipMemcpyAsync(d_moves, moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
-        HIPOK(hipMemcpyAsync(d_coff, child_off, ((size_t)P + 1) * 4, hipMemcpyHostToDevice, st));
+        if (P) HIPOK(hipMemcpyAsync(B.d_moves, src.moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
+        HIPOK(hipMemcpyAsync(d_coff, src.child_off, ((size_t)P + 1) * 4, hipMemcpyHostToDevice, st));
         if (nchild) {
-            HIPOK(hipMemcpyAsync(d_cmv, child_mv, (size_t)nchild * 2, hipMemcpyHostToDevice, st));
-            HIPOK(hipMemcpyAsync(d_cn, child_n, (size_t)nchild * 4, hipMemcpyHostToDevice, st));
+            HIPOK(hipMemcpyAsync(d_cmv, src.child_mv, (size_t)nchild * 2, hipMemcpyHostToDevice, st));
+            HIPOK(hipMemcpyAsync(d_cn, src.child_n, (size_t)nchild * 4, hipMemcpyHostToDevice, st));
         }
+        ch = {d_cmv, d_cn, d_coff, nullptr, nullptr};
     }
-    if (!san) HIPOK(hipMemsetAsync(o.status, 0x7f, (size_t)n_games * 4, st));   // sc::STATUS_NONE: no failing ply yet
     const size_t bsz = o.layout == 1 ? 4 : 1, msz = 4;
     const bool rows_wanted = o.boards || o.meta || o.dist || o.dist_legal || o.legal_idx || o.n_legal;
-    for (const Group& gr : groups) {
-        const uint32_t p0 = ply_off[gr.g0], p1 = ply_off[gr.g0 + gr.ng];
-        if (p1 == p0) continue;
-        if (san && !rows_wanted) break;   // SAN -> moves alone
-        scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, d_rows, ring ? ring->p->num_steps : 0,
-                       ring ? ring->p->t_move : nullptr, d_moves, d_src, st);
-        scl::replay_games(gr.ng, (int)(p1 - p0), d_moves, d_off + gr.g0, d_hist, gr.hist_cap, d_hoff + p0, d_plen + p0, d_moves + p0, st,
-                          d_bases, d_bases ? d_bidx + gr.g0 : nullptr);
-        for (uint32_t c0 = p0; c0 < p1; c0 += CH) {
-            const uint32_t n = std::min(CH, p1 - c0);
-            scl::encode_plies(o.layout, (int)n, d_hist, d_hoff + c0, d_plen + c0,
-                              o.boards ? static_cast<char*>(o.boards) + (size_t)c0 * 7168 * bsz : nullptr, d_meta, d_lm,
-                              o.legal_idx ? o.legal_idx + (size_t)c0 * 224 : nullptr, d_nl, st);
-            if (san) {
-                scl::san_dist((int)n, d_lm, d_nl, d_moves + c0, apply_mirror, d_meta, o.layout,
-                              o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr, o.dist ? o.dist + (size_t)c0 * 4672 : nullptr,
-                              o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr, o.n_legal ? o.n_legal + c0 : nullptr, st);
-                continue;
+    if (!has_san || rows_wanted)   // (else SAN -> moves alone)
+        TRY(B.each_group(ring, true, has_san ? nullptr : o.status, [&](uint32_t p0, uint32_t p1) {
+            for (uint32_t c0 = p0; c0 < p1; c0 += CH) {
+                const uint32_t n = std::min(CH, p1 - c0);
+                scl::encode_plies(o.layout, (int)n, B.d_hist, B.idx.from(c0),
+                                  {o.boards ? static_cast<char*>(o.boards) + (size_t)c0 * 7168 * bsz : nullptr, d_meta, d_lm,
+                                   o.legal_idx ? o.legal_idx + (size_t)c0 * 224 : nullptr, d_nl}, st);
+                const sc::PlyMoves pm{d_lm, d_nl, B.d_moves + c0};
+                const sc::RowOut rows{apply_mirror, d_meta, o.layout, o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr,
+                                      o.dist ? o.dist + (size_t)c0 * 4672 : nullptr, o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr,
+                                      o.n_legal ? o.n_legal + c0 : nullptr};
+                if (has_san) scl::san_dist((int)n, pm, rows, st);
+                else scl::steps_dist((int)n, pm, ch.from(c0), B.idx.from(c0), rows, o.status, st);
             }
-            scl::steps_dist((int)n, d_lm, d_nl, d_moves + c0, ring ? ring->p->t_cmove : d_cmv,
-                            ring ? reinterpret_cast<const uint32_t*>(ring->p->t_cn) : d_cn, ring ? nullptr : d_coff + c0,
-                            ring ? d_src + c0 : nullptr, ring ? ring->p->t_nchild : nullptr, d_pgame + c0, d_plen + c0, apply_mirror,
-                            d_meta, o.layout, o.meta ? static_cast<char*>(o.meta) + (size_t)c0 * 7 * msz : nullptr,
-                            o.dist ? o.dist + (size_t)c0 * 4672 : nullptr, o.dist_legal ? o.dist_legal + (size_t)c0 * 224 : nullptr,
-                            o.n_legal ? o.n_legal + c0 : nullptr, o.status, st);
-        }
-    }
-    if (!san) scl::status_final(n_games, o.status, st);
+            return 0;
+        }));
+    if (!has_san) scl::status_final(n_games, o.status, st);
     HIPOK(hipGetLastError());
     return 0;
 }
 
-// The sibling of encode_device_core for sc_moves_to_san_device: the same arena, ordering and record-budget grouping; per group
-// the ply index and the walk alone (a move generation reads neither keys nor repetition flags), then one wavefront per ply
-// (k_san_write, san_write_kernels.hip).  The status keys are k_steps_dist's: filled with 0x7f, folded by atomic min, turned into
-// codes by k_status_final, with the tokens behind a game's first failing ply zeroed in between.
-static int san_write_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const BaseSrc* base, uint64_t* tokens,
+// sc_moves_to_san_device on the same set-up: per group the index and the walk alone (a move generation reads neither keys nor
+// repetition flags), then one wavefront per ply (k_san_write).  The status keys are k_steps_dist's, the tokens behind a game's
+// first failing ply are zeroed before k_status_final turns the keys into codes.
+static int san_write_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const HostBases& bases, uint64_t* tokens,
                           int32_t* status, hipStream_t st) {
-    const uint32_t P = ply_off[n_games];
-    size_t max_rec = 1;
-    const std::vector<Group> groups = record_groups(n_games, ply_off, &max_rec);
-    uint32_t *d_off, *d_hoff, *d_plen, *d_pgame;
-    uint16_t* d_moves;
-    sc::Position* d_hist;
-    int32_t* d_bidx;
-    ArenaLayout L;
-    L.add(&d_off, (size_t)n_games + 1);
-    L.add(&d_moves, (size_t)P);
-    L.add(&d_hoff, (size_t)P);
-    L.add(&d_plen, (size_t)P);
-    L.add(&d_pgame, (size_t)P);
-    L.add(&d_hist, max_rec);
-    L.add(&d_bidx, (size_t)n_games, base != nullptr);
-    std::lock_guard<std::mutex> lk(g_enc_mu);
-    EncArena& A = g_enc_arena[dev];
-    TRY(arena_take(A, L.bytes, st));
-    ArenaRelease guard{A, st};
-    guard.armed = true;
-    L.bind(A.buf.p);
-    HIPOK(hipMemcpyAsync(d_off, ply_off, ((size_t)n_games + 1) * 4, hipMemcpyHostToDevice, st));
-    if (base) HIPOK(hipMemcpyAsync(d_bidx, base->idx, (size_t)n_games * 4, hipMemcpyHostToDevice, st));
-    if (P) HIPOK(hipMemcpyAsync(d_moves, moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
-    HIPOK(hipMemsetAsync(status, 0x7f, (size_t)n_games * 4, st));   // sc::STATUS_NONE: no failing ply yet
-    for (const Group& gr : groups) {
-        const uint32_t p0 = ply_off[gr.g0], p1 = ply_off[gr.g0 + gr.ng];
-        if (p1 == p0) continue;
-        scl::ply_index((int)(p1 - p0), gr.g0, gr.ng, d_off, gr.hist_cap, d_hoff, d_plen, d_pgame, nullptr, 0, nullptr, d_moves, nullptr, st);
-        scl::replay_walk(gr.ng, d_moves, d_off + gr.g0, d_hist, gr.hist_cap, st, base ? base->rec : nullptr, base ? d_bidx + gr.g0 : nullptr);
-        scl::san_write((int)(p1 - p0), d_hist, d_hoff + p0, d_plen + p0, d_pgame + p0, d_moves + p0, tokens + p0, status, st);
-    }
-    scl::san_clip((int)P, d_plen, d_pgame, status, tokens, st);
+    GameBatch B(n_games, ply_off, bases, st);
+    TRY(B.open(dev));
+    if (B.P) HIPOK(hipMemcpyAsync(B.d_moves, moves, (size_t)B.P * 2, hipMemcpyHostToDevice, st));
+    TRY(B.each_group(sc::RingPlies{}, false, status, [&](uint32_t p0, uint32_t p1) {
+        scl::san_write((int)(p1 - p0), B.d_hist, B.idx.from(p0), B.d_moves + p0, tokens + p0, status, st);
+        return 0;
+    }));
+    scl::san_clip((int)B.P, B.idx, status, tokens, st);
     scl::status_final(n_games, status, st);
     HIPOK(hipGetLastError());
     return 0;
 }
 
-// the host trace arrays of sc_encode_steps / sc_encode_steps_device (child_off == nullptr: the offsets of sc_encode_san_device)
-static int check_traces(int n_games, const uint32_t* move_off, const uint32_t* child_off) {
+int check_traces(int n_games, const uint32_t* move_off, const uint32_t* child_off) {
     uint32_t maxlen = 0;
     for (int g = 0; g < n_games; g++) {
         if (move_off[g + 1] < move_off[g]) return fail("move_off not monotonic");
@@ -249,6 +240,14 @@ static int check_traces(int n_games, const uint32_t* move_off, const uint32_t* c
     for (uint32_t p = 0; child_off && p < move_off[n_games]; p++)
         if (child_off[p + 1] < child_off[p] || child_off[p + 1] - child_off[p] > 224) return fail("child_off: more than 224 children or not monotonic");
     return 0;
+}
+
+// the opening of the three *_device_from entry points behind their null checks: the device of the call and its bases
+struct DeviceCall { int dev; HostBases bases; };
+static int device_call_open(const sc_engine* e, int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx, const char* who, DeviceCall* c) {
+    TRY(use_device(e, device_id));
+    *c = {e ? e->device : device_id, {nullptr, base_idx}};
+    return positions_bases(bases, base_idx, n_games, c->dev, false, who, &c->bases.rec);
 }
 
 extern "C" {
@@ -266,19 +265,17 @@ int sc_encode_steps_device_from(sc_engine* e, int device_id, int n_games, const 
                                 const uint32_t* child_off, int apply_mirror, int layout, void* stream, void* boards, void* meta,
                                 float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, int32_t* status) {
     if (n_games < 0 || !move_off || !child_off || !status) return fail("bad argument");
-    TRY(use_device(e, device_id));
-    const int dev = e ? e->device : device_id;
-    BaseSrc base{nullptr, base_idx};
-    TRY(positions_bases(bases, base_idx, n_games, dev, false, "sc_encode_steps_device_from", &base.rec));
     const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
-    TRY(check_device_outputs(o, dev));
+    DeviceCall c;
+    TRY(device_call_open(e, device_id, n_games, bases, base_idx, "sc_encode_steps_device_from", &c));
+    TRY(check_device_outputs(o, c.dev));
     if (n_games == 0) return 0;
     TRY(check_traces(n_games, move_off, child_off));
     const uint32_t total = move_off[n_games];
     if (total && !moves) return fail("bad argument");
     if (child_off[total] && (!child_mv || !child_n)) return fail("bad argument");
-    return encode_device_core(dev, n_games, move_off, moves, child_mv, child_n, child_off, nullptr, apply_mirror, o,
-                              static_cast<hipStream_t>(stream), nullptr, base.rec ? &base : nullptr);
+    return encode_device_core(c.dev, n_games, move_off, EncodeSrc::csr(moves, child_mv, child_n, child_off, c.bases), apply_mirror, o,
+                              static_cast<hipStream_t>(stream));
 }
 
 int sc_encode_san_device(sc_engine* e, int device_id, int n_games, const uint64_t* tokens, const uint32_t* tok_off, int apply_mirror,
@@ -293,19 +290,15 @@ int sc_encode_san_device_from(sc_engine* e, int device_id, int n_games, const sc
                               void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, uint16_t* moves,
                               int32_t* status) {
     if (n_games < 0 || !tok_off || !status) return fail("bad argument");
-    TRY(use_device(e, device_id));
-    const int dev = e ? e->device : device_id;
-    BaseSrc base{nullptr, base_idx};
-    TRY(positions_bases(bases, base_idx, n_games, dev, false, "sc_encode_san_device_from", &base.rec));
     const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
-    TRY(check_device_outputs(o, dev));
-    TRY(check_device_ptrs({{moves, "moves"}}, dev));
+    DeviceCall c;
+    TRY(device_call_open(e, device_id, n_games, bases, base_idx, "sc_encode_san_device_from", &c));
+    TRY(check_device_outputs(o, c.dev));
+    TRY(check_device_ptrs({{moves, "moves"}}, c.dev));
     if (n_games == 0) return 0;
     TRY(check_traces(n_games, tok_off, nullptr));
     if (tok_off[n_games] && !tokens) return fail("bad argument");
-    const SanSrc san{tokens, moves};
-    return encode_device_core(dev, n_games, tok_off, nullptr, nullptr, nullptr, nullptr, nullptr, apply_mirror, o,
-                              static_cast<hipStream_t>(stream), &san, base.rec ? &base : nullptr);
+    return encode_device_core(c.dev, n_games, tok_off, EncodeSrc::san(tokens, moves, c.bases), apply_mirror, o, static_cast<hipStream_t>(stream));
 }
 
 int sc_moves_to_san_device(int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off, void* stream, uint64_t* tokens,
@@ -316,14 +309,13 @@ int sc_moves_to_san_device(int device_id, int n_games, const uint16_t* moves, co
 int sc_moves_to_san_device_from(int device_id, int n_games, const sc_positions* bases, const int32_t* base_idx, const uint16_t* moves,
                                 const uint32_t* move_off, void* stream, uint64_t* tokens, int32_t* status) {
     if (n_games < 0 || !move_off || !status || !tokens) return fail("bad argument");
-    TRY(use_device(nullptr, device_id));
-    BaseSrc base{nullptr, base_idx};
-    TRY(positions_bases(bases, base_idx, n_games, device_id, false, "sc_moves_to_san_device_from", &base.rec));
-    TRY(check_device_ptrs({{tokens, "tokens"}, {status, "status"}}, device_id));
+    DeviceCall c;
+    TRY(device_call_open(nullptr, device_id, n_games, bases, base_idx, "sc_moves_to_san_device_from", &c));
+    TRY(check_device_ptrs({{tokens, "tokens"}, {status, "status"}}, c.dev));
     if (n_games == 0) return 0;
     TRY(check_traces(n_games, move_off, nullptr));
     if (move_off[n_games] && !moves) return fail("bad argument");
-    return san_write_core(device_id, n_games, move_off, moves, base.rec ? &base : nullptr, tokens, status, static_cast<hipStream_t>(stream));
+    return san_write_core(c.dev, n_games, move_off, moves, c.bases, tokens, status, static_cast<hipStream_t>(stream));
 }
 
 int sc_san_tokenize(const char* text, size_t len, uint64_t* tokens, uint32_t cap, uint32_t* n_tokens) {
@@ -395,7 +387,7 @@ int sc_encode_steps(sc_engine* e, int device_id, int n_games, const uint16_t* mo
         for (uint32_t& x : coff) x -= c0;
         const DevEncodeOut o{0, d_boards, d_meta, d_dist, nullptr, d_li, d_nl, d_status + g0};
         HIPOK(hipEventRecord(S.ev[0], st));
-        TRY(encode_device_core(dev, g1 - g0, moff.data(), moves + p0, child_mv + c0, child_n + c0, coff.data(), nullptr, apply_mirror, o, st));
+        TRY(encode_device_core(dev, g1 - g0, moff.data(), EncodeSrc::csr(moves + p0, child_mv + c0, child_n + c0, coff.data(), HostBases{}), apply_mirror, o, st));
         HIPOK(hipEventRecord(S.ev[1], st));
         HIPOK(hipStreamSynchronize(st));
         float ms = 0.f;

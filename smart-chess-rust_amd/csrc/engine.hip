@@ -41,6 +41,14 @@ SC_FIELD(sc_trace_info, termination, 12); SC_FIELD(sc_trace_info, winner, 16); S
 
 thread_local std::string g_err;
 static thread_local std::string g_warn;
+int write_text_file(const char* path, const std::string& text, bool append) {
+    FILE* f = fopen(path, append ? "ab" : "wb");
+    if (!f) return fail(std::string("cannot open ") + path);
+    const size_t w = fwrite(text.data(), 1, text.size(), f);
+    fclose(f);
+    return w == text.size() ? 0 : fail("short write");
+}
+
 int fail(const std::string& m, int code) {
     g_err = m;
     return code;
@@ -334,13 +342,9 @@ int sc_encode_positions_from(sc_engine* e, int device_id, int n, const sc_positi
     TRY(use_device(e, device_id));
     const sc::Position* d_bases = nullptr;
     TRY(positions_bases(bases, base_idx, n, e ? e->device : device_id, false, "sc_encode_positions_from", &d_bases));
-    uint32_t total = move_off[n];
-    uint32_t maxlen = 0;
-    for (int i = 0; i < n; i++) {
-        if (move_off[i + 1] < move_off[i]) return fail("move_off not monotonic");
-        maxlen = std::max(maxlen, move_off[i + 1] - move_off[i]);
-    }
-    if (maxlen > 4000) return fail("move list too long");
+    TRY(check_traces(n, move_off, nullptr));
+    uint32_t total = move_off[n], maxlen = 0;
+    for (int i = 0; i < n; i++) maxlen = std::max(maxlen, move_off[i + 1] - move_off[i]);
     int hist_cap = (int)maxlen + 2;
     // one arena for all device buffers of the call; with an engine it persists (grown on demand) and the copies run on
     // the engine's stream behind a single synchronisation
@@ -370,7 +374,7 @@ int sc_encode_positions_from(sc_engine* e, int device_id, int n, const sc_positi
     HIPOK(hipMemsetAsync(d_lm, 0, (size_t)n * 448, st));   // rows are zero past n_legal (each region is padded to 256 B:
     HIPOK(hipMemsetAsync(d_li, 0, (size_t)n * 448, st));   // the two tables are not adjacent in general)
     if (d_bases) HIPOK(hipMemcpyAsync(d_bidx, base_idx, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    scl::encode_positions(n, d_moves, d_off, nullptr, d_hist, hist_cap, d_boards, d_meta, d_lm, d_li, d_nl, d_out, st, d_bases, d_bidx);
+    scl::encode_positions({n, d_moves, d_off, d_hist, hist_cap, {d_bases, d_bidx}}, {d_boards, d_meta, d_lm, d_li, d_nl}, d_out, st);
     HIPOK(hipGetLastError());
     if (boards) HIPOK(hipMemcpyAsync(boards, d_boards, (size_t)n * 7168, hipMemcpyDeviceToHost, st));
     if (meta) HIPOK(hipMemcpyAsync(meta, d_meta, (size_t)n * 7 * 4, hipMemcpyDeviceToHost, st));
@@ -387,14 +391,8 @@ int sc_trace_write_json(const char* path, const sc_trace_info* info, const uint1
                         const int32_t* child_off, const uint16_t* child_move, const int32_t* child_n, const float* child_q,
                         const float* child_uct) {
     if (!path || !info) return fail("bad argument");
-    std::string js = sctrace::trace_to_json(info->n_steps, info->has_outcome, info->termination, info->winner, step_move, step_q,
-                                            child_off, child_move, child_n, child_q, child_uct);
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(std::string("cannot open ") + path);
-    size_t w = fwrite(js.data(), 1, js.size(), f);
-    fclose(f);
-    if (w != js.size()) return fail("short write");
-    return 0;
+    return write_text_file(path, sctrace::trace_to_json(info->n_steps, info->has_outcome, info->termination, info->winner, step_move, step_q,
+                                                        child_off, child_move, child_n, child_q, child_uct), false);
 }
 
 int sc_move_uci(uint16_t move, char* buf8) { return sctrace::move_uci(move, buf8); }

@@ -1,6 +1,6 @@
 // host_common.hpp -- what the host units of libsc_engine.so share (engine.hip, encode_steps.hip, device_calls.hip, selfplay.hip,
-// selfplay_io.hip): error state, the handles' structs and one helper for each piece of plumbing.  Host only: no kernel unit
-// includes it.
+// selfplay_io.hip): error state, the handles' structs, the described source of an encode (EncodeSrc) and one helper for each
+// piece of plumbing.  Host only: no kernel unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <assert.h>
@@ -175,11 +175,6 @@ struct sc_positions {
 int positions_bases(const sc_positions* bases, const int32_t* idx, int n, int dev, bool for_search, const char* who, const sc::Position** d_rec);
 // Board.fen() of a record
 std::string position_fen(const sc::Position& p, bool ep_legal);
-// the bases of an encoder call: the records (device) and the base index of every game (host, n_games; < 0: none)
-struct BaseSrc {
-    const sc::Position* rec;
-    const int32_t* idx;
-};
 
 // ------------------------------------------------------------------ training tensors on the device (encode_steps.hip)
 struct DevEncodeOut {
@@ -192,22 +187,32 @@ struct DevEncodeOut {
     int32_t* n_legal;
     int32_t* status;
 };
-// the trace ring as the encoder's source (sc_selfplay_encode_traces)
-struct RingSrc {
-    const int32_t* rows;   // host: ring row of each requested game
-    const sc::SpParams* p;
-};
-// SAN tokens as the encoder's source (sc_encode_san_device): parsed on the device into the call's move list
-struct SanSrc {
-    const uint64_t* tokens;   // host: one per ply
-    uint16_t* moves_out;      // device [P] or null: a copy of the parsed moves
+// the bases of a host call (rec == nullptr: none): the records on the device, the index of every game on the host (< 0: none)
+struct HostBases { const sc::Position* rec; const int32_t* idx; };
+// What an encode reads, one kind per call, and the games' optional bases.  ply_off is the call's in every kind.
+struct EncodeSrc {
+    enum Kind { CSR, RING, SAN } kind;
+    const uint16_t *moves, *child_mv;     // CSR: host arrays as sc_encode_steps takes them
+    const uint32_t *child_n, *child_off;
+    const int32_t* rows;      // RING (sc_selfplay_encode_traces): host, the ring row of each requested game; the moves and children
+    const sc::SpParams* p;    // are read from the ring's rows on the device
+    const uint64_t* tokens;   // SAN (sc_encode_san_device): host, one per ply; the moves are parsed on the device, every ply's
+    uint16_t* moves_out;      // children are its legal moves with count 1 on the move played.  device [P] or null: the parsed moves
+    HostBases bases;
+    static EncodeSrc csr(const uint16_t* mv, const uint16_t* cmv, const uint32_t* cn, const uint32_t* coff, HostBases b) { return {CSR, mv, cmv, cn, coff, {}, {}, {}, {}, b}; }
+    static EncodeSrc ring(const int32_t* rows, const sc::SpParams* p) { return {RING, {}, {}, {}, {}, rows, p, {}, {}, {}}; }
+    static EncodeSrc san(const uint64_t* tokens, uint16_t* moves_out, HostBases b) { return {SAN, {}, {}, {}, {}, {}, {}, tokens, moves_out, b}; }
 };
 // pointers the kernels of a call read or write must be device memory of `dev`; null entries are skipped
 int check_device_ptrs(std::initializer_list<std::pair<const void*, const char*>> ptrs, int dev);
 int check_device_outputs(const DevEncodeOut& o, int dev);
-int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const uint16_t* moves, const uint16_t* child_mv,
-                       const uint32_t* child_n, const uint32_t* child_off, const RingSrc* ring, int apply_mirror, const DevEncodeOut& o,
-                       hipStream_t st, const SanSrc* san = nullptr, const BaseSrc* base = nullptr);
+// the offsets of a batch of move lists (n + 1, host): monotonic, no list longer than 4000; with child_off also the children's
+int check_traces(int n_games, const uint32_t* move_off, const uint32_t* child_off);
+int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const EncodeSrc& src, int apply_mirror, const DevEncodeOut& o,
+                       hipStream_t st);
+
+// text to a file, whole or appended
+int write_text_file(const char* path, const std::string& text, bool append);
 
 // ------------------------------------------------------------------ self-play (selfplay.hip, selfplay_io.hip)
 struct sc_selfplay {

@@ -1,4 +1,5 @@
-// launchers.hpp -- host entry points of the kernel translation units.
+// launchers.hpp -- host entry points of the kernel translation units.  A kernel family's arguments travel as blocks, passed to the
+// kernels by value (*_types.hpp); the stream comes last.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -6,6 +7,7 @@
 #include "nn_types.hpp"
 #include "score_types.hpp"
 #include "batch_types.hpp"
+#include "encode_types.hpp"
 
 struct sc_fen_fields;   // include/sc_engine.h
 
@@ -20,46 +22,34 @@ void debug_choose_child(int n_cases, const int32_t* d_n_act, const int32_t* d_nc
 void set_position(const sc::SpParams& p, int slot, const uint16_t* d_moves, int n_moves, hipStream_t s, const sc::Position* d_base = nullptr);
 void match_boundary(const sc::SpParams& p, const sc::MatchLines& lines, hipStream_t s);   // match recycling: count the games that ended, start the next ones
 // sc_selfplay_set_openings: replay and check n_lines move lists into their records (rec_off as sc::MatchLines::off) -> status [n_lines]
-// d_bases / d_base_idx (or null): line i starts from record d_base_idx[i] of d_bases where that is >= 0, behind as many empty
-// records as rec_off leaves room for in front of it (sc_selfplay_set_openings_from)
+// With bases, a line that has one starts behind as many empty records as rec_off leaves room for in front of it
+// (sc_selfplay_set_openings_from)
 void open_lines(int n_lines, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_tab, const uint32_t* d_rec_off,
-                int32_t* d_status, hipStream_t s, const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
+                int32_t* d_status, const sc::Bases& bases, hipStream_t s);
 void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s);   // [n_slots][2][4] -> [8]
-// encode_kernels.hip (compiled with -ffp-contract=off)
-void encode_positions(int n_pos, const uint16_t* d_moves, const uint32_t* d_move_off, const uint32_t* d_move_len, sc::Position* d_hist,
-                      int hist_cap, int8_t* boards, int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal,
-                      int32_t* outcome, hipStream_t s, const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
+// encode_kernels.hip (compiled with -ffp-contract=off); the argument blocks are encode_types.hpp's
+void encode_positions(const sc::GameWalk& w, const sc::PlyRows& rows, int32_t* outcome, hipStream_t s);   // one position per "game"
 // training tensors (sc_encode_steps, sc_encode_steps_device, sc_selfplay_encode_traces): see encode_kernels.hip
-void ply_index(int n, int g0, int ng, const uint32_t* d_ply_off, int hist_cap, uint32_t* d_hoff, uint32_t* d_plen, uint32_t* d_pgame,
-               const int32_t* d_rows, int num_steps, const uint16_t* t_move, uint16_t* d_moves, uint32_t* d_src, hipStream_t s);
-// the walk of a group of games whose plies start at ply p0 of the batch: d_move_off holds absolute offsets into d_moves,
-// d_hoff / d_plen / d_ply_moves are the group's plies (record offset of the ply's game, moves played before the ply, the ply's
-// move = d_moves + p0)
-void replay_games(int n_games, int n_plies, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap,
-                  const uint32_t* d_hoff, const uint32_t* d_plen, const uint16_t* d_ply_moves, hipStream_t s,
-                  const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);   // base of each game of the group, or null
+void ply_index(const sc::PlyGroup& g, const sc::PlyIndex& idx, const sc::RingPlies& ring, hipStream_t s);
 // the walk alone: boards, castling rights, ep squares and clocks of every ply (keys and flags stay 0), which is all a move
 // generation reads (sc_moves_to_san_device)
-void replay_walk(int n_games, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_hist, int hist_cap, hipStream_t s,
-                 const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
-void encode_plies(int layout, int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, void* boards,
-                  int32_t* meta, uint16_t* legal_mv, uint16_t* legal_idx, int32_t* n_legal, hipStream_t s);
-void steps_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, const uint16_t* child_mv,
-                const uint32_t* child_n, const uint32_t* child_off, const uint32_t* src, const int32_t* nchild, const uint32_t* pgame,
-                const uint32_t* plen, int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
-                float* dist_legal, int32_t* n_legal_out, int32_t* status, hipStream_t s);
+void replay_walk(const sc::GameWalk& w, hipStream_t s);
+// ... and the keys and repetition flags of its n_plies plies: idx and d_ply_moves are those of the group's first ply on
+void replay_games(const sc::GameWalk& w, int n_plies, const sc::PlyIndex& idx, const uint16_t* d_ply_moves, hipStream_t s);
+void encode_plies(int layout, int n, const sc::Position* d_hist, const sc::PlyIndex& idx, const sc::PlyRows& rows, hipStream_t s);
+void steps_dist(int n, const sc::PlyMoves& m, const sc::Children& c, const sc::PlyIndex& idx, const sc::RowOut& o, int32_t* status,
+                hipStream_t s);
 void status_final(int n, int32_t* status, hipStream_t s);
 // san_kernels.hip: SAN tokens -> moves and the parser's status per game (sc_encode_san_device), and steps_dist for rows whose
 // children are the legal moves with count 1 on the played move
-void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status, hipStream_t s,
-               const sc::Position* d_bases = nullptr, const int32_t* d_base_idx = nullptr);
-void san_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, int apply_mirror, const int32_t* meta_s,
-              int layout, void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out, hipStream_t s);
+void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status,
+               const sc::Bases& bases, hipStream_t s);
+void san_dist(int n, const sc::PlyMoves& m, const sc::RowOut& o, hipStream_t s);
 // san_write_kernels.hip: moves -> SAN tokens, one wavefront per ply of a walked group (sc_moves_to_san_device); d_status holds
-// k_steps_dist's keys (0x7f-filled, status_final behind it); san_clip zeroes a game's tokens from its first failing ply on
-void san_write(int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, const uint32_t* d_pgame,
-               const uint16_t* d_ply_moves, uint64_t* d_tokens, int32_t* d_status, hipStream_t s);
-void san_clip(int n, const uint32_t* d_plen, const uint32_t* d_pgame, const int32_t* d_status, uint64_t* d_tokens, hipStream_t s);
+// k_steps_dist's keys (sc::STATUS_NONE at first, status_final behind it); san_clip zeroes a game's tokens from its first failing ply on
+void san_write(int n, const sc::Position* d_hist, const sc::PlyIndex& idx, const uint16_t* d_ply_moves, uint64_t* d_tokens,
+               int32_t* d_status, hipStream_t s);
+void san_clip(int n, const sc::PlyIndex& idx, const int32_t* d_status, uint64_t* d_tokens, hipStream_t s);
 // fen_kernels.hip: raw FEN fields -> validated records and their status (sc_positions_from_fen); the ep bit of Board.fen()
 void fen_positions(int n, const sc_fen_fields* d_fields, const int32_t* d_syntax, sc::Position* d_out, int32_t* d_status, hipStream_t s);
 void fen_ep_legal(int n, const sc::Position* d_rec, int32_t* d_ep_legal, hipStream_t s);

@@ -258,12 +258,11 @@ __global__ __launch_bounds__(64) void k_match_tally(const int32_t* tally, int n_
 // replays a slot's move list into its chain (the same replay_step: keys, repetition and irreversibility flags), with every move
 // checked against the generated legal moves.  status[i]: 0 ok; -(j + 1): move j is not legal; 1: the game is over in the line's
 // last position (outcome(claim_draw=True), or no legal move).  rec_off[i + 1] - rec_off[i] = the line's length + 1: the host's sum.
-// With bases (sc_selfplay_set_openings_from) line i starts from record base_idx[i] where that is >= 0, a validated record of
-// fen_kernels.hip.  The host may leave room for `pad` records in front of it (rec_off[i + 1] - rec_off[i] = pad + length + 1): they
+// With bases (sc_selfplay_set_openings_from) line i starts from its base where it has one (chain_start).  The host may leave room for `pad` records in front of it (rec_off[i + 1] - rec_off[i] = pad + length + 1): they
 // are written empty -- no men, no flags: zero planes for the encoder -- and the base then carries F_IRREV, so that no repetition
 // scan of the game walks past it into them (a scan from the start of a chain stops at index 0 by itself).
 __global__ __launch_bounds__(64) void k_open_lines(int n_lines, const uint16_t* moves, const uint32_t* move_off, Position* tab,
-                                                   const uint32_t* rec_off, int32_t* status, const Position* bases, const int32_t* base_idx) {
+                                                   const uint32_t* rec_off, int32_t* status, Bases bases) {
     const int i = blockIdx.x, lane = threadIdx.x;
     if (i >= n_lines) return;
     __shared__ move_t s_moves[MAXC];
@@ -272,14 +271,7 @@ __global__ __launch_bounds__(64) void k_open_lines(int n_lines, const uint16_t* 
     const int nm = (int)(move_off[i + 1] - move_off[i]);
     const int pad = (int)(rec_off[i + 1] - rec_off[i]) - 1 - nm;
     Position* hist = tab + rec_off[i] + (pad > 0 ? pad : 0);
-    Position cur;
-    const int bi = bases ? uniform(base_idx[i]) : -1;
-    if (bi >= 0) {
-        cur = uniform(bases[bi]);
-    } else {
-        set_startpos(cur);
-        cur.key = position_key(cur);
-    }
+    Position cur = chain_start(bases, i, true);
     if (lane == 0) {
         Position none;
         set_startpos(none);
@@ -374,10 +366,9 @@ void match_boundary(const sc::SpParams& p, const sc::MatchLines& lines, hipStrea
     hipLaunchKernelGGL(sc::k_match_boundary, dim3(p.n_slots), dim3(64), 0, s, p, lines, 1);
 }
 void open_lines(int n_lines, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_tab, const uint32_t* d_rec_off,
-                int32_t* d_status, hipStream_t s, const sc::Position* d_bases, const int32_t* d_base_idx) {
+                int32_t* d_status, const sc::Bases& bases, hipStream_t s) {
     if (n_lines <= 0) return;
-    hipLaunchKernelGGL(sc::k_open_lines, dim3(n_lines), dim3(64), 0, s, n_lines, d_moves, d_move_off, d_tab, d_rec_off, d_status, d_bases,
-                       d_base_idx);
+    hipLaunchKernelGGL(sc::k_open_lines, dim3(n_lines), dim3(64), 0, s, n_lines, d_moves, d_move_off, d_tab, d_rec_off, d_status, bases);
 }
 void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s) {
     hipLaunchKernelGGL(sc::k_match_tally, dim3(1), dim3(64), 0, s, d_tally, n_slots, d_out);

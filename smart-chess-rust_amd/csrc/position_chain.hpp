@@ -5,6 +5,7 @@
 
 #include "chess_history.hpp"
 #include "chess_rules_wave.hpp"
+#include "encode_types.hpp"
 #include "wave_util.hpp"
 
 namespace sc {
@@ -24,6 +25,21 @@ __device__ __forceinline__ Position uniform(const Position& q) {
     r.halfmove = (uint16_t)uniform((int)q.halfmove);
     r.fullmove = (uint16_t)uniform((int)q.fullmove);
     return r;
+}
+
+// The position a replay of game g starts from: its base (a validated record: key set, flags clear) where the call has bases and
+// the game's index is >= 0, else the start position.  keyed: with its transposition key; else key and flags are 0 (boards alone)
+__device__ __forceinline__ Position chain_start(const Bases& b, int g, bool keyed) {
+    Position cur;
+    const int bi = b.rec ? uniform(b.idx[g]) : -1;
+    if (bi >= 0) {
+        cur = uniform(b.rec[bi]);
+    } else {
+        set_startpos(cur);
+        if (keyed) cur.key = position_key(cur);
+    }
+    if (!keyed) cur.key = cur.flags = 0;
+    return cur;
 }
 
 // chain of positions: game history, then the tree path, then the leaf being created
@@ -123,6 +139,16 @@ __device__ inline void encode_wave(const Position* s_hist, int n_hist, int lane,
         for (int k = 0; k < 7; k++) meta_out[k] = m[k];
         meta_out[7] = 0;
     }
+}
+
+// the meta row of ply g as k_steps_dist and k_san_dist write it (lanes 0..6): with apply_mirror that of Board::rotate()
+__device__ __forceinline__ void write_meta_row(const RowOut& o, int g, int lane) {
+    if (!o.meta || lane >= 7) return;
+    const int32_t* m = o.meta_s + (size_t)g * 7;
+    int32_t v = m[lane];
+    if (o.apply_mirror) v = lane == 0 ? 1 - m[0] : lane == 1 ? m[1] + (m[0] == 1 ? 1 : 0) : lane == 2 ? m[4] : lane == 3 ? m[5] : lane == 4 ? m[2] : lane == 5 ? m[3] : v;
+    if (o.layout == 1) static_cast<float*>(o.meta)[(size_t)g * 7 + lane] = (float)v;
+    else static_cast<int32_t*>(o.meta)[(size_t)g * 7 + lane] = v;
 }
 
 // transposition key of a position, lane = square: the same value as position_key() (XOR of the per-(piece, square) keys and the

@@ -87,8 +87,7 @@ __device__ __forceinline__ bool san_match(const Position& p, const SanTok& d, mo
 // than one; 200000 + i: it is malformed or the reserved value.  The first failing ply wins; the game's moves from that ply on
 // are written as 0, which no walk plays.  Claimable draws do not stop the parse (python-chess's read_game goes on too).
 __global__ __launch_bounds__(64) void k_san_parse(int n_games, const uint64_t* __restrict__ tokens, const uint32_t* __restrict__ tok_off,
-                                                  uint16_t* __restrict__ moves, int32_t* __restrict__ status,
-                                                  const Position* __restrict__ bases, const int32_t* __restrict__ base_idx) {
+                                                  uint16_t* __restrict__ moves, int32_t* __restrict__ status, Bases bases) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n_games) return;
     __shared__ move_t s_moves[MAXC];
@@ -96,12 +95,7 @@ __global__ __launch_bounds__(64) void k_san_parse(int n_games, const uint64_t* _
     const int nm = (int)(tok_off[g + 1] - p0);
     const uint64_t* tk = tokens + p0;
     uint16_t* out = moves + p0;
-    Position cur;
-    const int bi = bases ? uniform(base_idx[g]) : -1;   // the game's base record (fen_kernels.hip), else the start position
-    if (bi >= 0) cur = uniform(bases[bi]);
-    else set_startpos(cur);
-    cur.key = 0;
-    cur.flags = 0;
+    Position cur = chain_start(bases, g, false);
     int st = 0, j = 0;
     uint64_t next = nm > 0 ? tk[0] : 0;
     for (; j < nm; j++) {
@@ -140,53 +134,40 @@ __global__ __launch_bounds__(64) void k_san_parse(int n_games, const uint64_t* _
 // same outputs in the same arithmetic -- dist = count / (sum + 1e-5) with sum = 1, the (mirrored) meta in the requested layout,
 // whole rows written -- without reading children and without the two checks, which the parser has made.  A ply whose move is
 // not among the legal moves (the 0 of a failed game) gets all-zero rows.
-__global__ __launch_bounds__(64) void k_san_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv,
-                                                 int apply_mirror, const int32_t* meta_s, int layout, void* meta_out, float* dist,
-                                                 float* dist_legal, int32_t* n_legal_out) {
+__global__ __launch_bounds__(64) void k_san_dist(int n, PlyMoves pm, RowOut o) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= n) return;
-    const int nl = n_legal_s[g];
-    const int turn = meta_s[(size_t)g * 7];
-    const move_t nx = next_mv[g];
+    const int nl = pm.n_legal[g];
+    const int turn = o.meta_s[(size_t)g * 7];
+    const move_t nx = pm.next_mv[g];
     const float share = 1.f / (1.f + 1e-5f);   // count 1 of a sum of 1
-    if (dist) {
-        float4* dz = reinterpret_cast<float4*>(dist + (size_t)g * 4672);
+    if (o.dist) {
+        float4* dz = reinterpret_cast<float4*>(o.dist + (size_t)g * 4672);
         for (int i = lane; i < 4672 / 4; i += 64) dz[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
     for (int i = lane; i < MAXC; i += 64) {
-        const bool played = i < nl && legal_mv[(size_t)g * MAXC + i] == nx;
-        if (played && dist) {
+        const bool played = i < nl && pm.legal_mv[(size_t)g * MAXC + i] == nx;
+        if (played && o.dist) {
             const int idx = move_index(nx, turn);
-            if (idx >= 0) dist[(size_t)g * 4672 + idx] = share;
+            if (idx >= 0) o.dist[(size_t)g * 4672 + idx] = share;
         }
-        if (dist_legal) dist_legal[(size_t)g * MAXC + i] = played ? share : 0.f;
+        if (o.dist_legal) o.dist_legal[(size_t)g * MAXC + i] = played ? share : 0.f;
     }
-    if (n_legal_out && lane == 0) n_legal_out[g] = nl;
-    if (meta_out && lane < 7) {
-        const int32_t* m = meta_s + (size_t)g * 7;
-        int32_t v = m[lane];
-        if (apply_mirror) {   // Board::rotate()
-            const int32_t t = m[0];
-            v = lane == 0 ? 1 - t : lane == 1 ? m[1] + (t == 1 ? 1 : 0) : lane == 2 ? m[4] : lane == 3 ? m[5] : lane == 4 ? m[2] : lane == 5 ? m[3] : v;
-        }
-        if (layout == 1) static_cast<float*>(meta_out)[(size_t)g * 7 + lane] = (float)v;
-        else static_cast<int32_t*>(meta_out)[(size_t)g * 7 + lane] = v;
-    }
+    if (o.n_legal && lane == 0) o.n_legal[g] = nl;
+    write_meta_row(o, g, lane);
 }
 
 }  // namespace sc
 
 namespace scl {
-void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status, hipStream_t s,
-               const sc::Position* d_bases, const int32_t* d_base_idx) {
+void san_parse(int n_games, const uint64_t* d_tokens, const uint32_t* d_tok_off, uint16_t* d_moves, int32_t* d_status,
+               const sc::Bases& bases, hipStream_t s) {
     if (n_games <= 0) return;
-    hipLaunchKernelGGL(sc::k_san_parse, dim3(n_games), dim3(64), 0, s, n_games, d_tokens, d_tok_off, d_moves, d_status, d_bases, d_base_idx);
+    hipLaunchKernelGGL(sc::k_san_parse, dim3(n_games), dim3(64), 0, s, n_games, d_tokens, d_tok_off, d_moves, d_status, bases);
 }
-void san_dist(int n, const uint16_t* legal_mv, const int32_t* n_legal_s, const uint16_t* next_mv, int apply_mirror, const int32_t* meta_s,
-              int layout, void* meta_out, float* dist, float* dist_legal, int32_t* n_legal_out, hipStream_t s) {
+void san_dist(int n, const sc::PlyMoves& m, const sc::RowOut& o, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_san_dist, dim3(n), dim3(64), 0, s, n, legal_mv, n_legal_s, next_mv, apply_mirror, meta_s, layout, meta_out,
-                       dist, dist_legal, n_legal_out);
+    hipLaunchKernelGGL(sc::k_san_dist, dim3(n), dim3(64), 0, s, n, m, o);
 }
 }  // namespace scl

@@ -7,8 +7,6 @@
 
 namespace sc {
 
-constexpr int32_t SAN_STATUS_NONE = 0x7f7f7f7f;   // what a 0x7f byte fill leaves: the key of a game without a failing ply
-
 // ------------------------------------------------------------------ the writer
 // One wave per ply q of the batch.  Record i = plen[q] of the ply's game is the position before the move, record i + 1 the one
 // after it (the walk has made every move a legal ply needs; the last ply's record nm is written too).  Generate the legal moves
@@ -21,15 +19,14 @@ constexpr int32_t SAN_STATUS_NONE = 0x7f7f7f7f;   // what a 0x7f byte fill leave
 // The token (sc_san_tokenize's format, character k in byte k, the suffix included: at most 7 characters) is wave-uniform and
 // built on the scalar unit; lane 0 stores it.  A move that is not legal stores 0 and folds the key 2 * ply + 1 into status[game]
 // by an atomic min (k_steps_dist's key of an illegal move: k_status_final turns it into -(ply + 1), the first failing ply wins).
-__global__ __launch_bounds__(64) void k_san_write(int n, const Position* __restrict__ hist_all, const uint32_t* __restrict__ hoff,
-                                                  const uint32_t* __restrict__ plen, const uint32_t* __restrict__ pgame,
+__global__ __launch_bounds__(64) void k_san_write(int n, const Position* __restrict__ hist_all, PlyIndex idx,
                                                   const uint16_t* __restrict__ ply_move, uint64_t* __restrict__ tokens,
                                                   int32_t* __restrict__ status) {
     const int q = blockIdx.x, lane = threadIdx.x;
     if (q >= n) return;
     __shared__ move_t s_moves[MAXC];
-    const Position* hist = hist_all + uniform((int)hoff[q]);
-    const int i = uniform((int)plen[q]);
+    const Position* hist = hist_all + uniform((int)idx.hoff[q]);
+    const int i = uniform((int)idx.plen[q]);
     const Position pos = uniform(hist[i]);
     const move_t m = (move_t)uniform((int)ply_move[q]);
     const int from = mv_from(m), to = mv_to(m), promo = mv_promo(m);
@@ -52,7 +49,7 @@ __global__ __launch_bounds__(64) void k_san_write(int n, const Position* __restr
     if (!legal) {
         if (lane == 0) {
             tokens[q] = 0;
-            atomicMin(&status[pgame[q]], (int32_t)(2 * i + 1));
+            atomicMin(&status[idx.pgame[q]], (int32_t)(2 * i + 1));
         }
         return;
     }
@@ -98,24 +95,23 @@ __global__ __launch_bounds__(64) void k_san_write(int n, const Position* __restr
 
 // one thread per ply, behind k_san_write and in front of k_status_final: a game's tokens from its first failing ply on are 0
 // (the walk went on from a position the game never had: what the writer made of the later plies means nothing)
-__global__ __launch_bounds__(256) void k_san_clip(int n, const uint32_t* __restrict__ plen, const uint32_t* __restrict__ pgame,
-                                                  const int32_t* __restrict__ status, uint64_t* __restrict__ tokens) {
+__global__ __launch_bounds__(256) void k_san_clip(int n, PlyIndex idx, const int32_t* __restrict__ status, uint64_t* __restrict__ tokens) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const int32_t key = status[pgame[q]];
-    if (key != SAN_STATUS_NONE && (int32_t)plen[q] >= (key >> 1)) tokens[q] = 0;
+    const int32_t key = status[idx.pgame[q]];
+    if (key != STATUS_NONE && (int32_t)idx.plen[q] >= (key >> 1)) tokens[q] = 0;
 }
 
 }  // namespace sc
 
 namespace scl {
-void san_write(int n, const sc::Position* d_hist, const uint32_t* d_hoff, const uint32_t* d_plen, const uint32_t* d_pgame,
-               const uint16_t* d_ply_moves, uint64_t* d_tokens, int32_t* d_status, hipStream_t s) {
+void san_write(int n, const sc::Position* d_hist, const sc::PlyIndex& idx, const uint16_t* d_ply_moves, uint64_t* d_tokens,
+               int32_t* d_status, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_san_write, dim3(n), dim3(64), 0, s, n, d_hist, d_hoff, d_plen, d_pgame, d_ply_moves, d_tokens, d_status);
+    hipLaunchKernelGGL(sc::k_san_write, dim3(n), dim3(64), 0, s, n, d_hist, idx, d_ply_moves, d_tokens, d_status);
 }
-void san_clip(int n, const uint32_t* d_plen, const uint32_t* d_pgame, const int32_t* d_status, uint64_t* d_tokens, hipStream_t s) {
+void san_clip(int n, const sc::PlyIndex& idx, const int32_t* d_status, uint64_t* d_tokens, hipStream_t s) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(sc::k_san_clip, dim3((n + 255) / 256), dim3(256), 0, s, n, d_plen, d_pgame, d_status, d_tokens);
+    hipLaunchKernelGGL(sc::k_san_clip, dim3((n + 255) / 256), dim3(256), 0, s, n, idx, d_status, d_tokens);
 }
 }  // namespace scl

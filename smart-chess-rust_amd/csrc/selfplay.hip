@@ -546,7 +546,7 @@ int sc_selfplay_set_openings_from(sc_selfplay* sp, int n_lines, const sc_positio
     if (n_moves) HIPOK(hipMemcpy(d_moves.p, moves, n_moves * 2, hipMemcpyHostToDevice));
     HIPOK(hipMemcpy(d_moff.p, move_off, ((size_t)n_lines + 1) * 4, hipMemcpyHostToDevice));
     HIPOK(hipMemcpy(d_roff.p, rec_off.data(), ((size_t)n_lines + 1) * 4, hipMemcpyHostToDevice));
-    scl::open_lines(n_lines, d_moves.p, d_moff.p, d_tab.p, d_roff.p, d_status.p, sp->stream, bases ? bases->d_rec : nullptr, d_bidx.p);
+    scl::open_lines(n_lines, d_moves.p, d_moff.p, d_tab.p, d_roff.p, d_status.p, {bases ? bases->d_rec : nullptr, d_bidx.p}, sp->stream);
     HIPOK(hipGetLastError());
     HIPOK(hipStreamSynchronize(sp->stream));
     std::vector<int32_t> st((size_t)n_lines);

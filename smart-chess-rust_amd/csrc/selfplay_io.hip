@@ -190,8 +190,7 @@ int sc_selfplay_encode_traces(sc_selfplay* sp, int n, const int32_t* games, int 
     TRY(check_device_outputs(o, sp->device));
     if (n == 0) return 0;
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const RingSrc ring{rows.data(), &p};
-    TRY(encode_device_core(sp->device, n, ply_off, nullptr, nullptr, nullptr, nullptr, &ring, apply_mirror, o, st));
+    TRY(encode_device_core(sp->device, n, ply_off, EncodeSrc::ring(rows.data(), &p), apply_mirror, o, st));
     // the rows are read on `st`: the next poll (held rows) waits for that before it releases them, and a row that is not held
     // could be reused by a new game -- the handle's next steps then wait for the encode on the device
     if (!sp->enc_ev) HIPOK(hipEventCreateWithFlags(&sp->enc_ev, hipEventDisableTiming));
@@ -214,14 +213,8 @@ int sc_selfplay_write_trace_json(sc_selfplay* sp, int game, const char* path) {
     if (len == 0 && !fen) return sc_trace_write_json(path, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data());
     // a game that started from an opening line: a third key, "opening", behind the reference's two; from a base: "fen" in front of it
     if (!path) return fail("bad argument");
-    const std::string js = sctrace::trace_to_json(info.n_steps, info.has_outcome, info.termination, info.winner, sm.data(), sq.data(), co.data(),
-                                                  cm.data(), cn.data(), cq.data(), cu.data(), line, len, fen);
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail(std::string("cannot open ") + path);
-    const size_t w = fwrite(js.data(), 1, js.size(), f);
-    fclose(f);
-    if (w != js.size()) return fail("short write");
-    return 0;
+    return write_text_file(path, sctrace::trace_to_json(info.n_steps, info.has_outcome, info.termination, info.winner, sm.data(), sq.data(),
+                                                        co.data(), cm.data(), cn.data(), cq.data(), cu.data(), line, len, fen), false);
 }
 
 // Finished games as PGN: moves = opening line + played moves, rendered by one sc_moves_to_san_device_from call for the batch
@@ -303,12 +296,7 @@ int sc_selfplay_write_pgn(sc_selfplay* sp, int n, const int32_t* games, const ch
         mt.pop_back();
         text += "\n" + pgn_wrap(mt) + "\n";
     }
-    FILE* f = fopen(path, append ? "ab" : "wb");
-    if (!f) return fail(std::string("cannot open ") + path);
-    const size_t w = fwrite(text.data(), 1, text.size(), f);
-    fclose(f);
-    if (w != text.size()) return fail("short write");
-    return 0;
+    return write_text_file(path, text, append != 0);
 }
 
 int sc_selfplay_get_tree(sc_selfplay* sp, int slot, int cap, int32_t* n, float* q, float* uct, float* prior, uint16_t* move,

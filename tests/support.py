@@ -1,4 +1,5 @@
-"""What the test files share: the two `scamd` fixtures, device buffers on the engine's HIP runtime (no torch), host pointers.
+"""What the test files share: the two `scamd` fixtures, device buffers on the engine's HIP runtime (no torch), host pointers,
+and the device calls of the encoders (run_san, run_steps) with the exact comparison of their tensors.
 A fixture imported into a test module is that module's own fixture.  Two fixtures here are named `scamd` and two `dev`: a test file imports
 exactly one of each pair -- with both imported, pytest silently keeps one of them."""
 import ctypes as C
@@ -99,3 +100,59 @@ def dev_per_module(scamd):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# ------------------------------------------------------------------ the encoders' device calls
+TENSORS = ("boards", "meta", "dist", "dist_legal", "legal_idx", "n_legal")
+
+
+def _sizes(P, layout):
+    P1 = max(P, 1)
+    return dict(boards=P1 * 7168 * (4 if layout else 1), meta=P1 * 28, dist=P1 * 4672 * 4, dist_legal=P1 * 224 * 4, legal_idx=P1 * 448,
+                n_legal=P1 * 4, moves=P1 * 2)
+
+
+def _read(dev, o, P, n, layout):
+    shapes = dict(boards=((P, 112, 8, 8) if layout else (P, 8, 8, 112), np.float32 if layout else np.int8),
+                  meta=((P, 7), np.float32 if layout else np.int32), dist=((P, 4672), np.float32), dist_legal=((P, 224), np.float32),
+                  legal_idx=((P, 224), np.uint16), n_legal=((P,), np.int32), moves=((P,), np.uint16), status=((n,), np.int32))
+    return {k: dev.read(o[k], *shapes[k]) for k in o if o[k] is not None}
+
+
+def run_san(scamd, san, dev, games, mirror=False, layout=0, skip=()):
+    """sc_encode_san_device on a non-default stream into buffers pre-filled with 0x5a (outputs named in `skip` are passed as
+    NULL); read back after synchronising that stream.  games: movetext strings or token arrays"""
+    tokens, off = san.pack_tokens(games)
+    n, P = len(games), int(off[-1])
+    o = {k: (None if k in skip else dev.alloc(nb)) for k, nb in _sizes(P, layout).items()}
+    o["status"] = dev.alloc(max(n, 1) * 4)
+    rc = scamd.lib().sc_encode_san_device(None, 0, n, _p(tokens if tokens.size else np.zeros(1, np.uint64)), _p(off), int(mirror), layout,
+                                          dev.stream, *[o[k] for k in TENSORS], o["moves"], o["status"])
+    assert rc == 0, scamd.lib().sc_last_error().decode()
+    dev.sync()
+    r = _read(dev, o, P, n, layout)
+    r["ply_off"] = off
+    return r
+
+
+def run_steps(scamd, dev, steps, mirror=False, layout=0):
+    """the tensor yardstick: sc_encode_steps_device on moves and children"""
+    mv, off, cm, cn, coff = scamd.pack_steps(steps)
+    n, P = len(steps), int(off[-1])
+    o = {k: dev.alloc(nb) for k, nb in _sizes(P, layout).items() if k != "moves"}
+    o["status"] = dev.alloc(max(n, 1) * 4)
+    rc = scamd.lib().sc_encode_steps_device(None, 0, n, _p(mv), _p(off), _p(cm), _p(cn), _p(coff), int(mirror), layout, dev.stream,
+                                            *[o[k] for k in TENSORS], o["status"])
+    assert rc == 0, scamd.lib().sc_last_error().decode()
+    dev.sync()
+    r = _read(dev, o, P, n, layout)
+    r["moves"] = mv[:P]
+    return r
+
+
+def assert_bit_equal(got, ref, keys=TENSORS + ("moves",), rows=None):
+    for k in keys:
+        if k in got:
+            a, b = (got[k], ref[k]) if rows is None else (got[k][rows], ref[k][rows])
+            assert a.dtype == b.dtype and a.shape == b.shape, k
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), k

@@ -9,8 +9,8 @@ from collections import Counter
 import numpy as np
 import pytest
 
-from support import dev_per_test, _p, scamd_gpu  # noqa: F401
-from test_gpu_san import TENSORS, _read, _sizes, assert_bit_equal, one_hot_steps, run_san, san_of, yardstick_moves
+from san_ref import one_hot_steps, san_of, yardstick_moves
+from support import TENSORS, _p, _read, _sizes, assert_bit_equal, dev_per_test, run_san, scamd_gpu  # noqa: F401
 from test_oracle_rules import PERFT
 
 pytestmark = pytest.mark.gpu

@@ -13,94 +13,19 @@ import numpy as np
 import pytest
 
 import helpers as H
-from support import dev_per_test, _p, scamd_gpu  # noqa: F401
+from san_ref import PINNED_RIVAL, one_hot_steps, san_of, yardstick_moves
+from support import TENSORS, _p, _sizes, assert_bit_equal, dev_per_test, run_san, run_steps, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 RESERVED = 0xFFFFFFFFFFFFFFFF
-TENSORS = ("boards", "meta", "dist", "dist_legal", "legal_idx", "n_legal")
 
 
 @pytest.fixture(scope="module")
 def san(scamd):
     import scamd.san as m
     return m
-
-
-def _sizes(P, layout):
-    P1 = max(P, 1)
-    return dict(boards=P1 * 7168 * (4 if layout else 1), meta=P1 * 28, dist=P1 * 4672 * 4, dist_legal=P1 * 224 * 4, legal_idx=P1 * 448,
-                n_legal=P1 * 4, moves=P1 * 2)
-
-
-def _read(dev, o, P, n, layout):
-    shapes = dict(boards=((P, 112, 8, 8) if layout else (P, 8, 8, 112), np.float32 if layout else np.int8),
-                  meta=((P, 7), np.float32 if layout else np.int32), dist=((P, 4672), np.float32), dist_legal=((P, 224), np.float32),
-                  legal_idx=((P, 224), np.uint16), n_legal=((P,), np.int32), moves=((P,), np.uint16), status=((n,), np.int32))
-    return {k: dev.read(o[k], *shapes[k]) for k in o if o[k] is not None}
-
-
-def run_san(scamd, san, dev, games, mirror=False, layout=0, skip=()):
-    """sc_encode_san_device on a non-default stream into buffers pre-filled with 0x5a (outputs named in `skip` are passed as
-    NULL); read back after synchronising that stream.  games: movetext strings or token arrays"""
-    tokens, off = san.pack_tokens(games)
-    n, P = len(games), int(off[-1])
-    o = {k: (None if k in skip else dev.alloc(nb)) for k, nb in _sizes(P, layout).items()}
-    o["status"] = dev.alloc(max(n, 1) * 4)
-    rc = scamd.lib().sc_encode_san_device(None, 0, n, _p(tokens if tokens.size else np.zeros(1, np.uint64)), _p(off), int(mirror), layout,
-                                          dev.stream, *[o[k] for k in TENSORS], o["moves"], o["status"])
-    assert rc == 0, scamd.lib().sc_last_error().decode()
-    dev.sync()
-    r = _read(dev, o, P, n, layout)
-    r["ply_off"] = off
-    return r
-
-
-def run_steps(scamd, dev, steps, mirror=False, layout=0):
-    """the tensor yardstick: sc_encode_steps_device on moves and children"""
-    mv, off, cm, cn, coff = scamd.pack_steps(steps)
-    n, P = len(steps), int(off[-1])
-    o = {k: dev.alloc(nb) for k, nb in _sizes(P, layout).items() if k != "moves"}
-    o["status"] = dev.alloc(max(n, 1) * 4)
-    rc = scamd.lib().sc_encode_steps_device(None, 0, n, _p(mv), _p(off), _p(cm), _p(cn), _p(coff), int(mirror), layout, dev.stream,
-                                            *[o[k] for k in TENSORS], o["status"])
-    assert rc == 0, scamd.lib().sc_last_error().decode()
-    dev.sync()
-    r = _read(dev, o, P, n, layout)
-    r["moves"] = mv[:P]
-    return r
-
-
-def one_hot_steps(orc, moves):
-    """ValidationDataset._to_trace: the children of a ply are the legal moves, count 1 on the move played"""
-    st = orc.State()
-    steps = []
-    for m in moves:
-        steps.append((m, [(x, 1 if x == m else 0) for x in st.legal_moves()]))
-        st.push(m)
-    return steps
-
-
-def yardstick_moves(orc, movetext):
-    """helpers.san_to_move over the oracle, on the SAN words of a plain movetext (numbers and the result dropped here)"""
-    st = orc.State()
-    moves = []
-    for w in movetext.split():
-        if w[0].isdigit() and w not in ("0-0", "0-0-0") or w == "*":
-            continue
-        m, _, _ = H.san_to_move(st, w.replace("0", "O") if w.startswith("0-0") else w, orc)
-        st.push(m)
-        moves.append(m)
-    return moves
-
-
-def assert_bit_equal(got, ref, keys=TENSORS + ("moves",), rows=None):
-    for k in keys:
-        if k in got:
-            a, b = (got[k], ref[k]) if rows is None else (got[k][rows], ref[k][rows])
-            assert a.dtype == b.dtype and a.shape == b.shape, k
-            assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), k
 
 
 @pytest.fixture(scope="module")
@@ -144,64 +69,9 @@ def test_each_output_null_in_turn(scamd, san, dev, golden):
 
 
 # ------------------------------------------------------------------ the edge-line corpus, rendered to SAN
-_LET = {2: "N", 3: "B", 4: "R", 5: "Q", 6: "K"}
-
-
-def _sq(s):
-    return "abcdefgh"[s & 7] + str((s >> 3) + 1)
-
-
-def san_of(st, m, style, seen):
-    """SAN of the legal move m in oracle state st.  style "min": standard minimal disambiguation, "=" before a promotion piece;
-    "noeq": the same without the "="; "over": piece, origin square, "-" or "x", destination (castling with the digit 0).
-    seen counts the special cases rendered."""
-    fr, to, pr = H.mv_parts(m)
-    b = H.board_of(st)
-    pt, white = abs(b[fr]), b[fr] > 0
-    ep = pt == 1 and (fr & 7) != (to & 7) and not b[to]
-    cap = bool(b[to]) or ep
-    st.push(m)
-    chk = st.is_check()
-    suf = ("#" if not st.legal_moves() else "+") if chk else ""
-    st.pop()
-    seen["ep"] += ep
-    seen["promo_capture_check"] += bool(pr and cap and chk)
-    seen["underpromo"] += pr in (2, 3, 4)
-    if pt == 6 and abs(to - fr) == 2:
-        seen["castle_k" if to > fr else "castle_q"] += 1
-        s = "O-O" if to > fr else "O-O-O"
-        return (s.replace("O", "0") if style == "over" else s) + suf
-    promo = ("" if style == "noeq" else "=") + _LET[pr] if pr else ""
-    if style == "over":
-        return (_LET[pt] if pt > 1 else "") + _sq(fr) + ("x" if cap else "-") + _sq(to) + promo + suf
-    if pt == 1:
-        return ("abcdefgh"[fr & 7] + "x" if cap else "") + _sq(to) + promo + suf
-    others = [x for x in st.legal_moves() if x != m and (x >> 6) & 63 == to and abs(b[x & 63]) == pt]
-    dis = ""
-    if others:
-        if not any((x & 7) == (fr & 7) for x in others):
-            dis = "abcdefgh"[fr & 7]
-            seen["file_dis"] += 1
-        elif not any((x & 63) >> 3 == fr >> 3 for x in others):
-            dis = str((fr >> 3) + 1)
-            seen["rank_dis"] += 1
-        else:
-            dis = _sq(fr)
-    elif not st.is_check():
-        # a rival of the same kind reaches the square too, but is pinned off it: only legality makes the short form unique
-        for r in H.attackers(b, to, white):
-            pl = H.pin_line(b, r) if r != fr and abs(b[r]) == pt else None
-            seen["pinned_rival"] += pl is not None and to not in pl
-    return _LET[pt] + dis + ("x" if cap else "") + _sq(to) + promo + suf
-
-
-# the corpus has no short form that is unique only through a pin: after 3...d6 the knight on c6 is pinned, so 4...Ne7 is the g8 knight's
-_PINNED_RIVAL = ["e2e4", "e7e5", "g1f3", "b8c6", "f1b5", "d7d6", "e1g1", "g8e7"]
-
-
 @pytest.mark.parametrize("style", ["min", "over", "noeq"])
 def test_edge_lines_rendered_to_san(scamd, san, orc, dev, style):
-    lines = [ln["uci"] for ln in H.load_edge_lines()] + [_PINNED_RIVAL]
+    lines = [ln["uci"] for ln in H.load_edge_lines()] + [PINNED_RIVAL]
     seen = Counter()
     games, want = [], []
     for uci in lines:
@@ -294,6 +164,31 @@ def test_long_knight_shuffle_beside_short_games(scamd, san, orc, dev):
     off = r["ply_off"]
     rep = r["boards"][off[1]:off[2]].reshape(300, 64, 112)[:, 0, 12:14]   # repetition planes of the position before each ply
     assert rep[:4].sum() == 0 and rep[4:8, 0].all() and rep[8:, 1].all()
+
+
+def test_two_record_groups_long_game_in_the_first(scamd, san, orc, dev):
+    """300 games of which game 150 has 4000 plies: 300 x 4002 position records exceed the walk's budget of 2^20, so the call
+    walks two groups of games, the long game among short ones in the first.
+    The oracle's State holds 1024 plies, so the yardstick walks the first 1000 plies of the shuffle; every fourth ply the board,
+    the side to move, the castling rights (all intact: only knights move) and the ep square (none) are those of four plies before,
+    and a SAN word's move and a position's legal moves depend on nothing else, so the yardstick's moves and one-hot steps of the
+    1000 plies, which must show that period, are continued with it.  The clocks and repetition planes, which do change, come
+    from the device on both sides (run_steps is the tensors' yardstick)."""
+    short = ["1. e4 e5", "1. d4", "1. c4 c5 2. Nc3"]
+    period = ["Nf3", "Nf6", "Ng1", "Ng8"]
+    games = [short[i % 3] for i in range(300)]
+    games[150] = " ".join(period * 1000)
+    by_text = {g: yardstick_moves(orc, g) for g in short + [" ".join(period * 250)]}
+    steps = {g: one_hot_steps(orc, m) for g, m in by_text.items()}
+    head, head_steps = by_text.pop(" ".join(period * 250)), steps.pop(" ".join(period * 250))
+    assert len(head) == 1000 and head == head[:4] * 250 and head_steps == head_steps[:4] * 250
+    by_text[games[150]], steps[games[150]] = head[:4] * 1000, head_steps[:4] * 1000
+    moves = [by_text[g] for g in games]
+    assert len(moves[150]) == 4000 and 262 * 4002 <= 2 ** 20 < 263 * 4002   # the first group ends behind game 261
+    r = run_san(scamd, san, dev, games)
+    assert (r["status"] == 0).all(), r["status"]
+    assert np.array_equal(r["moves"], np.asarray([m for g in moves for m in g], np.uint16))
+    assert_bit_equal(r, run_steps(scamd, dev, [steps[g] for g in games]))
 
 
 def test_bad_arguments_are_refused(scamd, san, dev):

@@ -1,7 +1,7 @@
 """Games written as SAN and PGN on the GPU (-m gpu): sc_moves_to_san_device, one wavefront per ply, and what stands on it
 (sc_selfplay_write_pgn, sc-play --pgn, tools/trace_to_pgn.py, scamd.san.moves_to_san).
 Two yardsticks, neither of which calls the device: the words of the reference's own 60 games (tests/golden/ref_sample_games.csv,
-read to moves by helpers.san_to_move over the CPU oracle), and cpu_san below, python-chess's Board.san() over orc.State.
+read to moves by helpers.san_to_move over the CPU oracle), and san_ref.py's renderer, python-chess's Board.san() over orc.State.
 All comparisons are exact text or exact integers.  Device buffers come from hipMalloc on the HIP runtime libsc_engine.so uses,
 pre-filled with 0x5a, with guard words behind tokens[P) and status[n), on a non-default stream; this file does not import torch
 -- the torch-facing calls run in child processes."""
@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from san_ref import cpu_game
 from support import dev_per_test, _p, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -24,69 +25,12 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 PLAY = os.path.join(ROOT, "smart-chess-rust_amd", "lib", "sc-play")
 GUARD = 4   # words behind each output
 FILL64, FILL32 = 0x5a5a5a5a5a5a5a5a, 0x5a5a5a5a
-_LET = {2: "N", 3: "B", 4: "R", 5: "Q", 6: "K"}
 
 
 @pytest.fixture(scope="module")
 def san(scamd):
     import scamd.san as m
     return m
-
-
-def _sq(s):
-    return "abcdefgh"[s & 7] + str((s >> 3) + 1)
-
-
-# ------------------------------------------------------------------ the CPU renderer (never calls the device)
-def cpu_san(st, m, seen=None):
-    """python-chess's Board.san(m) over the oracle (Board._algebraic_without_suffix + the check marks); m must be legal in st"""
-    seen = Counter() if seen is None else seen
-    legal = st.legal_moves()
-    assert m in legal, (st.fen(), m)
-    fr, to, pr = H.mv_parts(m)
-    pt = abs(st.piece_at(fr))
-    if pt == 6 and abs((to & 7) - (fr & 7)) == 2:
-        s = "O-O" if (to & 7) == 6 else "O-O-O"
-    else:
-        ep = pt == 1 and (fr & 7) != (to & 7) and st.piece_at(to) == 0
-        cap = st.piece_at(to) != 0 or ep
-        seen["ep"] += ep
-        if pt == 1:
-            s = "abcdefgh"[fr & 7] if cap else ""      # pawns are never disambiguated
-        else:
-            s = _LET[pt]
-            others = [x & 63 for x in legal if (x >> 6) & 63 == to and (x & 63) != fr and abs(st.piece_at(x & 63)) == pt]
-            if others:
-                row = any(o >> 3 == fr >> 3 for o in others)
-                col = any(o & 7 == fr & 7 for o in others)
-                if row or not col:
-                    s += "abcdefgh"[fr & 7]
-                if col:
-                    s += str((fr >> 3) + 1)
-                seen["file_and_rank"] += (row or not col) and col
-            elif not st.is_check():
-                # a rival of the same kind attacks the square too but is pinned off it: only legality makes the short form unique
-                b = H.board_of(st)
-                for r in H.attackers(b, to, b[fr] > 0):
-                    pl = H.pin_line(b, r) if r != fr and abs(b[r]) == pt else None
-                    seen["pinned_rival"] += pl is not None and to not in pl
-        s += ("x" if cap else "") + _sq(to) + ("=" + _LET[pr] if pr else "")
-        seen["underpromo"] += pr in (2, 3, 4)
-    st.push(m)
-    chk = st.is_check()
-    s += ("+" if st.legal_moves() else "#") if chk else ""
-    seen["promo_capture_check"] += bool(pr and "x" in s and chk)
-    st.pop()
-    return s
-
-
-def cpu_game(orc, moves, fen=None, seen=None):
-    st = orc.State(fen) if fen else orc.State()
-    words = []
-    for m in moves:
-        words.append(cpu_san(st, m, seen))
-        st.push(m)
-    return words
 
 
 def census(words):
@@ -286,6 +230,19 @@ def test_batch_edges(scamd, san, orc, dev, golden, edge):
     k = max(range(90), key=lambda i: len(edge["moves"][i]))
     assert len(edge["moves"][k]) == 198
     assert run_write(scamd, san, dev, [edge["moves"][k]])[:2] == ([edge["words"][k]], [0])
+
+
+def test_two_record_groups_long_game_in_the_first(scamd, san, orc, dev):
+    """300 games of which game 150 has 4000 plies: 300 x 4002 position records exceed the walk's budget of 2^20, so the call
+    walks two groups of games, the long game among short ones in the first"""
+    u = lambda s: [orc.from_uci(x) for x in s.split()]
+    short = [(u("e2e4 e7e5"), ["e4", "e5"]), (u("d2d4"), ["d4"]), (u("c2c4 c7c5 b1c3"), ["c4", "c5", "Nc3"])]
+    games, want = [short[i % 3][0] for i in range(300)], [short[i % 3][1] for i in range(300)]
+    games[150], want[150] = u("g1f3 g8f6 f3g1 f6g8") * 1000, ["Nf3", "Nf6", "Ng1", "Ng8"] * 1000
+    assert len(games[150]) == 4000 and 262 * 4002 <= 2 ** 20 < 263 * 4002   # the first group ends behind game 261
+    words, status, _ = run_write(scamd, san, dev, games)
+    assert status == [0] * 300
+    assert words == want
 
 
 # ------------------------------------------------------------------ 6. the handle and the launcher

@@ -1,11 +1,12 @@
 """developer tool (CPU-only box, starts nothing on a GPU): are the gfx950 instruction streams of the kernels the same in two trees?
 
-    python tools/isa_compare.py OLD_TREE [NEW_TREE] [--rename OLD=NEW ...] [--keep DIR]
+    python tools/isa_compare.py OLD_TREE [NEW_TREE] [--rename OLD=NEW ...] [--by-name] [--keep DIR]
 
 Compiles every kernel unit each tree's build.py lists (the units may differ between the trees: kernels move) to device-only
 assembly with that unit's flags, demangles, strips comments, directives and label numbering, pools a tree's functions by
 demangled name and compares the pools.  --rename maps a name of the old tree to its name in the new one (applied to the whole
-text, so a kernel's own LDS symbols follow).  NEW_TREE defaults to the tree this file is in.  Exit status 1 when a function
+text, so a kernel's own LDS symbols follow).  --by-name pools by the name without its parameter list, for kernels whose
+parameters were regrouped (their LDS symbols follow too).  NEW_TREE defaults to the tree this file is in.  Exit status 1 when a function
 present in both trees differs."""
 import argparse
 import ast
@@ -25,11 +26,18 @@ def units(tree):
     return [(u, ast.literal_eval(f)) for u, f in pairs if u.endswith("_kernels.hip")]
 
 
-def pool(tree, tag, tmp, renames):
+def pool(tree, tag, tmp, renames, by_name=False):
     fns = {}
     for unit, extra in units(tree):
         fns.update(functions(assembly(tree, unit, extra, os.path.join(tmp, tag + "_" + unit + ".s")), renames))
+    if by_name:
+        fns = {bare(n): [line.replace(n, bare(n)) for line in body] for n, body in fns.items()}
     return fns
+
+
+def bare(name):
+    """a demangled function name without its parameter list"""
+    return re.sub(r"\(.*\)$", "", name)
 
 
 def assembly(tree, unit, extra, out):
@@ -66,13 +74,14 @@ def main():
     ap.add_argument("old_tree")
     ap.add_argument("new_tree", nargs="?", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
+    ap.add_argument("--by-name", action="store_true", help="pool by function name without the parameter list")
     ap.add_argument("--keep", help="directory for the .s files (default: a temporary one)")
     a = ap.parse_args()
     renames = [tuple(r.split("=", 1)) for r in a.rename]
     tmp = a.keep or tempfile.mkdtemp(prefix="isa_compare_")
     os.makedirs(tmp, exist_ok=True)
     differ = 0
-    old, new = pool(a.old_tree, "old", tmp, renames), pool(a.new_tree, "new", tmp, [])
+    old, new = pool(a.old_tree, "old", tmp, renames, a.by_name), pool(a.new_tree, "new", tmp, [], a.by_name)
     print("== %d functions in the old tree, %d in the new" % (len(old), len(new)))
     for name in sorted(set(old) | set(new)):
         short = name if len(name) <= 110 else name[:107] + "..."
