@@ -104,7 +104,8 @@ int sc_predict_batch(sc_engine*, int n, const int8_t* boards, const int32_t* met
 int sc_predict_batch_argmax(sc_engine*, int n, const int8_t* boards, const int32_t* meta, const uint16_t* legal_idx,
                             const uint32_t* legal_off, float* priors, float* value);
 int sc_engine_synchronize(sc_engine*);
-/* test aid: fp32 residual stream [n][64][channels] after `stage` (0 = conv_block, b = res block b, 1000 = trunk output) */
+/* test aid: fp32 residual stream [n][64][channels] after `stage`: 0 = after conv_block, b = after the b-th residual block (1-based:
+ * 1 is the first block), 1000 = trunk output */
 int sc_forward_debug(sc_engine*, int n, const int8_t* boards, const int32_t* meta, int stage, float* out);
 
 /* Rules + encoder on the GPU: replaces python-chess (src/chess.rs:665-803) and _encode

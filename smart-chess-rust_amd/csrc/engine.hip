@@ -282,7 +282,8 @@ int sc_forward_batch(sc_engine* e, int n, const int8_t* boards, const int32_t* m
     return forward_host(e, n, boards, meta, nullptr, nullptr, nullptr, value, logp, nullptr, -1);
 }
 
-/* debugging aid for tests: residual stream after `stage` (0 stem, b block b, 1000 latent): out[n][64][C] */
+/* debugging aid for tests: residual stream after `stage` (0: after the stem, b: after the b-th residual block, 1-based, 1000: the
+ * latent): out[n][64][C] */
 int sc_forward_debug(sc_engine* e, int n, const int8_t* boards, const int32_t* meta, int stage, float* out) {
     return forward_host(e, n, boards, meta, nullptr, nullptr, nullptr, nullptr, nullptr, out, stage);
 }
