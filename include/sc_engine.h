@@ -386,6 +386,47 @@ int sc_gather_batch(int device_id, int n_src, int n_batch, const int32_t* rows, 
                     const float* outcome, void* stream, float* out_boards, float* out_meta, float* out_dist, float* out_outcome,
                     int32_t* n_bad);
 
+/* ------------------------------------------------------------------ identical training positions merged, targets averaged */
+/* Self-play in lockstep from one start position, or from opening lines used twice, writes the same network input many times with
+ * contradicting targets.  This call groups rows of the compact tensors (the form sc_gather_batch reads) that are the same sample
+ * input and writes one row per group: the input of the group's head, the mean visit shares, the mean outcome, and a count.  The
+ * outputs have the form of the inputs, so sc_gather_batch and sc_score_positions read them as they are.
+ * Positions and rows: position p (0 <= p < n_in) stands for source row r(p) = rows ? rows[p] : p (rows: device int32 [n_in]; NULL
+ * needs n_in <= n_src); a source row may stand at several positions.  r(p) outside [0, n_src): nothing is read through it,
+ * group_of[p] = -1, p belongs to no group and adds 1 to counts[1].
+ * Same sample: positions a and b are the same sample iff the 7 168 board bytes are equal, the 28 meta bytes are equal, n_legal is
+ * equal and lies in 0..218, and legal_idx[:n_legal] is equal entry by entry.  Padding past n_legal (garbage, NaN, indices up to
+ * 65535) is never looked at.  A position whose n_legal is outside 0..218 is the same as nothing: a group of one whose row is
+ * copied verbatim, and 1 more in counts[1].
+ * Groups: the head of a group is its smallest position; groups are numbered by ascending head.  group_of[p] (int32 [n_in]) is the
+ * group's number, out_first[j] the head's position, out_count[j] the group's size m.
+ * The merged row j: out_boards, out_meta, out_n_legal and the whole 224-entry out_legal_idx row are the head's bytes;
+ * out_dist_legal[j][i] for i >= n_legal is the head's bits; for i < n_legal it is s / (float)m, an IEEE division, with s = x_1,
+ * s = s + x_k for k = 2..m over the members in ascending position, in float32; out_outcome[j] is formed in the same way.  For m = 1
+ * the row is bit-identical to its source row.  Rows >= counts[0] of the outputs are not written.  Each output may be NULL.
+ * counts (device int32 [4], zeroed on the stream first): [0] the number of groups, [1] bad positions (as above), [2] positions
+ * whose bytes differed from the head of their key (see below), [3] the largest m.
+ * Keys are a shortcut, never the decision: rows are found through a key of key_bits bits (128 in normal use; 0..128 accepted)
+ * over exactly the bytes named above, and EVERY position is then compared byte for byte with the head its key points to.  A
+ * position that differs becomes a group of its own, is never merged with anything and adds 1 to counts[2].  So unequal rows are
+ * never merged, whatever the key; equal rows can fail to merge only behind a key clash, which at 128 bits does not happen, and
+ * which is reported.  Values of key_bits below 128 exist so that this path can be tested.
+ * Workspace: device memory of at least the bytes sc_merge_positions_workspace(n_in) reports (about 120 per position; no device is
+ * needed to ask), used during the call's work on the stream only.  A smaller one: -1.
+ * Determinism: no float atomic is used anywhere, the order of every sum is fixed by position: identical calls give identical bits.
+ * Pointer checks as sc_forward_device, the workspace included (host memory or memory of another GPU than device_id's: -1);
+ * boards, legal_idx, out_boards and out_legal_idx 16-byte aligned; negative sizes, n_in above 2^30 or key_bits outside 0..128: -1;
+ * n_in == 0: four zeros go to counts and nothing else is written.
+ * Stream contract as sc_gather_batch: the work is enqueued on `stream` (NULL: the default stream); the call does not wait on the
+ * host and keeps nothing after it returns.  Returns 0, or < 0 as every entry point (-3: no HIP device). */
+int sc_merge_positions_workspace(int n_in, size_t* bytes);
+int sc_merge_positions(int device_id, int n_src, int n_in, const int32_t* rows /* or NULL: position p is row p, n_in <= n_src */,
+                       const int8_t* boards, const int32_t* meta, const float* dist_legal, const uint16_t* legal_idx,
+                       const int32_t* n_legal, const float* outcome, int key_bits, void* workspace, size_t workspace_bytes,
+                       void* stream, int8_t* out_boards, int32_t* out_meta, float* out_dist_legal, uint16_t* out_legal_idx,
+                       int32_t* out_n_legal, float* out_outcome, int32_t* out_count, int32_t* out_first, int32_t* group_of,
+                       int32_t* counts /* [4] */);
+
 /* ------------------------------------------------------------------ self-play (L-search) */
 /* SYNTH: integer-hash evaluator for exact search-parity tests; SYNTH_COARSE: the same with 2-bit priors and values from
  * {-0.5, 0, 0.5} (exact PUCT ties between some siblings); SYNTH_UNIFORM: uniform priors, value 0 (every unvisited sibling

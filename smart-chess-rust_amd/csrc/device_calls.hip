@@ -1,4 +1,4 @@
-// device_calls.hip -- host side of libsc_engine.so: the calls on device tensors (forward, losses, agreement, minibatches).
+// device_calls.hip -- host side of libsc_engine.so: the calls on device tensors (forward, losses, agreement, minibatches, merged positions).
 //
 // sc_forward_device / sc_score_positions / sc_compare_engines (include/sc_engine.h).  The positions are cut into slices of
 // SCORE_SLICE (the figure sc_encode_steps uses), so the scratch of a call is bounded whatever its size: enqueue_forward's own
@@ -215,6 +215,65 @@ int sc_gather_batch(int device_id, int n_src, int n_batch, const int32_t* rows, 
     a.n_bad = n_bad;
     scl::gather_batch(a, st);
     HIPOK(hipGetLastError());
+    return 0;
+}
+
+// Identical rows of the compact training tensors merged into one row each (include/sc_engine.h): the kernels of
+// merge_kernels.hip on the caller's stream, their scratch in the caller's workspace.  No engine, no host wait, nothing kept.
+int sc_merge_positions_workspace(int n_in, size_t* bytes) {
+    if (n_in < 0 || n_in > scmg::MAX_IN || !bytes) return fail("bad argument");
+    *bytes = scmg::workspace(n_in).bytes;
+    return 0;
+}
+
+int sc_merge_positions(int device_id, int n_src, int n_in, const int32_t* rows, const int8_t* boards, const int32_t* meta,
+                       const float* dist_legal, const uint16_t* legal_idx, const int32_t* n_legal, const float* outcome, int key_bits,
+                       void* workspace, size_t workspace_bytes, void* stream, int8_t* out_boards, int32_t* out_meta, float* out_dist_legal,
+                       uint16_t* out_legal_idx, int32_t* out_n_legal, float* out_outcome, int32_t* out_count, int32_t* out_first,
+                       int32_t* group_of, int32_t* counts) {
+    if (n_src < 0 || n_in < 0 || n_in > scmg::MAX_IN || key_bits < 0 || key_bits > 128 || !boards || !meta || !dist_legal || !legal_idx ||
+        !n_legal || !outcome)
+        return fail("bad argument");
+    if (!rows && n_in > n_src) return fail("bad argument: without rows, position p is row p and n_in may not exceed n_src");
+    const scmg::Workspace L = scmg::workspace(n_in);
+    if (n_in > 0 && (!workspace || workspace_bytes < L.bytes))
+        return fail("workspace: " + std::to_string(L.bytes) + " bytes are needed (sc_merge_positions_workspace)");
+    TRY(use_device(nullptr, device_id));
+    TRY(check_device_ptrs({{rows, "rows"}, {boards, "boards"}, {meta, "meta"}, {dist_legal, "dist_legal"}, {legal_idx, "legal_idx"},
+                           {n_legal, "n_legal"}, {outcome, "outcome"}, {workspace, "workspace"}, {out_boards, "out_boards"},
+                           {out_meta, "out_meta"}, {out_dist_legal, "out_dist_legal"}, {out_legal_idx, "out_legal_idx"},
+                           {out_n_legal, "out_n_legal"}, {out_outcome, "out_outcome"}, {out_count, "out_count"},
+                           {out_first, "out_first"}, {group_of, "group_of"}, {counts, "counts"}}, device_id));
+    TRY(check_row_alignment({{boards, "boards"}, {legal_idx, "legal_idx"}, {out_boards, "out_boards"}, {out_legal_idx, "out_legal_idx"}}));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (counts) HIPOK(hipMemsetAsync(counts, 0, 4 * sizeof(int32_t), st));
+    if (n_in == 0) return 0;
+    scmg::MergeArgs a{};
+    a.n_src = n_src;
+    a.n_in = n_in;
+    a.key_bits = key_bits;
+    a.rows = rows;
+    a.boards = boards;
+    a.meta = meta;
+    a.dist_legal = dist_legal;
+    a.legal_idx = legal_idx;
+    a.n_legal = n_legal;
+    a.outcome = outcome;
+    a.ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    a.out_boards = out_boards;
+    a.out_meta = out_meta;
+    a.out_dist_legal = out_dist_legal;
+    a.out_legal_idx = out_legal_idx;
+    a.out_n_legal = out_n_legal;
+    a.out_outcome = out_outcome;
+    a.out_count = out_count;
+    a.out_first = out_first;
+    a.group_of = group_of;
+    a.counts = counts;
+    const char* why = nullptr;
+    const hipError_t err = scl::merge_positions(a, st, &why);
+    if (why) return fail(why);
+    HIPOK(err);
     return 0;
 }
 

@@ -7,6 +7,7 @@
 #include "nn_types.hpp"
 #include "score_types.hpp"
 #include "batch_types.hpp"
+#include "merge_types.hpp"
 #include "encode_types.hpp"
 
 struct sc_fen_fields;   // include/sc_engine.h
@@ -71,4 +72,7 @@ void compare_rows(const scsc::CompareArgs& a, hipStream_t s);
 void score_summary(const scsc::SummaryArgs& a, hipStream_t s);
 // batch_kernels.hip: rows of the compact training tensors, chosen by index -> a trainer-layout minibatch (sc_gather_batch)
 void gather_batch(const scbt::GatherArgs& a, hipStream_t s);
+// merge_kernels.hip: identical rows of the compact training tensors -> one row each, targets averaged (sc_merge_positions); a.n_in > 0.
+// Enqueues everything on s; an error that is not HIP's own is named in *why
+hipError_t merge_positions(const scmg::MergeArgs& a, hipStream_t s, const char** why);
 }  // namespace scl

@@ -1,4 +1,7 @@
-"""Shuffled trainer-layout minibatches from the compact training tensors, on the GPU (csrc/batch_kernels.hip)."""
+"""Shuffled trainer-layout minibatches from the compact training tensors, on the GPU (csrc/batch_kernels.hip), and identical
+positions merged into one sample each (csrc/merge_kernels.hip)."""
+import ctypes as C
+
 import numpy as np
 
 from .binding import MAX_MOVES, PLY_BYTES, _check, _stream, _torch, _tp, lib
@@ -65,6 +68,73 @@ def gather_batch_torch(src, rows, mirror=None, n_bad=None):
                                  _tp(src["legal_idx"]), _tp(src["n_legal"]), _tp(src["outcome"]), _stream(torch, device),
                                  _tp(out[0]), _tp(out[1]), _tp(out[2]), _tp(out[3]), _tp(n_bad)))
     return out
+
+
+_merge_ws = {}   # device -> the workspace of merge_positions_torch, a byte tensor kept at the largest size asked for
+
+
+def _merge_workspace(torch, device, n_in):
+    need = C.c_size_t(0)
+    _check(lib().sc_merge_positions_workspace(n_in, C.byref(need)))
+    ws = _merge_ws.get(device)
+    if ws is None or ws.numel() < need.value:
+        ws = _merge_ws[device] = torch.empty(need.value, dtype=torch.uint8, device=torch.device("cuda", device))
+    return ws
+
+
+def merge_positions_torch(src, rows=None, key_bits=128):
+    """Rows of the compact tensors that are the same sample input -- board bytes, meta, n_legal and legal_idx[:n_legal] -- merged
+    into one row each, with the mean visit shares and the mean outcome (sc_merge_positions), without leaving the GPU.
+    src: the dict gather_batch_torch takes; rows: None (every row, in order) or an int32 / int64 cuda tensor [n_in] of row numbers
+    (position p is row rows[p]; a row may repeat, a row outside the source belongs to no group); key_bits: 128, less only to test
+    the byte compare behind the key.
+    -> a dict of the same six keys, one row per group (groups ascend with their smallest position), which gather_batch_torch and
+    score_torch read as they are, plus count int32 [G] (the group's size), first int32 [G] (its smallest position), group_of int32
+    [n_in] (-1: no group), n_bad (rows outside the source, and rows with n_legal outside 0..218, which stay alone) and
+    n_key_clash (positions that differed from the head of their key and stay alone: 0 at 128 bits); ply_off / status of src
+    are passed on when rows is None.  Enqueued on torch.cuda.current_stream(); the counts are the call's one host read.  The
+    workspace is kept per device: calls on one device are expected on one stream at a time."""
+    torch = _torch(cached=True)
+    device, n = _check_compact_tensors(torch, src)
+    dev = torch.device("cuda", device)
+    if rows is not None:
+        if rows.dtype not in (torch.int32, torch.int64) or rows.dim() != 1 or rows.device != dev:
+            raise ValueError(f"rows: a one-dimensional int32 or int64 tensor on cuda:{device} is needed")
+        rows = rows.to(torch.int32).contiguous()
+    n_in = n if rows is None else int(rows.shape[0])
+    ws = _merge_workspace(torch, device, n_in)
+    out = {k: torch.empty((n_in,) + tuple(src[k].shape[1:]), dtype=src[k].dtype, device=dev) for k in _COMPACT_KEYS}
+    count, first, group_of = (torch.empty(n_in, dtype=torch.int32, device=dev) for _ in range(3))
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    _check(lib().sc_merge_positions(device, n, n_in, _tp(rows), *[_tp(src[k]) for k in _COMPACT_KEYS], int(key_bits), _tp(ws), ws.numel(),
+                                    _stream(torch, device), *[_tp(out[k]) for k in _COMPACT_KEYS], _tp(count), _tp(first),
+                                    _tp(group_of), _tp(counts)))
+    G, n_bad, n_clash, _ = counts.tolist()
+    res = {k: v[:G] for k, v in out.items()}
+    res.update(count=count[:G], first=first[:G], group_of=group_of, n_bad=n_bad, n_key_clash=n_clash)
+    if rows is None:
+        res.update({k: src[k] for k in ("ply_off", "status") if k in src})
+    return res
+
+
+def unique_by_ply(tensors):
+    """The diversity report of a merge: per ply index, the number of plies and the number of distinct samples among them.
+    tensors: group_of (merge_positions_torch's; positions in game order) and ply_off [games + 1] (game g's positions are
+    ply_off[g] .. ply_off[g + 1]); optional ply_first [games]: the ply index of each game's first position (default 0).
+    -> dict(plies int64 [L], distinct int64 [L]) on the host, L the largest ply index + 1; positions without a group do not count"""
+    g = tensors["group_of"]
+    g = np.asarray(g.cpu() if hasattr(g, "cpu") else g, np.int64)
+    off = np.asarray(tensors["ply_off"], np.int64)
+    lens = np.diff(off)
+    if int(off[-1]) - int(off[0]) != g.shape[0]:
+        raise ValueError("ply_off does not match group_of")
+    first = np.asarray(tensors.get("ply_first", np.zeros(len(lens))), np.int64)
+    ply = np.concatenate([first[i] + np.arange(n) for i, n in enumerate(lens)]) if len(lens) else np.zeros(0, np.int64)
+    L = int(ply.max()) + 1 if ply.size else 0
+    keep = g >= 0
+    plies = np.bincount(ply[keep], minlength=L)
+    pairs = np.unique(np.stack([ply[keep], g[keep]]), axis=1)
+    return dict(plies=plies.astype(np.int64), distinct=np.bincount(pairs[0], minlength=L).astype(np.int64))
 
 
 class ReplayIndex:
@@ -145,6 +215,7 @@ class ReplayBuffer:
         self.index = ReplayIndex(capacity_plies, start_step)
         self.device = device
         self.store = None
+        self._merged = None   # (index version, merged()'s result)
 
     def __len__(self):
         return int(self.index.eligible_rows().size)
@@ -176,15 +247,31 @@ class ReplayBuffer:
             for key in _COMPACT_KEYS:
                 self.store[key][d:d + k].copy_(tensors[key][s:s + k])
 
-    def epoch_order(self, seed=0, epoch=0, shuffle=True, mirror=False):
+    def merged(self):
+        """merge_positions_torch over the eligible rows (oldest game first): one row per distinct sample, targets averaged;
+        with ply_off / ply_first of the eligible plies for unique_by_ply.  Computed once, until the next add()."""
+        torch = self._storage()
+        if self._merged is None or self._merged[0] != self.index.version:
+            rows = torch.from_numpy(self.index.eligible_rows()).to(torch.device("cuda", self.device))
+            m = merge_positions_torch(self.store, rows)
+            skip = [0 if n < self.index.start_step else self.index.start_step for _, n in self.index.games]
+            m["ply_off"] = np.concatenate([[0], np.cumsum([n - k for (_, n), k in zip(self.index.games, skip)])]).astype(np.int64)
+            m["ply_first"] = np.asarray(skip, np.int64)
+            self._merged = (self.index.version, m)
+        return self._merged[1]
+
+    def epoch_order(self, seed=0, epoch=0, shuffle=True, mirror=False, unique=False):
         """the rows of one epoch in the order batches() draws them, and their mirror bits: (int32 [E], uint8 [E] or None) on the
         GPU.  The order is torch.randperm on the device from a generator seeded by (seed, epoch); mirror "random" takes one bit
-        per sample from the same generator."""
+        per sample from the same generator.  unique: the rows are those of merged()."""
         if mirror not in (False, True, "random"):
             raise ValueError('mirror must be False, True or "random"')
         torch = self._storage()
         dev = torch.device("cuda", self.device)
-        order = torch.from_numpy(self.index.eligible_rows()).to(dev)
+        if unique:
+            order = torch.arange(self.merged()["count"].shape[0], dtype=torch.int64, device=dev)
+        else:
+            order = torch.from_numpy(self.index.eligible_rows()).to(dev)
         E = order.shape[0]
         gen = torch.Generator(device=dev)
         gen.manual_seed(ReplayIndex.epoch_seed(seed, epoch))
@@ -196,17 +283,18 @@ class ReplayBuffer:
             bits = torch.ones(E, dtype=torch.uint8, device=dev) if mirror else None
         return order.to(torch.int32), bits
 
-    def batches(self, batch_size, seed=0, epoch=0, shuffle=True, drop_last=True, mirror=False):
+    def batches(self, batch_size, seed=0, epoch=0, shuffle=True, drop_last=True, mirror=False, unique=False):
         """one epoch: yields (boards [B,112,8,8], meta [B,7], dist [B,4672], outcome [B,1]), float32 on the GPU, in the order of
         epoch_order(); mirror False / True / "random".  Nothing is copied to the host per batch.  An add() during the epoch ends
-        it with a RuntimeError: the rows of the plan may have been evicted."""
-        order, bits = self.epoch_order(seed, epoch, shuffle, mirror)
+        it with a RuntimeError: the rows of the plan may have been evicted.  unique: the epoch runs over merged() -- every distinct
+        sample once, with its mean targets; the merge is made once and kept until the next add()."""
+        order, bits = self.epoch_order(seed, epoch, shuffle, mirror, unique)
         plan = ReplayIndex.epoch_plan(int(order.shape[0]), batch_size, drop_last)
-        return self._epoch(plan, order, bits)
+        return self._epoch(plan, order, bits, self.merged() if unique else self.store)
 
-    def _epoch(self, plan, order, bits):
+    def _epoch(self, plan, order, bits, src):
         version = self.index.version
         for lo, hi in plan:
             if self.index.version != version:
                 raise RuntimeError("games were added during the epoch: start a new one")
-            yield gather_batch_torch(self.store, order[lo:hi], None if bits is None else bits[lo:hi])
+            yield gather_batch_torch(src, order[lo:hi], None if bits is None else bits[lo:hi])
