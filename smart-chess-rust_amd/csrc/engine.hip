@@ -1,6 +1,6 @@
 // engine.hip -- host side of libsc_engine.so: the C ABI of include/sc_engine.h over the HIP kernels.  This unit: the engine and
 // its host-pointer calls, the helpers of host_common.hpp; training tensors are in encode_steps.hip, the calls on device tensors in
-// device_calls.hip, self-play in selfplay.hip and selfplay_io.hip.
+// device_calls.hip, self-play in selfplay.hip, match_play.hip, selfplay_io.hip and debug_calls.hip.
 //
 // Replaces, behind the reference's own interfaces: backend construction + Game::predict
 // (src/main.rs:83-128, src/backends/torch.rs:89-146), the rules/encoder calls into python-chess

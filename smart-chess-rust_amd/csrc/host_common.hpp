@@ -1,6 +1,6 @@
 // host_common.hpp -- what the host units of libsc_engine.so share (engine.hip, encode_steps.hip, device_calls.hip, selfplay.hip,
-// selfplay_io.hip): error state, the handles' structs, the described source of an encode (EncodeSrc) and one helper for each
-// piece of plumbing.  Host only: no kernel unit includes it.
+// match_play.hip, selfplay_io.hip, debug_calls.hip): error state, the handles' structs, the described source of an encode
+// (EncodeSrc) and one helper for each piece of plumbing.  Host only: no kernel unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <assert.h>
@@ -175,6 +175,8 @@ struct sc_positions {
 int positions_bases(const sc_positions* bases, const int32_t* idx, int n, int dev, bool for_search, const char* who, const sc::Position** d_rec);
 // Board.fen() of a record
 std::string position_fen(const sc::Position& p, bool ep_legal);
+// text into a caller's buffer of cap bytes (cut to cap - 1 and terminated; cap == 0: nothing is written): the text's full length
+int copy_text(const std::string& s, char* buf, int cap);
 
 // ------------------------------------------------------------------ training tensors on the device (encode_steps.hip)
 struct DevEncodeOut {
@@ -214,7 +216,7 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const Enco
 // text to a file, whole or appended
 int write_text_file(const char* path, const std::string& text, bool append);
 
-// ------------------------------------------------------------------ self-play (selfplay.hip, selfplay_io.hip)
+// ------------------------------------------------------- self-play (selfplay.hip, match_play.hip, selfplay_io.hip, debug_calls.hip)
 struct sc_selfplay {
     sc_engine* engine = nullptr;
     int device = 0;
@@ -270,12 +272,21 @@ struct sc_selfplay {
     bool poisoned = false;
 };
 
+// a device buffer that lives as long as the handle.  The zero-fill runs on the handle's stream, ahead of every launch on it
+template <class T>
+static int sp_alloc(sc_selfplay* sp, T** ptr, size_t n, bool zero = true) {
+    HIPOK(dalloc(ptr, n));
+    sp->allocs.push_back(*ptr);
+    if (zero) HIPOK(hipMemsetAsync(*ptr, 0, std::max<size_t>(n, 1) * sizeof(T), sp->stream));
+    return 0;
+}
+// The weights of the end-of-ply move choice, w[n] = powf((float)n, 1.0f / temperature) for n = 0..n_max, by the host libm
+// (selfplay.hip): the table of a handle and of sc_debug_choose_child
+std::vector<float> choice_weights(float temperature, int n_max);
+
 int sp_refuse(const sc_selfplay* sp);   // the error of a poisoned handle
-// complete the last enqueued simulation (expand / backward / ply transition) so that host reads see a fully backed-up state; a
-// following enqueue would have done the same work in its first launch
-void sp_flush(sc_selfplay* sp);
-int sp_latch(sc_selfplay* sp);   // called with the stream idle: looks at the device's error word
-// the opening of a host read or write: set the device, sp_flush, wait for the stream; with `latch` also sp_latch, and refuse a
+// The opening of a host read or write: set the device, complete the last enqueued simulation (expand / backward / ply transition:
+// host reads see a fully backed-up state), wait for the stream; with `latch` also look at the device's error word, and refuse a
 // poisoned handle
 int sp_quiesce(sc_selfplay* sp, bool latch);
 // the opening line of handle-local game `game` (sc_selfplay_set_openings): its length, *moves = its first move; 0 without lines

@@ -95,7 +95,7 @@ struct SpParams {
     const float* vf_w;
     uint32_t vf_fc1b, vf_fc1m, vf_fc2w, vf_fc2b;
     // end-of-ply move choice: choice_w[n] = powf((float)n, 1.0f / temperature) for n = 0..choice_w_max (= the largest simulation
-    // budget of a ply), filled by the host with the host libm (selfplay.hip choice_weights); null at temperature 0
+    // budget of a ply), filled by the host with the host libm (host_common.hpp choice_weights); null at temperature 0
     const float* choice_w;
     int choice_w_max;
     unsigned long long* dbg_cycles;  // optional [slot][32] stamps of the last launch (developer aid): 0..7 the search's cycle stamps, 8.. experiment builds

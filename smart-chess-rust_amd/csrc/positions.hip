@@ -22,6 +22,15 @@ std::string position_fen(const sc::Position& p, bool ep_legal) {
     return buf;
 }
 
+int copy_text(const std::string& s, char* buf, int cap) {
+    if (cap > 0) {
+        const size_t k = std::min(s.size(), (size_t)cap - 1);
+        memcpy(buf, s.data(), k);
+        buf[k] = 0;
+    }
+    return (int)s.size();
+}
+
 int positions_bases(const sc_positions* bases, const int32_t* idx, int n, int dev, bool for_search, const char* who, const sc::Position** d_rec) {
     *d_rec = nullptr;
     if (!bases || !idx) return 0;
@@ -118,13 +127,7 @@ int sc_positions_status(const sc_positions* ps, int i) {
 int sc_positions_fen(const sc_positions* ps, int i, char* buf, int cap) {
     if (!ps || i < 0 || i >= ps->n || cap < 0 || (cap > 0 && !buf)) return fail("bad argument");
     if (ps->status[(size_t)i] < 0) return fail("sc_positions_fen: position " + std::to_string(i) + " was refused (status " + std::to_string(ps->status[(size_t)i]) + ")");
-    const std::string s = position_fen(ps->rec[(size_t)i], ps->ep_legal[(size_t)i] != 0);
-    if (cap > 0) {
-        const size_t k = std::min(s.size(), (size_t)cap - 1);
-        memcpy(buf, s.data(), k);
-        buf[k] = 0;
-    }
-    return (int)s.size();
+    return copy_text(position_fen(ps->rec[(size_t)i], ps->ep_legal[(size_t)i] != 0), buf, cap);
 }
 
 }  // extern "C"

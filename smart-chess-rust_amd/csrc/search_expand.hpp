@@ -102,7 +102,7 @@ __device__ inline void finish_game(SpParams& p, int g, int lane, int has_outcome
 // child; *total = the f32 sum of the weights of the weighted branch (0 at temperature 0).  The one implementation: the
 // self-play kernels and the test aid k_debug_choose_child (sc_debug_choose_child) both call it.
 // The weight N^(1/temperature) is READ from w[0..w_max], which the host filled with ITS libm's powf for this temperature
-// (selfplay.hip choice_weights): the reference's f32::powf is that function, and the index below must be the reference's bit for
+// (host_common.hpp choice_weights): the reference's f32::powf is that function, and the index below must be the reference's bit for
 // bit -- the device's own powf is one ulp off it for a quarter of all (count, temperature) pairs.  Temperature 1
 // (the temperature-switch window) needs no table: powf(n, 1) == n.  A count never exceeds the ply's simulation budget, which
 // the table covers; the index is clamped all the same so that no read can leave the table.

@@ -49,11 +49,37 @@ static std::string pgn_wrap(const std::string& text) {
     return o + "\n";
 }
 
-extern "C" {
+// the opening of an accessor of one slot: the handle quiesced (no latch), the slot's control block read
+static int sp_read_ctl(sc_selfplay* sp, int slot, sc::GameCtl* c) {
+    TRY(sp_quiesce(sp, false));
+    HIPOK(hipMemcpy(c, sp->p.ctl + slot, sizeof *c, hipMemcpyDeviceToHost));
+    return 0;
+}
 
-int sc_selfplay_get_trace(sc_selfplay* sp, int game, sc_trace_info* info, uint16_t* step_move, float* step_q,
-                          int32_t* child_off, uint16_t* child_move, int32_t* child_n, float* child_q, float* child_uct) {
-    if (!sp || !info || game < 0 || game >= sp->p.total_games) return fail("bad argument");
+// A finished game's row of the trace ring on the host: the header and the child counts always, of the arrays those named in `want`
+// (every vector holds one spare element: data() is never null).  The children are compacted: those of ply i start at child_off[i].
+enum { TR_MOVE = 1, TR_Q = 2, TR_CMOVE = 4, TR_CN = 8, TR_CQ = 16, TR_CU = 32, TR_ALL = 63 };
+struct TraceRow {
+    sc_trace_info info;
+    std::vector<int32_t> child_off, cn;   // [n_steps + 1], [n_children_total]
+    std::vector<uint16_t> move, cmove;    // [n_steps], [n_children_total]
+    std::vector<float> q, cq, cu;
+};
+// one copy per array for the whole game (rows of 224 entries per ply), compacted on the host: a copy per ply and array cost more
+// than the games themselves when many short games stream out
+template <class T>
+static int read_children(const TraceRow& r, const T* d_rows, std::vector<T>& out) {
+    const size_t ns = (size_t)r.info.n_steps;
+    std::vector<T> rows(ns * 224 + 1);
+    if (ns) HIPOK(hipMemcpy(rows.data(), d_rows, ns * 224 * sizeof(T), hipMemcpyDeviceToHost));
+    out.resize((size_t)r.info.n_children_total + 1);
+    for (size_t i = 0; i < ns; i++)
+        memcpy(out.data() + r.child_off[i], rows.data() + i * 224, (size_t)(r.child_off[i + 1] - r.child_off[i]) * sizeof(T));
+    return 0;
+}
+// 0, 1: the game has not finished, 2: its row is gone, < 0: an error -- the codes of sc_selfplay_get_trace
+static int sp_read_trace(sc_selfplay* sp, int game, unsigned want, TraceRow& r) {
+    if (!sp || game < 0 || game >= sp->p.total_games) return fail("bad argument");
     const uint64_t want_id = sp->p.first_game_id + (uint64_t)game;
     game %= sp->p.trace_cap;
     if (sp->poisoned) return sp_refuse(sp);
@@ -70,49 +96,44 @@ int sc_selfplay_get_trace(sc_selfplay* sp, int game, sc_trace_info* info, uint16
         case ROW_GONE: return fail(h.state == sc::TR_FREE ? "trace released or overwritten" : "trace overwritten by a later game (trace_capacity ring)", 2);
         case ROW_READY: break;
     }
-    const size_t S = (size_t)p.num_steps, base = (size_t)game * S;
-    int ns = h.n_steps;
-    std::vector<int32_t> nch((size_t)std::max(ns, 1));
-    if (ns) HIPOK(hipMemcpy(nch.data(), p.t_nchild + base, (size_t)ns * 4, hipMemcpyDeviceToHost));
-    int total = 0;
-    for (int i = 0; i < ns; i++) total += nch[(size_t)i];
-    info->n_steps = ns;
-    info->n_children_total = total;
-    info->has_outcome = h.has_outcome;
-    info->termination = h.termination;
-    info->winner = h.winner;
-    info->game_id = h.game_id;
-    if (step_move && ns) HIPOK(hipMemcpy(step_move, p.t_move + base, (size_t)ns * 2, hipMemcpyDeviceToHost));
-    if (step_q && ns) HIPOK(hipMemcpy(step_q, p.t_q + base, (size_t)ns * 4, hipMemcpyDeviceToHost));
-    if (child_off) {
-        int off = 0;
-        for (int i = 0; i < ns; i++) {
-            child_off[i] = off;
-            off += nch[(size_t)i];
-        }
-        child_off[ns] = off;
-    }
-    if ((child_move || child_n || child_q || child_uct) && ns) {
-        // one copy per array for the whole game (rows of 224 entries per ply), compacted on the host: a copy per ply and
-        // array cost more than the games themselves when many short games stream out
-        const size_t rows = (size_t)ns * 224, src = base * 224;
-        std::vector<uint16_t> mv(child_move ? rows : 0);
-        std::vector<int32_t> cn(child_n ? rows : 0);
-        std::vector<float> cq(child_q ? rows : 0), cu(child_uct ? rows : 0);
-        if (child_move) HIPOK(hipMemcpy(mv.data(), p.t_cmove + src, rows * 2, hipMemcpyDeviceToHost));
-        if (child_n) HIPOK(hipMemcpy(cn.data(), p.t_cn + src, rows * 4, hipMemcpyDeviceToHost));
-        if (child_q) HIPOK(hipMemcpy(cq.data(), p.t_cq + src, rows * 4, hipMemcpyDeviceToHost));
-        if (child_uct) HIPOK(hipMemcpy(cu.data(), p.t_cu + src, rows * 4, hipMemcpyDeviceToHost));
-        int off = 0;
-        for (int i = 0; i < ns; i++) {
-            const size_t n = (size_t)nch[(size_t)i], r0 = (size_t)i * 224;
-            if (child_move) memcpy(child_move + off, mv.data() + r0, n * 2);
-            if (child_n) memcpy(child_n + off, cn.data() + r0, n * 4);
-            if (child_q) memcpy(child_q + off, cq.data() + r0, n * 4);
-            if (child_uct) memcpy(child_uct + off, cu.data() + r0, n * 4);
-            off += (int)n;
-        }
-    }
+    const size_t ns = (size_t)h.n_steps, base = (size_t)game * (size_t)p.num_steps;
+    r.child_off.assign(ns + 2, 0);
+    if (ns) HIPOK(hipMemcpy(r.child_off.data() + 1, p.t_nchild + base, ns * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ns; i++) r.child_off[i + 1] += r.child_off[i];
+    r.info.n_steps = h.n_steps;
+    r.info.n_children_total = r.child_off[ns];
+    r.info.has_outcome = h.has_outcome;
+    r.info.termination = h.termination;
+    r.info.winner = h.winner;
+    r.info.game_id = h.game_id;
+    r.move.resize(ns + 1);
+    r.q.resize(ns + 1);
+    if ((want & TR_MOVE) && ns) HIPOK(hipMemcpy(r.move.data(), p.t_move + base, ns * 2, hipMemcpyDeviceToHost));
+    if ((want & TR_Q) && ns) HIPOK(hipMemcpy(r.q.data(), p.t_q + base, ns * 4, hipMemcpyDeviceToHost));
+    if (want & TR_CMOVE) TRY(read_children(r, p.t_cmove + base * 224, r.cmove));
+    if (want & TR_CN) TRY(read_children(r, p.t_cn + base * 224, r.cn));
+    if (want & TR_CQ) TRY(read_children(r, p.t_cq + base * 224, r.cq));
+    if (want & TR_CU) TRY(read_children(r, p.t_cu + base * 224, r.cu));
+    return 0;
+}
+
+extern "C" {
+
+int sc_selfplay_get_trace(sc_selfplay* sp, int game, sc_trace_info* info, uint16_t* step_move, float* step_q,
+                          int32_t* child_off, uint16_t* child_move, int32_t* child_n, float* child_q, float* child_uct) {
+    if (!info) return fail("bad argument");
+    TraceRow r;
+    TRY(sp_read_trace(sp, game, (step_move ? TR_MOVE : 0) | (step_q ? TR_Q : 0) | (child_move ? TR_CMOVE : 0) | (child_n ? TR_CN : 0) |
+                                    (child_q ? TR_CQ : 0) | (child_uct ? TR_CU : 0), r));
+    *info = r.info;
+    const size_t ns = (size_t)r.info.n_steps, nc = (size_t)r.info.n_children_total;
+    if (step_move) memcpy(step_move, r.move.data(), ns * 2);
+    if (step_q) memcpy(step_q, r.q.data(), ns * 4);
+    if (child_off) memcpy(child_off, r.child_off.data(), (ns + 1) * 4);
+    if (child_move) memcpy(child_move, r.cmove.data(), nc * 2);
+    if (child_n) memcpy(child_n, r.cn.data(), nc * 4);
+    if (child_q) memcpy(child_q, r.cq.data(), nc * 4);
+    if (child_uct) memcpy(child_uct, r.cu.data(), nc * 4);
     return 0;
 }
 
@@ -201,20 +222,15 @@ int sc_selfplay_encode_traces(sc_selfplay* sp, int n, const int32_t* games, int 
 }
 
 int sc_selfplay_write_trace_json(sc_selfplay* sp, int game, const char* path) {
-    sc_trace_info info;
-    TRY(sc_selfplay_get_trace(sp, game, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-    std::vector<uint16_t> sm((size_t)info.n_steps + 1), cm((size_t)info.n_children_total + 1);
-    std::vector<float> sq((size_t)info.n_steps + 1), cq((size_t)info.n_children_total + 1), cu((size_t)info.n_children_total + 1);
-    std::vector<int32_t> co((size_t)info.n_steps + 2), cn((size_t)info.n_children_total + 1);
-    TRY(sc_selfplay_get_trace(sp, game, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data()));
+    TraceRow r;
+    TRY(sp_read_trace(sp, game, TR_ALL, r));
     const uint16_t* line = nullptr;
     const int len = sp_opening(sp, game, &line);
     const char* fen = sp_opening_fen(sp, game);
-    if (len == 0 && !fen) return sc_trace_write_json(path, &info, sm.data(), sq.data(), co.data(), cm.data(), cn.data(), cq.data(), cu.data());
-    // a game that started from an opening line: a third key, "opening", behind the reference's two; from a base: "fen" in front of it
     if (!path) return fail("bad argument");
-    return write_text_file(path, sctrace::trace_to_json(info.n_steps, info.has_outcome, info.termination, info.winner, sm.data(), sq.data(),
-                                                        co.data(), cm.data(), cn.data(), cq.data(), cu.data(), line, len, fen), false);
+    // a game that started from an opening line: a third key, "opening", behind the reference's two; from a base: "fen" in front of it
+    return write_text_file(path, sctrace::trace_to_json(r.info.n_steps, r.info.has_outcome, r.info.termination, r.info.winner, r.move.data(), r.q.data(),
+                                                        r.child_off.data(), r.cmove.data(), r.cn.data(), r.cq.data(), r.cu.data(), line, len, fen), false);
 }
 
 // Finished games as PGN: moves = opening line + played moves, rendered by one sc_moves_to_san_device_from call for the batch
@@ -227,26 +243,24 @@ int sc_selfplay_write_pgn(sc_selfplay* sp, int n, const int32_t* games, const ch
     std::vector<int32_t> base_idx((size_t)std::max(n, 1), -1);
     std::vector<const char*> fens;
     int pending = 0;
-    for (int i = 0; i < n; i++) {   // readiness of every game first (2 wins over 1, as sc_selfplay_encode_traces): nothing is written then
-        const int rc = sc_selfplay_get_trace(sp, games[i], &info[(size_t)i], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    TraceRow r;
+    for (int i = 0; i < n; i++) {   // every game must be ready (2 wins over 1, as sc_selfplay_encode_traces): nothing is written otherwise
+        const int rc = sp_read_trace(sp, games[i], TR_MOVE, r);
         if (rc < 0 || rc == 2) return rc;
         pending |= rc;
-    }
-    if (pending) return fail("game not finished", 1);
-    for (int i = 0; i < n; i++) {
+        if (rc) continue;
+        info[(size_t)i] = r.info;
         const uint16_t* line = nullptr;
         const int len = sp_opening(sp, games[i], &line);
         moves.insert(moves.end(), line, line + len);
-        const size_t at = moves.size();
-        moves.resize(at + (size_t)info[(size_t)i].n_steps + 1);
-        TRY(sc_selfplay_get_trace(sp, games[i], &info[(size_t)i], moves.data() + at, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-        moves.resize(at + (size_t)info[(size_t)i].n_steps);
+        moves.insert(moves.end(), r.move.begin(), r.move.begin() + r.info.n_steps);
         off.push_back((uint32_t)moves.size());
         if (const char* fen = sp_opening_fen(sp, games[i])) {
             base_idx[(size_t)i] = (int32_t)fens.size();
             fens.push_back(fen);
         }
     }
+    if (pending) return fail("game not finished", 1);
     const uint32_t P = off.back();
     std::vector<uint64_t> tok((size_t)P + 1);
     std::vector<int32_t> status((size_t)std::max(n, 1), 0);
@@ -302,10 +316,9 @@ int sc_selfplay_write_pgn(sc_selfplay* sp, int n, const int32_t* games, const ch
 int sc_selfplay_get_tree(sc_selfplay* sp, int slot, int cap, int32_t* n, float* q, float* uct, float* prior, uint16_t* move,
                          int32_t* first_child, int32_t* n_child) {
     if (!sp || slot < 0 || slot >= sp->p.n_slots) return fail("bad argument");
-    TRY(sp_quiesce(sp, false));
     const sc::SpParams& p = sp->p;
     sc::GameCtl c;
-    HIPOK(hipMemcpy(&c, p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
+    TRY(sp_read_ctl(sp, slot, &c));
     int nn = std::min(c.n_nodes, cap);
     size_t nb = (size_t)slot * p.node_cap;
     if (nn > 0) {
@@ -329,9 +342,8 @@ int sc_selfplay_get_tree(sc_selfplay* sp, int slot, int cap, int32_t* n, float* 
 int sc_selfplay_get_slot(sc_selfplay* sp, int slot, int32_t* ply, int32_t* sim, int32_t* status, uint64_t* game_id,
                          int32_t* last_path, int32_t* last_path_len) {
     if (!sp || slot < 0 || slot >= sp->p.n_slots) return fail("bad argument");
-    TRY(sp_quiesce(sp, false));
     sc::GameCtl c;
-    HIPOK(hipMemcpy(&c, sp->p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
+    TRY(sp_read_ctl(sp, slot, &c));
     if (ply) *ply = c.ply;
     if (sim) *sim = c.sim;
     if (status) *status = c.status;
@@ -368,12 +380,9 @@ int sc_selfplay_set_position_from(sc_selfplay* sp, int slot, const sc_positions*
         if (i < 0) return fail("sc_selfplay_set_position_from: bad base index");
         d_base += i;
     }
-    TRY(sp_quiesce(sp, false));
-    {
-        sc::GameCtl c;
-        HIPOK(hipMemcpy(&c, sp->p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
-        if (c.status == sc::ST_PENDING) return fail("slot is waiting for a trace-ring row: no game to reposition");
-    }
+    sc::GameCtl c;
+    TRY(sp_read_ctl(sp, slot, &c));
+    if (c.status == sc::ST_PENDING) return fail("slot is waiting for a trace-ring row: no game to reposition");
     ScopedDev<uint16_t> d_moves;
     HIPOK(d_moves.alloc((size_t)n_moves));
     if (n_moves) HIPOK(hipMemcpy(d_moves.p, moves, (size_t)n_moves * 2, hipMemcpyHostToDevice));
@@ -387,9 +396,8 @@ int sc_selfplay_set_position_from(sc_selfplay* sp, int slot, const sc_positions*
 // the ep square is printed, the text is formatted here
 int sc_selfplay_get_fen(sc_selfplay* sp, int slot, char* buf, int cap) {
     if (!sp || slot < 0 || slot >= sp->p.n_slots || cap < 0 || (cap > 0 && !buf)) return fail("bad argument");
-    TRY(sp_quiesce(sp, false));
     sc::GameCtl c;
-    HIPOK(hipMemcpy(&c, sp->p.ctl + slot, sizeof c, hipMemcpyDeviceToHost));
+    TRY(sp_read_ctl(sp, slot, &c));
     if (c.status != sc::ST_ACTIVE && c.status != sc::ST_FINISHED) return fail("sc_selfplay_get_fen: the slot holds no game");
     if (c.ply < 0 || c.ply >= sp->p.hist_cap) return fail("sc_selfplay_get_fen: the slot's ply is outside its chain");
     const sc::Position* d_rec = sp->p.hist + (size_t)slot * sp->p.hist_cap + c.ply;
@@ -402,13 +410,7 @@ int sc_selfplay_get_fen(sc_selfplay* sp, int slot, char* buf, int cap) {
     int32_t epl = 0;
     HIPOK(hipMemcpy(&rec, d_rec, sizeof rec, hipMemcpyDeviceToHost));
     HIPOK(hipMemcpy(&epl, d_epl.p, 4, hipMemcpyDeviceToHost));
-    const std::string s = position_fen(rec, epl != 0);
-    if (cap > 0) {
-        const size_t k = std::min(s.size(), (size_t)cap - 1);
-        memcpy(buf, s.data(), k);
-        buf[k] = 0;
-    }
-    return (int)s.size();
+    return copy_text(position_fen(rec, epl != 0), buf, cap);
 }
 
 // One search from a given position: the body of NNPlayer::bestmove (src/play.rs:241-252) / chess_play_mcts

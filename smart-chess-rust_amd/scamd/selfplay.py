@@ -1,4 +1,4 @@
-"""Batched self-play, searches, interactive play and matches (csrc/selfplay.hip, csrc/selfplay_io.hip); the two debug hooks."""
+"""Batched self-play, searches, interactive play and matches (csrc/selfplay.hip, csrc/match_play.hip, csrc/selfplay_io.hip); the two debug hooks (csrc/debug_calls.hip)."""
 import ctypes as C
 import math
 

@@ -128,6 +128,28 @@ def test_no_slot_idles_for_two_plies_while_games_remain(scamd):
     sp.close()
 
 
+@pytest.mark.parametrize("match", [False, True], ids=["plain", "match"])
+def test_a_handle_made_after_a_used_one_starts_clean(scamd, match):
+    """a handle's buffers are zero before its first launch, whatever the device memory held: the second handle is given what the
+    first one freed"""
+    cfg = {**HANDLE, "rollout_num": 8}
+    runs = []
+    for _ in range(2):
+        sp = scamd.SelfPlay(None, n_slots=4, n_games=4, num_steps=4, **cfg)
+        if match:
+            sp.set_match(None, None, SALT_A, SALT_B, colours=1)
+            assert sp.match_tally() == {k: dict.fromkeys(KEYS, 0) for k in ("a_white", "b_white")}
+        st = sp.stats()
+        assert [st[k] for k in ("sims_done", "nn_evals", "games_finished", "plies_done", "error_flags")] == [0] * 5, st
+        assert all(sp.slot(i)["ply"] == 0 and sp.slot(i)["sim"] == 0 for i in range(4))
+        sp.run()
+        assert sp.stats()["error_flags"] == 0
+        runs.append(([sp.trace(k) for k in range(4)], sp.match_tally() if match else None))
+        sp.close()
+    assert all(t is not None and len(t["steps"]) == 4 for t in runs[0][0])
+    assert runs[0] == runs[1]
+
+
 def _lockstep(scamd, white, black, cfg):
     sp = scamd.SelfPlay(white, n_slots=160, n_games=160, **cfg)
     sp.set_players(white, black)

@@ -173,6 +173,28 @@ def test_empty_line_changes_nothing(scamd, tmp_path):
     sp.close()
 
 
+def test_second_set_openings_replaces_the_first(scamd):
+    """a second call replaces the first one's table, moves and bases and draws the slots again: a handle given suite A (a base with
+    Black to move: padded records) and then suite B (an odd line, an empty one: not copied) is the handle given suite B alone"""
+    suite_a = [("rnbqkbnr/pppppppp/8/8/4P3/8/PPPP1PPP/RNBQKBNR b KQkq - 0 1", ["c7c5"]), ["d2d4", "d7d5"]]
+    suite_b = [["g1f3", "g8f6", "b1c3"], []]
+    cfg = dict(n_slots=2, n_games=4, num_steps=6, colours=1)
+    x = _match(scamd, suite_a, **cfg)
+    assert x.get_opening_fen(0) == suite_a[0][0] and x.get_opening(2) == suite_a[1]
+    x.set_openings(suite_b)
+    y = _match(scamd, suite_b, **cfg)
+    out = []
+    for sp in (x, y):
+        for k in range(4):
+            assert sp.get_opening(k) == suite_b[(k >> 1) % 2] and sp.get_opening_fen(k) is None, k
+        sp.run()
+        st = sp.stats()
+        assert st["error_flags"] == 0
+        out.append((st, sp.match_tally(), _finished(sp, 4)))   # (a trace: moves, root q, every child tuple, outcome)
+        sp.close()
+    assert out[0] == out[1]
+
+
 # ---------------------------------------------------------------------------------- 6. refusals
 FOOLS_MATE = "f2f3 e7e5 g2g4 d8h4".split()
 CLAIMABLE = "g1f3 g8f6 f3g1 f6g8 g1f3 g8f6 f3g1".split()   # f6g8 would repeat the start position for the third time
