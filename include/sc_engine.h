@@ -266,6 +266,41 @@ int sc_positions_count(const sc_positions*);
 int sc_positions_status(const sc_positions*, int i);
 int sc_positions_fen(const sc_positions*, int i, char* buf, int cap);
 
+/* ------------------------------------------------------------------ perft on the device: node counts, divide, move kinds */
+/* The legal move sequences of exactly `depth` moves from each of n entries, counted by the device rules (gen_legal_wave,
+ * make_move): the number every move generator is compared by.  All pointers are host pointers; the call is synchronous.
+ * Entry i is bases[base_idx[i]] followed by moves[move_off[i] .. move_off[i+1]), as sc_encode_positions_from reads them:
+ * base_idx[i] < 0, or base_idx == NULL, or bases == NULL: the start position; moves == NULL with move_off == NULL: no entry has
+ * moves.  A base whose status is negative refuses the call (-1, nothing is written); a base whose status is 1 is accepted.
+ *   status[i]   0, or -(j+1): move j of the entry's list is not legal.  Such an entry has nodes 0, zero kinds and n_div 0; the
+ *               other entries are not affected.
+ *   nodes[i]    the number of sequences; depth 0: 1.  Only "no legal move" ends a line: repetitions, the fifty-move count and
+ *               insufficient material do not, as in every published perft table.  depth: 0..16.
+ *   kinds[i][k] over the LAST moves of those sequences (the Chess Programming Wiki's columns): SC_PERFT_CAPTURES (en passant
+ *               included), _EP, _CASTLES, _PROMOTIONS, _CHECKS (the side to move after the last move is in check; mates are
+ *               included), _CHECKMATES.  Slot SC_PERFT_NODES repeats nodes[i], slot 7 is written 0; depth 0: slots 1-7 are 0.
+ *   divide      n_div[i]: the legal moves of entry i (0 at depth 0 and for a refused entry); div_moves[i][k]: those moves in the
+ *               generator's order (python-chess's), not sorted; div_nodes[i][k]: the sequences that begin with move k.  Both rows
+ *               are written 0 from n_div[i] on; the row of div_nodes sums to nodes[i].
+ * max_frontier: the node records (72 bytes) a level buffer holds; 0: 2^20; otherwise 256..2^24.  A level that outgrows it is
+ * walked in pieces; no output depends on it.  The call's device memory -- at most `depth` such buffers and 8 bytes per record of
+ * counts and offsets, plus the outputs -- is allocated for the call and freed when it returns.
+ * n: 0..2^24-1 (n == 0 is valid and touches nothing).  Integer sums only: identical calls give identical bytes.
+ * Returns 0, or < 0 as every entry point (-3: no HIP device; argument errors are found before a device is looked for).
+ * sc_perft_last_timing: measurement aid (tools/perft_rate.py) -- of the calling thread's last sc_perft, the HIP-event time of its
+ * kernel launches, summed over the stretches between two host reads, and the wall time of the whole call. */
+enum { SC_PERFT_NODES = 0, SC_PERFT_CAPTURES = 1, SC_PERFT_EP = 2, SC_PERFT_CASTLES = 3,
+       SC_PERFT_PROMOTIONS = 4, SC_PERFT_CHECKS = 5, SC_PERFT_CHECKMATES = 6 /* 7: reserved, written 0 */ };
+int sc_perft(int device_id, int n, const sc_positions* bases, const int32_t* base_idx,
+             const uint16_t* moves, const uint32_t* move_off, int depth, int max_frontier,
+             uint64_t* nodes      /* [n]            required   */,
+             uint64_t* kinds      /* [n][8]         or NULL    */,
+             uint16_t* div_moves  /* [n][224]       or NULL    */,
+             uint64_t* div_nodes  /* [n][224]       or NULL; NULL exactly when div_moves is */,
+             int32_t*  n_div      /* [n]            or NULL    */,
+             int32_t*  status     /* [n]            or NULL    */);
+int sc_perft_last_timing(float* kernels_ms, float* total_ms);
+
 /* sc_encode_positions with a base per position: position i is bases[base_idx[i]] followed by its moves; base_idx[i] < 0, or
  * base_idx == NULL, or bases == NULL: the start position, and the outputs are those of sc_encode_positions.  History planes
  * older than the base are zero; repetitions and the fifty-move count start at the base (its halfmove clock counts).  A base whose

@@ -9,6 +9,7 @@
 #include "batch_types.hpp"
 #include "merge_types.hpp"
 #include "encode_types.hpp"
+#include "perft_types.hpp"
 
 struct sc_fen_fields;   // include/sc_engine.h
 
@@ -75,4 +76,14 @@ void gather_batch(const scbt::GatherArgs& a, hipStream_t s);
 // merge_kernels.hip: identical rows of the compact training tensors -> one row each, targets averaged (sc_merge_positions); a.n_in > 0.
 // Enqueues everything on s; an error that is not HIP's own is named in *why
 hipError_t merge_positions(const scmg::MergeArgs& a, hipStream_t s, const char** why);
+// perft_kernels.hip: perft on the device (sc_perft); the argument blocks are perft_types.hpp's.  perft_roots: the entries of a chunk
+// replayed into level 0, their status and the divide rows' moves.  perft_count / perft_scan: legal moves per node, their exclusive
+// scan into d_off[0 .. n) and the total into d_off[n].  perft_expand: the children of a piece of a level into the next level.
+// perft_leaf: the last level -- counts (with lo.kinds: the kinds of every node's moves too) and their sums by root move
+void perft_roots(const scpf::RootArgs& a, hipStream_t s);
+void perft_div_ones(int n, const int32_t* d_n_div, unsigned long long* d_div_nodes, hipStream_t s);   // depth 1: a leaf per legal move
+void perft_count(const scpf::Level& lv, uint32_t* d_cnt, hipStream_t s);
+void perft_scan(uint32_t n, const uint32_t* d_cnt, uint32_t* d_tile_sum, uint32_t* d_off, hipStream_t s);
+void perft_expand(const scpf::ExpandArgs& a, hipStream_t s);
+void perft_leaf(const scpf::Level& lv, const scpf::LeafOut& lo, const scpf::Totals& t, hipStream_t s);
 }  // namespace scl

@@ -78,6 +78,8 @@ ABI = {
     "sc_positions_count": (_i, [_vp]),
     "sc_positions_status": (_i, [_vp, _i]),
     "sc_positions_fen": (_i, [_vp, _i, C.c_char_p, _i]),
+    "sc_perft": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_perft_last_timing": (_i, [C.POINTER(_f), C.POINTER(_f)]),
     "sc_encode_positions_from": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_encode_steps_device_from": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_encode_san_device_from": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
