@@ -111,6 +111,7 @@ def analyse(engine, fens, rollout, cpuct=2.5, best=None, evaluator="net", seed=0
             _check(sp.L.sc_selfplay_set_search(sp.h, cpuct, 0.15, 0))
             sp.enqueue(rollout)
             sp.sync()
+            sp.check_flags("analyse")   # (a blocked position searched deeper than 1024 levels: no numbers from such a tree)
             for i in range(n):
                 t = sp.tree(i)
                 fc, nc = (int(t["first_child"][0]), int(t["n_child"][0])) if t["n"].size and t["first_child"][0] >= 0 else (0, 0)

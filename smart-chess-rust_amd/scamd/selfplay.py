@@ -111,6 +111,17 @@ class SelfPlay(_Handle):
     def enable_timing(self, stride=1):
         _check(self.L.sc_selfplay_enable_timing(self.h, stride))
 
+    def check_flags(self, what):
+        """raises EngineError (.code -4, .flags) if the handle's error flags are set (sc_selfplay_stats.error_flags: 8 = a descent
+        reached the depth limit of 1024 path nodes): the trees of a flagged handle are not those of the search, as sc_search
+        refuses them"""
+        flags = self.stats()["error_flags"]
+        if flags:
+            e = EngineError(f"{what}: search error flags {flags} set (1 non-finite PUCT value, 2 node pool overflow, 4 move without "
+                            "action index, 8 path deeper than 1024 nodes, 16 / 32 hand-off timeout): the tree is invalid")
+            e.code, e.flags = -4, flags
+            raise e
+
     def launches_per_step(self):
         """1: fused step kernel with the value FC inside, 2: fused step kernel + value FC launch, 3: separate launches"""
         return int(self.L.sc_selfplay_launches_per_step(self.h))
@@ -311,10 +322,12 @@ class Play:
         return self.sp.fen(0)
 
     def mcts(self, rollout, cpuct=2.5, noise=False):
-        """chess_play_mcts: `rollout` more simulations on the current tree (epsilon 0.15 as lib.rs:243)"""
+        """chess_play_mcts: `rollout` more simulations on the current tree (epsilon 0.15 as lib.rs:243).  Raises EngineError when
+        the search sets an error flag (a path of more than 1024 nodes: a blocked position searched that deep)"""
         _check(self.sp.L.sc_selfplay_set_search(self.sp.h, cpuct, 0.15, int(bool(noise))))
         self.sp.enqueue(rollout)
         self.sp.sync()
+        self.sp.check_flags("Play.mcts")
 
     def _root_children(self):
         t = self.sp.tree(0)

@@ -1,5 +1,9 @@
-"""Test helpers (SAN parsing on top of the oracle's legal-move list)."""
+"""Test helpers: SAN parsing on top of the oracle's legal-move list, edge-case predicates, and the comparison of a device
+search tree with the oracle's (shared by the GPU search tests)."""
+import ctypes as C
 import random
+
+import numpy as np
 
 PT = {"N": 2, "B": 3, "R": 4, "Q": 5, "K": 6}
 
@@ -433,3 +437,56 @@ def load_edge_lines():
     import os
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "edge_lines.json")) as fh:
         return json.load(fh)
+
+
+# ------------------------------------------------------------------ device search tree against the oracle's
+def _same_tree(t, d):
+    """SelfPlay.tree(slot) equals Search.dump(): node count, N, value sums, uct words, moves, child counts"""
+    return (len(t["n"]) == len(d["n"]) and np.array_equal(t["n"], d["n"]) and np.array_equal(t["q"], d["q"])
+            and np.array_equal(t["uct"], d["uct"]) and np.array_equal(t["move"][1:], d["move"][1:])
+            and np.array_equal(t["n_child"], d["n_child"]))
+
+
+def assert_same_tree_bits(t, d, where):
+    """_same_tree on the bit patterns (-0.0 is not +0.0, a NaN equals itself), naming the first node that differs"""
+    assert len(t["n"]) == len(d["n"]), (where, "nodes", len(t["n"]), len(d["n"]))
+    for k in ("n", "q", "uct", "n_child"):
+        a, b = t[k].view(np.uint32), d[k].view(np.uint32)
+        assert np.array_equal(a, b), (where, k, np.flatnonzero(a != b)[:8])
+    assert np.array_equal(t["move"][1:], d["move"][1:]), (where, "move")
+    assert _same_tree(t, d), where
+
+
+class GpuPredictEvaluator:
+    """orc_eval_fn (oracle/sc_oracle_mcts.h) that answers with the ENGINE's `predict` on the oracle's own encoding of the
+    state: the post-_encode contract of src/backends/torch.rs:108-146."""
+
+    def __init__(self, orc, eng):
+        self.orc, self.eng, self.L = orc, eng, orc.lib()
+        self.priors = []          # one array per expansion, in allocation order of the children
+        self.values = []
+        self.fn = orc.EVAL_FN(self._call)
+
+    def _call(self, user, st, n_legal, legal, legal_idx, priors, value):
+        boards = np.zeros((8, 8, 112), np.int8)
+        meta = np.zeros(7, np.int32)
+        self.L.orc_encode(st, boards.ctypes.data_as(C.c_void_p), meta.ctypes.data_as(C.c_void_p))
+        idx = np.asarray([legal_idx[i] for i in range(n_legal)], np.uint16)
+        pri, val = self.eng.predict(boards[None], meta[None], [idx])
+        p = np.asarray(pri[0], np.float32)
+        for i in range(n_legal):
+            priors[i] = float(p[i])
+        value[0] = float(val[0])
+        self.priors.append(p.copy())
+        self.values.append(np.float32(val[0]))
+
+
+def _assert_same(t, d, ev, where):
+    """the tree of a search fed by the network against the oracle's tree fed by `ev`, bit for bit, priors included"""
+    n = len(d["n"])
+    assert len(t["n"]) == n, where
+    for k in ("n", "q", "uct", "n_child"):
+        assert np.array_equal(t[k].view(np.uint32), d[k].view(np.uint32)), (where, k, np.flatnonzero(t[k] != d[k])[:8])
+    assert np.array_equal(t["move"][1:], d["move"][1:]), where
+    pri = np.concatenate(ev.priors) if ev.priors else np.zeros(0, np.float32)
+    assert len(pri) == n - 1 and np.array_equal(t["prior"][1:].view(np.uint32), pri.view(np.uint32)), (where, "prior")

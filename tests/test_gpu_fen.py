@@ -9,6 +9,7 @@ from collections import Counter
 import numpy as np
 import pytest
 
+from helpers import _same_tree
 from san_ref import one_hot_steps, san_of, yardstick_moves
 from support import TENSORS, _p, _read, _sizes, assert_bit_equal, dev_per_test, run_san, scamd_gpu  # noqa: F401
 from test_oracle_rules import PERFT
@@ -161,12 +162,6 @@ def test_rules_and_encoder_from_a_base(scamd, fen, orc):
 
 
 # ---------------------------------------------------------------------------------- 3. search from a base
-def _same_tree(t, d):
-    return (len(t["n"]) == len(d["n"]) and np.array_equal(t["n"], d["n"]) and np.array_equal(t["q"], d["q"])
-            and np.array_equal(t["uct"], d["uct"]) and np.array_equal(t["move"][1:], d["move"][1:])
-            and np.array_equal(t["n_child"], d["n_child"]))
-
-
 def _oracle_search(orc, st, sims, depth=0, user=None):
     """sims = [(count, cpuct), ...] on a fresh oracle search of st"""
     srch = orc.Search(st, depth=depth)

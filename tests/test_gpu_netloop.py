@@ -13,13 +13,12 @@ prior in the last bit and shows up here.
 
 Second half: the same comparison in distribution against the fp32 oracle network (what the reference's libtorch backend
 computes, py/module.py:135-154), where bf16 / fp8 operand rounding makes the trees diverge chaotically."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
-from helpers import random_games
+from helpers import GpuPredictEvaluator, _assert_same, random_games  # noqa: F401
 from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -34,40 +33,6 @@ LINES = [
     ["g1f3", "g8f6", "f3g1", "f6g8", "g1f3", "g8f6", "f3g1"],  # repetition planes set, Black to move
 ]
 SLOTS = [0, 17, 31, 40, 63]
-
-
-class GpuPredictEvaluator:
-    """orc_eval_fn (oracle/sc_oracle_mcts.h) that answers with the ENGINE's `predict` on the oracle's own encoding of the
-    state: the post-_encode contract of src/backends/torch.rs:108-146."""
-
-    def __init__(self, orc, eng):
-        self.orc, self.eng, self.L = orc, eng, orc.lib()
-        self.priors = []          # one array per expansion, in allocation order of the children
-        self.values = []
-        self.fn = orc.EVAL_FN(self._call)
-
-    def _call(self, user, st, n_legal, legal, legal_idx, priors, value):
-        boards = np.zeros((8, 8, 112), np.int8)
-        meta = np.zeros(7, np.int32)
-        self.L.orc_encode(st, boards.ctypes.data_as(C.c_void_p), meta.ctypes.data_as(C.c_void_p))
-        idx = np.asarray([legal_idx[i] for i in range(n_legal)], np.uint16)
-        pri, val = self.eng.predict(boards[None], meta[None], [idx])
-        p = np.asarray(pri[0], np.float32)
-        for i in range(n_legal):
-            priors[i] = float(p[i])
-        value[0] = float(val[0])
-        self.priors.append(p.copy())
-        self.values.append(np.float32(val[0]))
-
-
-def _assert_same(t, d, ev, where):
-    n = len(d["n"])
-    assert len(t["n"]) == n, where
-    for k in ("n", "q", "uct", "n_child"):
-        assert np.array_equal(t[k].view(np.uint32), d[k].view(np.uint32)), (where, k, np.flatnonzero(t[k] != d[k])[:8])
-    assert np.array_equal(t["move"][1:], d["move"][1:]), where
-    pri = np.concatenate(ev.priors) if ev.priors else np.zeros(0, np.float32)
-    assert len(pri) == n - 1 and np.array_equal(t["prior"][1:].view(np.uint32), pri.view(np.uint32)), (where, "prior")
 
 
 CASES = [(10, 128, "bf16"), (10, 256, "bf16"), (10, 128, "fp8"), (3, 256, "fp8")]

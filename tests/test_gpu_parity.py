@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import random_games
+from helpers import _same_tree, random_games  # noqa: F401
 from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -166,12 +166,6 @@ def test_predict_argmax_branch(scamd, orc):
 
 
 # ---------------------------------------------------------------------------------- search (a1-a9, a20)
-def _same_tree(t, d):
-    return (len(t["n"]) == len(d["n"]) and np.array_equal(t["n"], d["n"]) and np.array_equal(t["q"], d["q"])
-            and np.array_equal(t["uct"], d["uct"]) and np.array_equal(t["move"][1:], d["move"][1:])
-            and np.array_equal(t["n_child"], d["n_child"]))
-
-
 @pytest.mark.parametrize("line", [[], ["e2e4", "c7c5", "g1f3"], ["f2f3", "e7e5", "g2g4"]])
 def test_search_lockstep_exact(scamd, orc, line):
     """every simulation: identical node pool (N, Q sums, uct, moves) and identical path"""

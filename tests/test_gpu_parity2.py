@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import random_games
+from helpers import _same_tree, random_games  # noqa: F401
 from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -29,12 +29,6 @@ WIDE137 = ("h2h4 g8h6 a2a4 h6g4 f2f4 g4h6 a4a5 h6g4 d2d4 g4f2 e1f2 b8a6 h4h5 a6b
            "d8e7 d5f7 d7d8q h8g8 e8f7 h7h8 h6h7 g8f8 b4b5 f8g8 b5b6 g8e8 b6b7 e8g8 b7b8q g8e8 "
            "h1h2 e8g8 c4c2 g8e8 e7e4 e8g8 a8a3 g8e8 f7e8 h8g7 f2g3 f3f2 e8e5 g7f7 h7h8q f2g1b").split()
 MATED = ["f2f3", "e7e5", "g2g4", "d8h4"]   # White is checkmated: a game set to this line ends after its first search
-
-
-def _same_tree(t, d):
-    return (len(t["n"]) == len(d["n"]) and np.array_equal(t["n"], d["n"]) and np.array_equal(t["q"], d["q"])
-            and np.array_equal(t["uct"], d["uct"]) and np.array_equal(t["move"][1:], d["move"][1:])
-            and np.array_equal(t["n_child"], d["n_child"]))
 
 
 def _pushed(orc, moves):
