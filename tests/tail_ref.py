@@ -150,20 +150,23 @@ def logp_closed(b):
     return np.repeat(b - lse, 64)
 
 
-def _fc(meta, Wm, b1, w2, b2, round_meta):
+def _fc(meta, Wm, b1, w2, b2, round_meta, feat=None):
+    """feat: the feature columns' share of FC1, [n][128] (tests/heads_ref.py); None where the probe zeroes those columns"""
     meta = np.asarray(meta, np.int32).reshape(-1, 7)
     m = np.asarray(bf16_rne(meta.astype(np.float32)) if round_meta else meta, np.float64)
     h = np.asarray(b1, np.float64)[None, :] + m @ np.asarray(Wm, np.float64).T
+    if feat is not None:
+        h = h + np.asarray(feat, np.float64)
     a = np.abs(np.asarray(b1, np.float64))[None, :] + np.abs(m) @ np.abs(np.asarray(Wm, np.float64)).T
     r = np.maximum(h, 0.0)
     s = r @ np.asarray(w2, np.float64) + b2
     return meta, a, r, s
 
 
-def value_closed(meta, Wm, b1, w2, b2, round_meta=True):
-    """float64 [n]: tanh(sum_j relu(b1[j] + sum_k bf16(meta[k]) Wm[j][k]) w2[j] + b2) (2 turn - 1).  round_meta=False is the
-    oracle's fp32 mode, which feeds meta unrounded (oracle/nn.c rounds it in the emulating modes only)"""
-    meta, _, _, s = _fc(meta, Wm, b1, w2, b2, round_meta)
+def value_closed(meta, Wm, b1, w2, b2, round_meta=True, feat=None):
+    """float64 [n]: tanh(sum_j relu(b1[j] + feat[j] + sum_k bf16(meta[k]) Wm[j][k]) w2[j] + b2) (2 turn - 1).  round_meta=False is
+    the oracle's fp32 mode, which feeds meta unrounded (oracle/nn.c rounds it in the emulating modes only)"""
+    meta, _, _, s = _fc(meta, Wm, b1, w2, b2, round_meta, feat)
     return np.tanh(s) * (2.0 * meta[:, 0] - 1.0)
 
 
@@ -181,8 +184,21 @@ def exp_rel(x):
 
 
 def logp_bound(b):
-    """float64 [4672]: |device logp - logp_closed(b)| per action.  Terms, for exact logits z (wave w = plane % 4 holds maximum m_w,
-    mx = max m_w, t_i = exp(z_i - mx)):
+    """float64 [4672]: |device logp - logp_closed(b)| per action: logp_bound_z of the logits b[ch] at every pixel"""
+    return logp_bound_z(np.repeat(np.asarray(b, np.float64), 64))
+
+
+def logp_closed_z(z):
+    """float64 [4672]: z - log sum exp z"""
+    z = np.asarray(z, np.float64)
+    mx = z.max()
+    return z - (mx + np.log(np.exp(z - mx).sum()))
+
+
+def logp_bound_z(z, dz=0.0):
+    """float64 [4672]: |device logp - logp_closed_z(z)| per action, for logits whose device copy is off by at most dz (elementwise:
+    its own dz, plus the t-weighted mean of dz through the sum of exponentials).  Terms, for exact logits z (wave w = plane % 4 holds
+    maximum m_w, mx = max m_w, t_i = exp(z_i - mx)):
       se     relative error of the sum of exponentials = the t-weighted mean of
              [ z_i - m_w rounded (|z_i - m_w| U) + EXP(z_i - m_w)               the lane's exponential
              + 18 U (per-lane 19-term sum) + 6 U (wave_sum_fixed)
@@ -191,8 +207,8 @@ def logp_bound(b):
       log    |ln se| LOG_REL + ln 2 * 2^-24
       lse    mx + log(se): |lse| U
       z-lse  |logp_i| U"""
-    b = np.asarray(b, np.float64)
-    z = np.repeat(b, 64)
+    z = np.asarray(z, np.float64)
+    dz = np.broadcast_to(np.asarray(dz, np.float64), z.shape)
     wave = (np.arange(4672) % 256) // 64
     mw = np.asarray([z[wave == w].max() for w in range(4)])
     mx = mw.max()
@@ -201,7 +217,7 @@ def logp_bound(b):
     se = t.sum()
     e_se = (t * (a * U + exp_rel(a) + r * U + exp_rel(r) + K_SE * U)).sum() / se + 2 * 4672 * TINY / se
     lse = mx + np.log(se)
-    return e_se + np.abs(np.log(se)) * LOG_REL + LN2 * U + np.abs(lse) * U + np.abs(z - lse) * U
+    return e_se + np.abs(np.log(se)) * LOG_REL + LN2 * U + np.abs(lse) * U + np.abs(z - lse) * U + dz + (t * dz).sum() / se
 
 
 def prior_bound(logp_row, idx, arg_err=0.0):
@@ -221,23 +237,23 @@ def prior_bound(logp_row, idx, arg_err=0.0):
     return rel * e / s + TINY / s, rel
 
 
-def value_bound(meta, Wm, b1, w2, b2, k_fc2=K_FC2_DEVICE, round_meta=True):
+def value_bound(meta, Wm, b1, w2, b2, k_fc2=K_FC2_DEVICE, round_meta=True, feat=None):
     """float64 [n]: |value - value_closed|.  Terms:
       FC1     14 roundings on |b1_j| + sum_k |m_k Wm_jk| per hidden unit (bias + 7 products, 7 additions; the zero partials add nothing)
       FC2     k_fc2 roundings on sum_j |relu_j w2_j| + |b2|: the lane's pair 3, wave_sum_fixed 6, the bias 1 (oracle: 129, sequential)
       tanh    the error of its argument times 1 - v^2 (taken at the nearer end of the argument's interval), TANH_REL |v| for the
               function, 1 U |v| for the rounding of the result (the sign factor is exact)"""
-    _, a, r, s = _fc(meta, Wm, b1, w2, b2, round_meta)
+    _, a, r, s = _fc(meta, Wm, b1, w2, b2, round_meta, feat)
     w2 = np.abs(np.asarray(w2, np.float64))
-    e_s = K_FC1 * U * (a @ w2) + k_fc2 * U * (r @ w2 + abs(b2))
+    e_s = K_FC1 * U * (a @ w2) + k_fc2 * U * (r @ w2 + abs(b2))           # the feature share: every partial sum exact (heads_ref)
     v = np.abs(np.tanh(s))
     slope = 1.0 - np.tanh(np.maximum(np.abs(s) - e_s, 0.0)) ** 2
     return slope * e_s + (TANH_REL + U) * v + TINY
 
 
-def value_args(meta, Wm, b1, w2, b2, round_meta=True):
+def value_args(meta, Wm, b1, w2, b2, round_meta=True, feat=None):
     """float64 [n]: the argument s of tanh (the tests check the probes' ranges on it)"""
-    return _fc(meta, Wm, b1, w2, b2, round_meta)[3]
+    return _fc(meta, Wm, b1, w2, b2, round_meta, feat)[3]
 
 
 # ------------------------------------------------------------------ index sets of the prior tests

@@ -116,20 +116,22 @@ def tie_margin(y, prec):
 
 
 # ------------------------------------------------------------------ LayerNorm, block epilogue: float64 value and fp32 bound
-def ln(x, g, e, dx=0.0):
+def ln(x, g, e, dx=0.0, k_s=None, k_inv=0):
     """LayerNorm over the last axis (eps 1e-6), no ReLU: -> (y, bound on |device y - y|) for exact input x whose device copy is off by
-    at most dx (elementwise)"""
+    at most dx (elementwise).  k_s: the roundings of the sum S where the width is no multiple of 128 (K_LN_S otherwise); k_inv: 1
+    where 1 / width is itself rounded (no power of two): one more rounding in the mean and in Q / C"""
     x = np.asarray(x, np.float64)
     C = x.shape[-1]
+    k_s, k_q = (K_LN_S(C), K_LN_Q(C)) if k_s is None else (k_s, k_s + 1)      # Q: the square's rounding on top
     dx = np.broadcast_to(np.asarray(dx, np.float64), x.shape)
     ax = np.abs(x)
     mean = x.mean(-1, keepdims=True)
     var = ((x - mean) ** 2).mean(-1, keepdims=True)
     q = (x * x).mean(-1, keepdims=True)                       # Q / C
-    d_mean = (K_LN_S(C) * U * ax.sum(-1, keepdims=True) + dx.sum(-1, keepdims=True)) / C + K_MEAN * U * np.abs(mean)
-    d_q = K_LN_Q(C) * U * q + 2 * (ax * dx).mean(-1, keepdims=True)
+    d_mean = (k_s * U * ax.sum(-1, keepdims=True) + dx.sum(-1, keepdims=True)) / C + (K_MEAN + k_inv) * U * np.abs(mean)
+    d_q = k_q * U * q + 2 * (ax * dx).mean(-1, keepdims=True)
     # the cancellation term: every rounding of Q/C and of mean^2 is relative to those, not to their difference
-    d_var = d_q + 2 * np.abs(mean) * d_mean + K_VAR * U * (q + mean * mean)
+    d_var = d_q + 2 * np.abs(mean) * d_mean + (K_VAR + k_inv) * U * (q + mean * mean)
     v = var + EPS
     rstd = v ** -0.5
     rel_rstd = 0.5 * (d_var + U * v) / v + (K_RSTD - 1) * U
