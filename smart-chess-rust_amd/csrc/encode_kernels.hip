@@ -22,23 +22,8 @@ __global__ __launch_bounds__(64) void k_encode_positions(GameWalk w, PlyRows row
     Position cur = chain_start(w.bases, g, true);
     if (lane == 0) hist[0] = cur;
     __syncthreads();
-    int status = 0;
-    int played = 0;
-    for (int i = 0; i < nm && i + 1 < w.hist_cap; i++) {
-        int nlm = 0;
-        gen_legal_wave(cur, s_moves, lane, nlm);
-        __syncthreads();
-        bool found = false;
-        for (int k = 0; k < nlm; k++)
-            if (s_moves[k] == mv[i]) found = true;
-        __syncthreads();
-        if (!found) {
-            status = -(i + 1);
-            break;
-        }
-        replay_step(cur, mv[i], i, hist, hist, &s_np, lane);
-        played = i + 1;
-    }
+    int status;
+    const int played = replay_checked(cur, mv, min(nm, w.hist_cap - 1), hist, s_moves, &s_np, lane, status);
     HistChain hc{hist};
     int n = 0;
     bool in_check = gen_legal_wave(cur, s_moves, lane, n);
@@ -259,9 +244,9 @@ __global__ __launch_bounds__(64) void k_steps_dist(int n, PlyMoves pm, Children 
     }
     __syncthreads();
     const move_t nx = pm.next_mv[g];
-    int has_next = 0, bad = 0;
+    const bool any_next = legal_has_move(s_lm, nl, nx, lane);
+    int bad = 0;
     uint32_t sum = 0;
-    for (int i = lane; i < nl; i += 64) has_next |= (s_lm[i] == nx) ? 1 : 0;
     for (int i = lane; i < nc; i += 64) {
         const move_t m = ch.mv[c0 + i];
         int k = -1;
@@ -286,7 +271,7 @@ __global__ __launch_bounds__(64) void k_steps_dist(int n, PlyMoves pm, Children 
         }
     if (o.dist_legal)
         for (int i = lane; i < MAXC; i += 64) o.dist_legal[(size_t)g * MAXC + i] = (i < nl && s_hit[i]) ? (float)s_cn[i] / den : 0.f;
-    const bool any_bad = __ballot(bad) != 0, any_next = __ballot(has_next) != 0;
+    const bool any_bad = __ballot(bad) != 0;
     if (lane == 0) {
         if (any_bad || !any_next) atomicMin(&status[idx.pgame[g]], (int32_t)(2 * idx.plen[g] + (any_bad ? 0 : 1)));
         if (o.n_legal) o.n_legal[g] = nl;

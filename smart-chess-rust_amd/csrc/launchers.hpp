@@ -3,6 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+namespace scl {
+// scan_kernels.hip: the exclusive scan of d_in[0 .. n) into d_out[0 .. n) and the total into *d_total, modulo 2^32; nothing for n == 0.
+// d_tile_sum: scratch of (n + SCAN_TILE - 1) / SCAN_TILE words, SCAN_TILE being the counts per workgroup (256 threads x 4).  Three
+// launches on s.  (Ahead of the type headers: merge_types.hpp lays out its workspace with SCAN_TILE)
+constexpr int SCAN_TILE = 1024;
+void exclusive_scan_u32(uint32_t n, const uint32_t* d_in, uint32_t* d_tile_sum, uint32_t* d_out, uint32_t* d_total, hipStream_t s);
+}  // namespace scl
+
 #include "mcts_types.hpp"
 #include "nn_types.hpp"
 #include "score_types.hpp"
@@ -77,13 +85,12 @@ void gather_batch(const scbt::GatherArgs& a, hipStream_t s);
 // Enqueues everything on s; an error that is not HIP's own is named in *why
 hipError_t merge_positions(const scmg::MergeArgs& a, hipStream_t s, const char** why);
 // perft_kernels.hip: perft on the device (sc_perft); the argument blocks are perft_types.hpp's.  perft_roots: the entries of a chunk
-// replayed into level 0, their status and the divide rows' moves.  perft_count / perft_scan: legal moves per node, their exclusive
-// scan into d_off[0 .. n) and the total into d_off[n].  perft_expand: the children of a piece of a level into the next level.
+// replayed into level 0, their status and the divide rows' moves.  perft_count: legal moves per node (perft.hip scans them into
+// d_off[0 .. n], the total last, with exclusive_scan_u32).  perft_expand: the children of a piece of a level into the next level.
 // perft_leaf: the last level -- counts (with lo.kinds: the kinds of every node's moves too) and their sums by root move
 void perft_roots(const scpf::RootArgs& a, hipStream_t s);
 void perft_div_ones(int n, const int32_t* d_n_div, unsigned long long* d_div_nodes, hipStream_t s);   // depth 1: a leaf per legal move
 void perft_count(const scpf::Level& lv, uint32_t* d_cnt, hipStream_t s);
-void perft_scan(uint32_t n, const uint32_t* d_cnt, uint32_t* d_tile_sum, uint32_t* d_off, hipStream_t s);
 void perft_expand(const scpf::ExpandArgs& a, hipStream_t s);
 void perft_leaf(const scpf::Level& lv, const scpf::LeafOut& lo, const scpf::Totals& t, hipStream_t s);
 }  // namespace scl

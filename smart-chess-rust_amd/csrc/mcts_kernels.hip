@@ -283,21 +283,8 @@ __global__ __launch_bounds__(64) void k_open_lines(int n_lines, const uint16_t* 
         hist[0] = cur;
     }
     __syncthreads();
-    int st = 0;
-    for (int j = 0; j < nm; j++) {
-        int nlm = 0;
-        gen_legal_wave(cur, s_moves, lane, nlm);
-        __syncthreads();
-        bool found = false;
-        for (int k = 0; k < nlm; k++)
-            if (s_moves[k] == mv[j]) found = true;
-        __syncthreads();
-        if (!found) {
-            st = -(j + 1);
-            break;
-        }
-        replay_step(cur, mv[j], j, hist, hist, &s_np, lane);
-    }
+    int st;
+    replay_checked(cur, mv, nm, hist, s_moves, &s_np, lane, st);
     if (st == 0) {
         int n = 0, winner = -1;
         gen_legal_wave(cur, s_moves, lane, n);

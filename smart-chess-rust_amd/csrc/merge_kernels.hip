@@ -15,10 +15,10 @@
 //       becomes a group of its own and is counted as a key clash.  No loop waits for another wave.
 //   k_verify       one wavefront per position: byte compare with the row of the key's head.  Equal: a member of that head.
 //       Different (a key clash): a group of its own, counted.
-//   k_scan_*       exclusive scan of the head flags (tile totals, their scan by one workgroup, tile-local scan): group numbers
-//       ascend with the head's position.
+//   (scan)         scl::exclusive_scan_u32 (scan_kernels.hip) of the head flags: group numbers ascend with the head's position,
+//       and the number of groups is counts[0].
 //   k_group        group_of, and the (group, position) pairs of a stable radix sort (rocPRIM, header-only) by group: members of
-//       a group in ascending position.  k_segments: where each group starts.
+//       a group in ascending position; thread 0 starts the largest count at 1.  k_segments: where each group starts.
 //   k_merge        one wavefront per group: the head's planes, meta, indices copied with 16-byte loads and stores; lane i owns
 //       share entries i, i + 64, i + 128, i + 192 and walks the members in order, the loads of 16 members issued before the
 //       first of their adds; s / (float) m is the IEEE division (no -ffast-math in this unit; v_div_scale / v_div_fmas /
@@ -201,72 +201,6 @@ __global__ __launch_bounds__(256) void k_verify(MergeArgs A, Ws W) {
     }
 }
 
-// ---- exclusive scan of flag -> gid: tile totals, their scan, the tiles
-__device__ __forceinline__ int block_excl_scan(int v, int* s_buf, int* total) {   // 256 threads; -> exclusive prefix of v
-    const int t = threadIdx.x;
-    s_buf[t] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int x = t >= o ? s_buf[t - o] : 0;
-        __syncthreads();
-        s_buf[t] += x;
-        __syncthreads();
-    }
-    const int incl = s_buf[t];
-    *total = s_buf[255];
-    __syncthreads();
-    return incl - v;
-}
-
-__device__ __forceinline__ int tile_flags(const Ws& W, int n, unsigned base, int f[4]) {
-    int sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const unsigned i = base + k;
-        f[k] = i < (unsigned)n ? W.flag[i] : 0;
-        sum += f[k];
-    }
-    return sum;
-}
-
-__global__ __launch_bounds__(256) void k_scan_tiles(int n, Ws W) {
-    __shared__ int s_buf[256];
-    int f[4], total;
-    const int v = tile_flags(W, n, blockIdx.x * (unsigned)SCAN_TILE + threadIdx.x * 4u, f);
-    block_excl_scan(v, s_buf, &total);
-    if (threadIdx.x == 0) W.tile_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_scan_sums(int n_tiles, Ws W) {   // one workgroup
-    __shared__ int s_buf[256];
-    int carry = 0;
-    for (int base = 0; base < n_tiles; base += 256) {
-        const int i = base + (int)threadIdx.x;
-        const int v = i < n_tiles ? W.tile_sum[i] : 0;
-        int total;
-        const int ex = block_excl_scan(v, s_buf, &total);
-        if (i < n_tiles) W.tile_sum[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        W.aux[0] = carry;                // the number of groups
-        W.aux[3] = carry > 0 ? 1 : 0;    // the largest m so far: k_merge raises it for every larger group
-    }
-}
-
-__global__ __launch_bounds__(256) void k_scan_apply(int n, Ws W) {
-    __shared__ int s_buf[256];
-    int f[4], total;
-    const unsigned base = blockIdx.x * (unsigned)SCAN_TILE + threadIdx.x * 4u;
-    const int v = tile_flags(W, n, base, f);
-    int at = W.tile_sum[blockIdx.x] + block_excl_scan(v, s_buf, &total);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (base + k < (unsigned)n) W.gid[base + k] = at;
-        at += f[k];
-    }
-}
-
 __global__ __launch_bounds__(256) void k_group(MergeArgs A, Ws W) {
     const unsigned p = blockIdx.x * 256u + threadIdx.x;
     if (p >= (unsigned)A.n_in) return;
@@ -275,6 +209,7 @@ __global__ __launch_bounds__(256) void k_group(MergeArgs A, Ws W) {
     if (A.group_of) A.group_of[p] = g;
     W.grp[p] = g < 0 ? (uint32_t)A.n_in : (uint32_t)g;
     W.pos[p] = (int)p;
+    if (p == 0) W.aux[3] = W.aux[0] > 0 ? 1 : 0;   // the largest m so far: k_merge raises it for every larger group
 }
 
 __global__ __launch_bounds__(256) void k_segments(int n, Ws W) {
@@ -375,7 +310,7 @@ __global__ __launch_bounds__(256) void k_merge(MergeArgs A, Ws W) {
         if (A.out_outcome) reinterpret_cast<uint32_t*>(A.out_outcome)[j] = oc_bits;
         if (A.out_count) A.out_count[j] = m;
         if (A.out_first) A.out_first[j] = p0;
-        // the largest m: groups of one are k_scan_sums' business, and a group no larger than what is already there has nothing
+        // the largest m: groups of one are k_group's business, and a group no larger than what is already there has nothing
         // to add -- one atomic per group on one address would serialise in the L2 and be most of the kernel's time
         if (m > 1 && m > __atomic_load_n(W.aux + 3, __ATOMIC_RELAXED)) atomicMax(W.aux + 3, m);
     }
@@ -420,13 +355,13 @@ hipError_t merge_positions(const scmg::MergeArgs& a, hipStream_t s, const char**
     if ((e = hipMemsetAsync(W.aux, 0, 32, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(W.slot_rep, 0xff, (size_t)L.slots * 4, s)) != hipSuccess) return e;    // -1: free
     if ((e = hipMemsetAsync(W.slot_head, 0x7f, (size_t)L.slots * 4, s)) != hipSuccess) return e;   // above every position
-    const unsigned waves = (unsigned)((n + 3) / 4), threads = (unsigned)((n + 255) / 256), tiles = (unsigned)((n + SCAN_TILE - 1) / SCAN_TILE);
+    const unsigned waves = (unsigned)((n + 3) / 4), threads = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_row_key, dim3(waves), dim3(256), 0, s, a, W);
     hipLaunchKernelGGL(k_find_head, dim3(threads), dim3(256), 0, s, a, W);
     hipLaunchKernelGGL(k_verify, dim3(waves), dim3(256), 0, s, a, W);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(256), 0, s, n, W);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(256), 0, s, (int)tiles, W);
-    hipLaunchKernelGGL(k_scan_apply, dim3(tiles), dim3(256), 0, s, n, W);
+    // flags are 0 or 1 and group numbers non-negative: the same bits as uint32; the number of groups goes to aux[0]
+    exclusive_scan_u32((uint32_t)n, reinterpret_cast<const uint32_t*>(W.flag), reinterpret_cast<uint32_t*>(W.tile_sum),
+                       reinterpret_cast<uint32_t*>(W.gid), reinterpret_cast<uint32_t*>(W.aux), s);
     hipLaunchKernelGGL(k_group, dim3(threads), dim3(256), 0, s, a, W);
     size_t sort_bytes = L.sort_bytes;
     e = rocprim::radix_sort_pairs(a.ws + L.sort_tmp, sort_bytes, W.grp, W.grp_sorted, W.pos, W.members, (size_t)n, 0u, bits, s, false);

@@ -1,5 +1,5 @@
 // merge_types.hpp -- kernel argument block and workspace layout of the position merge (merge_kernels.hip), shared by host code and
-// kernels.
+// kernels.  Included through launchers.hpp, whose scl::SCAN_TILE sizes the scan's region.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -36,8 +36,6 @@ struct Workspace {
     size_t bytes;
 };
 
-constexpr int SCAN_TILE = 1024;   // flags per workgroup of the scan
-
 inline Workspace workspace(int n_in) {
     Workspace w{};
     const size_t n = n_in > 0 ? (size_t)n_in : 1;
@@ -55,7 +53,7 @@ inline Workspace workspace(int n_in) {
     w.slot_of = take(n * 4);
     w.flag = take(n * 4);
     w.gid = take(n * 4);
-    w.tile_sum = take(((n + SCAN_TILE - 1) / SCAN_TILE) * 4);
+    w.tile_sum = take(((n + scl::SCAN_TILE - 1) / scl::SCAN_TILE) * 4);
     w.grp = take(n * 4);
     w.pos = take(n * 4);
     w.grp_sorted = take(n * 4);

@@ -64,7 +64,7 @@ int Walk::level(int L, uint32_t m) {
     }
     TRY(begin());
     scl::perft_count({buf[L].p, 0, m}, cnt[L].p, nullptr);
-    scl::perft_scan(m, cnt[L].p, tile_sum.p, off[L].p, nullptr);
+    scl::exclusive_scan_u32(m, cnt[L].p, tile_sum.p, off[L].p, off[L].p + m, nullptr);
     TRY(end());
     uint32_t total = 0;
     HIPOK(hipMemcpy(&total, off[L].p + m, 4, hipMemcpyDeviceToHost));
@@ -178,7 +178,7 @@ int sc_perft(int device_id, int n, const sc_positions* bases, const int32_t* bas
         const uint32_t widest = *std::max_element(w.cap, w.cap + depth);
         HIPOK(w.leaf_cnt.alloc(w.cap[depth - 1]));
         if (w.with_kinds) HIPOK(w.leaf_kinds.alloc(2 * (size_t)w.cap[depth - 1]));
-        HIPOK(w.tile_sum.alloc(widest / SCAN_TILE + 1));
+        HIPOK(w.tile_sum.alloc(widest / scl::SCAN_TILE + 1));
     }
     HIPOK(hipEventCreate(&w.ev0));
     HIPOK(hipEventCreate(&w.ev1));

@@ -6,12 +6,12 @@
 // holds a workgroup barrier between them (wave_sync orders a wave's LDS stores and loads) and none waits for another workgroup.
 //
 //   k_perft_roots      one wavefront per entry: its base or the start position, its moves replayed with every move looked up
-//       among the generated legal moves (lane-parallel, one ballot), the root record or the failing ply; the legal moves of the
+//       among the generated legal moves (legal_has_move), the root record or the failing ply; the legal moves of the
 //       root are the divide row's moves.
 //   k_perft_count      legal moves per node -> uint32.  On the last level that is the node's share of the total ("bulk counting":
 //       no record is made for depth `depth`).
-//   k_perft_scan_*     exclusive scan of the counts (tile totals, their scan by one workgroup, the tiles): a node's first child
-//       slot.  Children lie in frontier order and, within a node, in generator order: the oracle's enumeration order.
+//   (scan)             the host scans the counts with scl::exclusive_scan_u32 (scan_kernels.hip): a node's first child slot, the
+//       total behind the last.  Children lie in frontier order and, within a node, in generator order: the oracle's enumeration order.
 //   k_perft_expand     generates again -- 6 k cycles of a wave that would otherwise wait for a 448-byte row to come back from
 //       HBM, and 448 B a node is six times the record -- then lane l makes children l, l + 64, l + 128, l + 192 with the scalar
 //       make_move<false> on its own registers and stores them at the node's offset.  The count is compared with the scan's.
@@ -60,18 +60,13 @@ __device__ __forceinline__ void store_node(Node* dst, const Position& p, uint32_
     dst->pad = 0;
     dst->root = root;
 }
-// the value lane `sel` holds (sel wave-uniform), in every lane
-__device__ __forceinline__ bb_t from_lane(bb_t v, int sel) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, sel);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), sel);
-    return ((bb_t)hi << 32) | lo;
-}
+// the board lane `sel` holds (sel wave-uniform), in every lane
 __device__ __forceinline__ Position from_lane(const Position& q, int sel) {
     Position r;
 #pragma unroll
-    for (int t = 0; t < 6; t++) r.pcs[t] = from_lane(q.pcs[t], sel);
-    r.occ[0] = from_lane(q.occ[0], sel);
-    r.occ[1] = from_lane(q.occ[1], sel);
+    for (int t = 0; t < 6; t++) r.pcs[t] = scw::from_lane(q.pcs[t], sel);
+    r.occ[0] = scw::from_lane(q.occ[0], sel);
+    r.occ[1] = scw::from_lane(q.occ[1], sel);
     r.key = 0;
     r.turn = (uint8_t)__builtin_amdgcn_readlane((int)q.turn, sel);
     r.castling = (uint8_t)__builtin_amdgcn_readlane((int)q.castling, sel);
@@ -98,9 +93,7 @@ __global__ __launch_bounds__(64) void k_perft_roots(RootArgs a) {
         int nl = 0;
         gen_legal_wave(cur, s_moves, lane, nl);
         wave_sync();
-        bool hit = false;
-        for (int k = lane; k < nl; k += 64) hit |= s_moves[k] == mv;
-        const bool found = __ballot(hit) != 0;
+        const bool found = legal_has_move(s_moves, nl, mv, lane);
         wave_sync();   // the list is read before the next generation writes it
         if (!found) {
             st = -(int)(q - m0 + 1);
@@ -145,64 +138,6 @@ __global__ __launch_bounds__(256) void k_perft_count(Level lv, uint32_t* cnt) {
         gen_legal_wave(p, s_moves[wv], lane, nl);
     }
     if (lane == 0) cnt[lv.first + i] = (uint32_t)nl;
-}
-
-// ------------------------------------------------------------------ exclusive scan of the counts
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_buf, uint32_t* total) {   // 256 threads
-    const int t = threadIdx.x;
-    s_buf[t] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const uint32_t x = t >= o ? s_buf[t - o] : 0u;
-        __syncthreads();
-        s_buf[t] += x;
-        __syncthreads();
-    }
-    const uint32_t incl = s_buf[t];
-    *total = s_buf[255];
-    __syncthreads();
-    return incl - v;
-}
-__device__ __forceinline__ uint32_t tile_counts(const uint32_t* cnt, uint32_t n, uint32_t base, uint32_t f[4]) {
-    uint32_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        f[k] = base + k < n ? cnt[base + k] : 0u;
-        sum += f[k];
-    }
-    return sum;
-}
-__global__ __launch_bounds__(256) void k_perft_scan_tiles(uint32_t n, const uint32_t* cnt, uint32_t* tile_sum) {
-    __shared__ uint32_t s_buf[256];
-    uint32_t f[4], total;
-    const uint32_t v = tile_counts(cnt, n, blockIdx.x * (uint32_t)SCAN_TILE + threadIdx.x * 4u, f);
-    block_excl_scan(v, s_buf, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-__global__ __launch_bounds__(256) void k_perft_scan_sums(uint32_t n_tiles, uint32_t* tile_sum, uint32_t* total_out) {   // one workgroup
-    __shared__ uint32_t s_buf[256];
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < n_tiles; base += 256) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t v = i < n_tiles ? tile_sum[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_excl_scan(v, s_buf, &total);
-        if (i < n_tiles) tile_sum[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) *total_out = carry;
-}
-__global__ __launch_bounds__(256) void k_perft_scan_apply(uint32_t n, const uint32_t* cnt, const uint32_t* tile_sum, uint32_t* off) {
-    __shared__ uint32_t s_buf[256];
-    uint32_t f[4], total;
-    const uint32_t base = blockIdx.x * (uint32_t)SCAN_TILE + threadIdx.x * 4u;
-    const uint32_t v = tile_counts(cnt, n, base, f);
-    uint32_t at = tile_sum[blockIdx.x] + block_excl_scan(v, s_buf, &total);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        if (base + k < n) off[base + k] = at;
-        at += f[k];
-    }
 }
 
 // ------------------------------------------------------------------ expand
@@ -376,13 +311,6 @@ void perft_div_ones(int n, const int32_t* d_n_div, unsigned long long* d_div_nod
 void perft_count(const Level& lv, uint32_t* d_cnt, hipStream_t s) {
     if (lv.n == 0) return;
     hipLaunchKernelGGL(k_perft_count, dim3((lv.n + 3) / 4), dim3(256), 0, s, lv, d_cnt);
-}
-void perft_scan(uint32_t n, const uint32_t* d_cnt, uint32_t* d_tile_sum, uint32_t* d_off, hipStream_t s) {
-    if (n == 0) return;
-    const unsigned tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    hipLaunchKernelGGL(k_perft_scan_tiles, dim3(tiles), dim3(256), 0, s, n, d_cnt, d_tile_sum);
-    hipLaunchKernelGGL(k_perft_scan_sums, dim3(1), dim3(256), 0, s, tiles, d_tile_sum, d_off + n);
-    hipLaunchKernelGGL(k_perft_scan_apply, dim3(tiles), dim3(256), 0, s, n, d_cnt, d_tile_sum, d_off);
 }
 void perft_expand(const ExpandArgs& a, hipStream_t s) {
     if (a.lv.n == 0) return;

@@ -10,7 +10,6 @@ constexpr int KINDS = 8;                  // a kinds row: SC_PERFT_* and one res
 constexpr uint32_t DEAD = 0xffffffffu;    // Node::root of a refused entry: it has no children and counts nothing
 constexpr uint32_t NO_MOVE = 255;         // the move byte of Node::root at level 0: the root itself, no move yet (a row has 224)
 constexpr int MAX_ENTRIES = (1 << 24) - 1;   // entry << 8 | move is one 32-bit number, and DEAD is none of them
-constexpr int SCAN_TILE = 1024;           // counts per workgroup of the scan kernels (256 threads x 4)
 constexpr int ATTR_RUN = 16;              // consecutive nodes per thread of k_perft_attribute: 4 096 per workgroup
 
 // A frontier node: the board half of sc::Position -- no key, no clocks, no flags: a generation reads none of them and

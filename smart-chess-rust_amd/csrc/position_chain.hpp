@@ -1,5 +1,6 @@
 // position_chain.hpp -- the chain of positions a wave looks back over (game line, tree path, leaf), its repetition scan,
-// the plane encoder (_encode) and the replay step of the kernels that rebuild a line from its moves.  Device functions only.
+// the plane encoder (_encode), and for the kernels that rebuild a line from its moves the replay step, the lookup of a move among
+// the legal moves and the checked replay made of the two.  Device functions only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -177,6 +178,35 @@ __device__ inline void replay_step(Position& cur, move_t m, int i, Position* his
     if (lane == 0) hist[i + 1] = cur;
     __threadfence_block();
     __syncthreads();
+}
+
+// Is mv among the generated legal moves s_moves[0 .. nl) (LDS)?  Lane-parallel: rounds of 64 and one ballot; the result is
+// wave-uniform.  No barrier in here: the caller orders the list's stores before it and the next generation behind it.
+__device__ __forceinline__ bool legal_has_move(const move_t* s_moves, int nl, move_t mv, int lane) {
+    bool hit = false;
+    for (int k = lane; k < nl; k += 64) hit |= s_moves[k] == mv;
+    return __ballot(hit) != 0;
+}
+
+// The checked replay of a one-wave workgroup: plays mv[0 .. n) from cur (= hist[0]) into hist[1 ..] with replay_step, every move
+// looked up among the legal moves first, and stops in front of the first that is absent.  -> the number of moves played;
+// status: 0, or -(i + 1) for an illegal move i.  s_moves [MAXC] and s_np are the caller's LDS.
+__device__ inline int replay_checked(Position& cur, const uint16_t* mv, int n, Position* hist, move_t* s_moves, Position* s_np, int lane,
+                                     int& status) {
+    status = 0;
+    for (int i = 0; i < n; i++) {
+        int nl = 0;
+        gen_legal_wave(cur, s_moves, lane, nl);
+        __syncthreads();
+        const bool found = legal_has_move(s_moves, nl, mv[i], lane);
+        __syncthreads();
+        if (!found) {
+            status = -(i + 1);
+            return i;
+        }
+        replay_step(cur, mv[i], i, hist, hist, s_np, lane);
+    }
+    return n;
 }
 
 }  // namespace sc

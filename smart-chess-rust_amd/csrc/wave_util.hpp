@@ -66,5 +66,11 @@ __device__ __forceinline__ uint64_t uniform(uint64_t v) {
     unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
     return ((uint64_t)hi << 32) | lo;
 }
+// ... and the value lane `sel` holds (sel wave-uniform), in every lane
+__device__ __forceinline__ uint64_t from_lane(uint64_t v, int sel) {
+    unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, sel);
+    unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), sel);
+    return ((uint64_t)hi << 32) | lo;
+}
 
 }  // namespace scw

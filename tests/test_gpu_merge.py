@@ -362,6 +362,40 @@ def test_two_million_positions_over_few_rows(scamd, dev):
         assert _same(got["outcome"][j:j + 1], mean[nl:]), j
 
 
+# ------------------------------------------------------------------ group heads at the edges of the scan's tiles
+def test_group_heads_at_the_scan_tile_edges(scamd, dev):
+    """257 * 1024 + 2 positions -- more tiles than the scan's sums kernel carries in one round, the last tile of two -- over 13
+    source rows that first appear at the first, second and last position of tiles 0, 1, 256 and 257: every tile carry and every
+    in-tile offset the group numbers depend on is non-zero somewhere.  Only the small outputs are asked for; the yardstick is
+    numpy, over every position"""
+    T = 1024
+    n = 257 * T + 2
+    heads = np.array([0, 1, T - 1, T, T + 1, 2 * T - 1, 2 * T, 256 * T - 1, 256 * T, 256 * T + 1, 257 * T - 1, 257 * T, n - 1], np.int64)
+    src = merge_ref.make_source(13)
+    seen = np.searchsorted(heads, np.arange(n), side="left")           # the source rows that appeared before position p
+    rows = (np.random.default_rng(17).random(n) * seen).astype(np.int32)   # one of them (position 0 is a head)
+    rows[heads] = np.arange(13, dtype=np.int32)
+    first = np.full(13, n, np.int64)
+    np.minimum.at(first, rows, np.arange(n))
+    assert first.tolist() == heads.tolist()                             # row j is new at heads[j] and nowhere earlier
+    L = scamd.lib()
+    need = C.c_size_t(0)
+    assert L.sc_merge_positions_workspace(n, C.byref(need)) == 0
+    ws = dev.alloc(need.value)
+    outs = {k: (dev.alloc(13 * ROW_BYTES[k]) if k in ("count", "first") else None) for k in OUT}
+    group_of, counts = dev.alloc(n * 4), dev.alloc(16)
+    d_src = upload(dev, src)
+    rc = L.sc_merge_positions(0, 13, n, dev.upload(rows), *[d_src[k] for k in KEYS], 128, ws, need.value, dev.stream,
+                              *[outs[k] for k in OUT], group_of, counts)
+    assert rc == 0, L.sc_last_error().decode()
+    dev.sync()
+    m = np.bincount(rows, minlength=13)
+    assert dev.read(counts, (4,), np.int32).tolist() == [13, 0, 0, int(m.max())]
+    assert _same(dev.read(group_of, (n,), np.int32), rows)              # rank by first appearance = the row's own number here
+    assert dev.read(outs["first"], (13,), np.int32).tolist() == heads.tolist()
+    assert dev.read(outs["count"], (13,), np.int32).tolist() == m.tolist()
+
+
 # ------------------------------------------------------------------ 9: the loader, with torch
 _CHILD = r'''
 import json, sys

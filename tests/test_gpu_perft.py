@@ -242,6 +242,47 @@ def test_wide_position(scamd, fen, orc):
     assert int(r["nodes"][0]) == 19073
 
 
+def _absent_move(st):
+    """a from-to pair that none of st's legal moves has"""
+    pairs = {m & 0xfff for m in st.legal_moves()}
+    return next(m for m in range(1, 4096) if (m & 63) != (m >> 6) and m not in pairs)
+
+
+def test_the_move_lookup_at_every_round_of_the_legal_list(scamd, fen, orc):
+    """the 218 moves of WIDE fill three rounds of 64 lanes and 26 lanes of a fourth: one-move lines through the first and last move
+    of every round, a move that is in no round, and an absent move behind a legal one, through the three callers of the lookup
+    that take move lists -- the position encoder, the opening lines of a match handle and perft's roots"""
+    root = orc.State(perft_ref.WIDE)
+    legal = root.legal_moves()
+    assert len(legal) == 218
+    lines = [[legal[k]] for k in (0, 63, 64, 127, 128, 191, 192, 217)]
+    after = []
+    for ln in lines:
+        st = root.copy()
+        st.push(ln[0])
+        after.append(st)
+    lines += [[_absent_move(root)], [legal[0], _absent_move(after[0])]]
+    fens = [perft_ref.WIDE] * 10
+    enc = scamd.encode_positions(lines, fens=fens)
+    assert enc["status"].tolist() == [0] * 8 + [-1, -2]
+    for i, st in enumerate(after):
+        ob, om = st.encode()
+        assert np.array_equal(enc["boards"][i], ob) and np.array_equal(enc["meta"][i], om), i
+        assert enc["legal_moves"][i].tolist() == st.legal_moves(), i
+    sp = scamd.SelfPlay(None, evaluator="synth", seed=5, with_noise=False, outcome_gate=-1, rollout_num=20, n_slots=2, n_games=2, num_steps=3)
+    sp.set_match(None, None, 11, 22, colours=1)
+    with pytest.raises(scamd.EngineError) as e:
+        sp.set_openings(list(zip(fens, lines)))
+    sp.close()
+    over = [int(st.outcome() is not None or not st.legal_moves()) for st in after]
+    assert e.value.code == -1 and e.value.status == over + [-1, -2]
+    r = run(scamd, fen, list(zip(fens, lines)), 1, guard=1)
+    assert r["status"].tolist() == [0] * 8 + [-1, -2]
+    assert r["nodes"].tolist() == [st.perft(1) for st in after] + [0, 0]
+    for i, st in enumerate(after):
+        assert r["div_moves"][i, :r["n_div"][i]].tolist() == st.legal_moves(), i
+
+
 def test_mixed_entries_and_an_illegal_move(scamd, fen, orc):
     """FEN bases, the start position (base_idx -1) and move lists in one call; an illegal move in one list gives -(j+1) there and
     leaves its neighbours as they are without it"""
