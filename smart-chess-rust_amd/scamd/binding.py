@@ -176,12 +176,35 @@ def lib():
     return L
 
 
+_HIP_ABI = {
+    "hipMalloc": [C.POINTER(_vp), C.c_size_t],
+    "hipFree": [_vp],
+    "hipMemcpy": [_vp, _vp, C.c_size_t, _i],
+    "hipMemset": [_vp, _i, C.c_size_t],
+    "hipStreamCreate": [C.POINTER(_vp)],
+    "hipStreamSynchronize": [_vp],
+    "hipStreamDestroy": [_vp],
+    "hipEventCreate": [C.POINTER(_vp)],
+    "hipEventRecord": [_vp, _vp],
+    "hipEventElapsedTime": [C.POINTER(C.c_float), _vp, _vp],
+    "hipEventDestroy": [_vp],
+}
+_hip = None
+
+
 def hip_runtime():
-    """ctypes handle of the HIP runtime libsc_engine.so uses (device buffers for the *_device entry points without torch)"""
-    lib()
-    if len(_engine_hip) != 1:
-        raise EngineError(f"cannot tell which HIP runtime libsc_engine.so uses: {_engine_hip}")
-    return C.CDLL(_engine_hip[0])
+    """ctypes handle of the HIP runtime libsc_engine.so uses (device buffers for the *_device entry points without torch): one per
+    process, with the argument types of the runtime calls the project makes through it"""
+    global _hip
+    if _hip is None:
+        lib()
+        if len(_engine_hip) != 1:
+            raise EngineError(f"cannot tell which HIP runtime libsc_engine.so uses: {_engine_hip}")
+        H = C.CDLL(_engine_hip[0])
+        for name, args in _HIP_ABI.items():
+            getattr(H, name).argtypes = args
+        _hip = H
+    return _hip
 
 
 def _check(rc):

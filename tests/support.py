@@ -39,13 +39,6 @@ class Dev:
     def __init__(self, scamd, fill=0x5a):
         self.fill = fill
         self.hip = scamd.hip_runtime()
-        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.hip.hipFree.argtypes = [C.c_void_p]
-        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-        self.hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-        self.hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-        self.hip.hipStreamDestroy.argtypes = [C.c_void_p]
         self.bufs = []
         s = C.c_void_p()
         assert self.hip.hipStreamCreate(C.byref(s)) == 0

@@ -1,7 +1,7 @@
 """Rate of sc_positions_from_fen: FEN text -> validated records in device memory, for a suite of a few thousand positions.
-Prints one JSON line.
+Prints one JSON line and appends it to profiles/fen_rate_<date>.jsonl (--out).
 
-  python tools/fen_rate.py [--positions 4096] [--reps 7]
+  python tools/fen_rate.py [--positions 4096] [--reps 7] [--out FILE]
 
 The positions are those of synthetic self-play games (256 slots, one position per slot and ply, read back with
 sc_selfplay_get_fen), so they are legal, mostly distinct and spread over openings and middlegames.  call_ms: host wall time of
@@ -10,16 +10,9 @@ k_fen_ep_legal, the download of records and status; the call synchronises.  pars
 (host only).  Medians over --reps regions after one warm-up call, [min, max] beside them."""
 import argparse
 import ctypes as C
-import datetime
-import json
-import os
-import socket
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
+from ratelib import emit, record, require_device, spread  # sets the package path
 
 import scamd  # noqa: E402
 import scamd.fen  # noqa: E402
@@ -40,16 +33,16 @@ def suite(n):
 
 
 def med(xs):
-    return [round(statistics.median(xs), 4), round(min(xs), 4), round(max(xs), 4)]
+    return [round(x, 4) for x in spread(xs)]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--positions", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=None, help="result file (default profiles/fen_rate_<date>.jsonl)")
     args = ap.parse_args()
-    if scamd.lib().sc_device_count() <= 0:
-        raise SystemExit("no HIP device")
+    require_device()
     fens = suite(args.positions)
     call, parse = [], []
     for r in range(args.reps + 1):
@@ -68,9 +61,9 @@ def main():
             call.append((t1 - t0) * 1e3)
             parse.append((t3 - t2) * 1e3)
     m = med(call)
-    print(json.dumps(dict(tool="fen_rate", date=datetime.date.today().isoformat(), host=socket.gethostname(), positions=len(fens),
-                          distinct=len(set(fens)), reps=args.reps, call_ms=m, positions_per_s=round(len(fens) / (m[0] * 1e-3)),
-                          parse_loop_ms=med(parse), note="call_ms includes the Python binding's encoding of the texts; parse_loop_ms is a ctypes loop")))
+    emit([record("fen_rate", positions=len(fens), distinct=len(set(fens)), reps=args.reps, call_ms=m, positions_per_s=round(len(fens) / (m[0] * 1e-3)),
+                 parse_loop_ms=med(parse), note="call_ms includes the Python binding's encoding of the texts; parse_loop_ms is a ctypes loop")],
+         args.out, "fen_rate")
 
 
 if __name__ == "__main__":

@@ -17,13 +17,11 @@ the whole scamd.play_match call, traces included.  Rows go to stdout and to --ou
 """
 import argparse
 import datetime
-import json
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
+from ratelib import ROOT, emit, require_device  # sets the package path
+
 import scamd  # noqa: E402
 
 SEARCH = dict(cpuct=1.5, temperature=0.0, temperature_switch=0, num_steps=200)
@@ -111,8 +109,7 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--openings", default=None, help="opening file for case o (tools/make_openings.py)")
     args = ap.parse_args()
-    if scamd.lib().sc_device_count() <= 0:
-        raise SystemExit("no HIP device")
+    require_device()
     a, b = scamd.Engine(args.blocks, 128, seed=1), scamd.Engine(args.blocks, 128, seed=2)
     plan = {"a": (100, [("lockstep", None), ("recycled", 200), ("recycled", 128)]), "b": (1024, [("lockstep", None), ("recycled", 256)]),
             "o": (100, [("recycled", 128)] + ([("openings", 128)] if args.openings else []))}
@@ -132,12 +129,8 @@ def main():
                 t0 = time.perf_counter()
                 scamd.play_match(a, b, n_games=n_games, rollout=args.rollout, seed=args.seed, swap=True, concurrency=conc, **SEARCH)
                 row["play_match_seconds"] = round(time.perf_counter() - t0, 3)
+            emit([row], args.out, "match_time", mode="a" if rows else "w")   # a run's rows replace the file's
             rows.append(row)
-            print(json.dumps(row), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        for row in rows:
-            f.write(json.dumps(row) + "\n")
     a.close()
     b.close()
 

@@ -1,6 +1,6 @@
 """Rate of merging identical training positions: sc_merge_positions (csrc/merge_kernels.hip) next to the route that exists without
 it -- torch.unique(dim=0, return_inverse=True) over the rows' sample bytes, then index_add_ and a division -- in the same visit,
-on the plies of the 256-game trace set of tools/encode_device_rate.py.  Appends one JSON line per row to
+on the plies of the 256-game trace set of tools/ratelib.py.  Appends one JSON line per row to
 profiles/merge_rate_<date>.jsonl and prints them.
 
   python tools/merge_rate.py [--reps 7] [--iters 5]
@@ -17,22 +17,13 @@ compare and the merge read again what is then in the caches).  The two routes' p
 The last line is the diversity report of the run (scamd.replay.unique_by_ply): plies and distinct samples per ply index."""
 import argparse
 import ctypes as C
-import datetime
-import json
-import os
-import socket
-import statistics
-import sys
 
 import torch  # before scamd: one HIP runtime in the process
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ratelib import common_args, emit, record, require_device, spread, timed_torch, trace_set  # sets the package path
 
 import scamd  # noqa: E402
 from scamd import replay  # noqa: E402
-from encode_device_rate import trace_set  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # bench.py's figure
 PLY_B = 8548
@@ -66,15 +57,11 @@ def by_first_position(inv):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
+    common_args(ap, reps=7)
     ap.add_argument("--iters", type=int, default=5, help="calls per timed region")
-    ap.add_argument("--blocks", type=int, default=10)
-    ap.add_argument("--channels", type=int, default=128)
     ap.add_argument("--out", default=None, help="result file (default profiles/merge_rate_<date>.jsonl)")
     args = ap.parse_args()
-    L = scamd.lib()
-    if L.sc_device_count() <= 0:
-        raise SystemExit("no HIP device")
+    L = require_device()
     dev = torch.device("cuda", 0)
     torch.zeros(1, device=dev)
     eng = scamd.Engine(args.blocks, args.channels, seed=1)
@@ -98,20 +85,8 @@ def main():
     tol = int(m["count"].max()) * 2.0 ** -23   # shares and outcomes within [-1, 1]: m additions in another order, half an ulp of 1 each way
     assert max_diff <= tol and float((m["outcome"] - t_oc[head]).abs().max()) <= tol
 
-    def timed(call):
-        for _ in range(args.iters):
-            call()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(args.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for _ in range(args.iters):
-                call()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1) / args.iters)
-        return statistics.median(ms), min(ms), max(ms)
+    def measure(call):
+        return spread(timed_torch(call, args.reps, args.iters, stream))
 
     need = C.c_size_t(0)
     assert L.sc_merge_positions_workspace(P, C.byref(need)) == 0
@@ -124,13 +99,12 @@ def main():
                                   *[tp(o) for o in outs], tp(counts))
         assert rc == 0, L.sc_last_error().decode()
 
-    res = {"merge_call": timed(raw_call), "merge_torch": timed(lambda: replay.merge_positions_torch(src)),
-           "torch_route": timed(lambda: torch_route(src))}
+    res = {"merge_call": measure(raw_call), "merge_torch": measure(lambda: replay.merge_positions_torch(src)),
+           "torch_route": measure(lambda: torch_route(src))}
     hbm_bound = P * PLY_B / (HBM_PEAK_GBS * 1e9) * 1e3
-    base = {"tool": "merge_rate", "host": socket.gethostname(), "date": datetime.date.today().isoformat(), "games": len(games),
-            "plies": P, "groups": G, "duplicate_share": round(1 - G / P, 5), "largest_group": int(m["count"].max()), "reps": args.reps,
-            "calls_per_region": args.iters, "bytes_per_ply": PLY_B, "workspace_bytes": need.value, "hbm_bound_ms": round(hbm_bound, 5),
-            "partitions_equal": equal, "max_abs_diff_to_torch_means": max_diff}
+    base = record("merge_rate", games=len(games), plies=P, groups=G, duplicate_share=round(1 - G / P, 5), largest_group=int(m["count"].max()),
+                  reps=args.reps, calls_per_region=args.iters, bytes_per_ply=PLY_B, workspace_bytes=need.value,
+                  hbm_bound_ms=round(hbm_bound, 5), partitions_equal=equal, max_abs_diff_to_torch_means=max_diff)
     t_med, t_lo, t_hi = res["torch_route"]
     lines = []
     for name, (med, lo, hi) in res.items():
@@ -138,17 +112,12 @@ def main():
                     x_hbm_bound=round(med / hbm_bound, 2))
         if name != "torch_route":
             line.update(x_torch_route=round(med / t_med, 4), torch_route_spread_ms=round(t_hi - t_lo, 5))
-        lines.append(json.dumps(line))
+        lines.append(line)
     u = replay.unique_by_ply(m)
-    lines.append(json.dumps(dict(tool="merge_rate", row="unique_by_ply", date=base["date"], games=len(games), plies=u["plies"].tolist(),
-                                 distinct=u["distinct"].tolist())))
+    lines.append(dict(tool="merge_rate", row="unique_by_ply", date=base["date"], games=len(games), plies=u["plies"].tolist(),
+                      distinct=u["distinct"].tolist()))
     eng.close()
-    path = args.out or os.path.join(ROOT, "profiles", f"merge_rate_{datetime.date.today().isoformat()}.jsonl")
-    if path != os.devnull:
-        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+    emit(lines, args.out, "merge_rate")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """Rate of perft on the device: nodes per second of sc_perft (csrc/perft_kernels.hip, csrc/perft.hip) on the start position at depth
 6 and on Kiwipete at depth 5, with and without kinds, at max_frontier 2^16, 2^20 and 2^22, next to the host build of the same
-rules code (lib/libsc_rules_host.so, sct_perft) on one core in the same process.  Appends one JSON line per row to
-profiles/perft_rate_<date>.jsonl and prints them.
+rules code (lib/libsc_rules_host.so, sct_perft) on one core in the same process.  Prints one JSON line per row and appends it to
+profiles/perft_rate_<date>.jsonl as soon as the row is measured.
 
   python tools/perft_rate.py [--reps 5] [--no-baseline]
 
@@ -14,18 +14,11 @@ of positions whose moves the walk generates: every node above the last level twi
 before anything is timed.  No torch in the process."""
 import argparse
 import ctypes as C
-import datetime
-import json
 import os
-import socket
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
+from ratelib import ROOT, emit, record, require_device, spread  # sets the package path
 
-import scamd  # noqa: E402
 from scamd import rules  # noqa: E402
 
 START = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
@@ -50,11 +43,8 @@ def main():
     ap.add_argument("--no-baseline", action="store_true", help="skip the host rows (tens of seconds of one core)")
     ap.add_argument("--out", default=None, help="result file (default profiles/perft_rate_<date>.jsonl)")
     args = ap.parse_args()
-    if scamd.lib().sc_device_count() <= 0:
-        raise SystemExit("no HIP device")
-    today = datetime.date.today().isoformat()
-    base = {"tool": "perft_rate", "host": socket.gethostname(), "date": today, "reps": args.reps}
-    lines = []
+    require_device()
+    base = record("perft_rate", reps=args.reps)
     for name, fen, depth, want in CASES:
         # the levels' sizes (one divide-free call per depth): what the walk generates
         level = [int(rules.perft([[]], d, fens=[fen])["nodes"][0]) for d in range(depth)]
@@ -71,14 +61,12 @@ def main():
                     if rep:   # the first call is the warm-up
                         wall.append((t1 - t0) * 1e3)
                         kern.append(rules.last_timing()[0])
-                ms, k_ms = statistics.median(wall), statistics.median(kern)
+                (ms, lo, hi), k_ms = spread(wall), spread(kern)[0]
                 g = gens + (checks if with_kinds else 0)
-                lines.append(json.dumps(dict(base, row="sc_perft", position=name, depth=depth, nodes=want, kinds=with_kinds, max_frontier=frontier,
-                                             ms=round(ms, 3), ms_min=round(min(wall), 3), ms_max=round(max(wall), 3),
-                                             nodes_per_s=round(want / (ms * 1e-3), 1), kernels_ms=round(k_ms, 3),
-                                             outside_share=round(1 - k_ms / ms, 4), generations=g,
-                                             ns_per_generation=round(k_ms * 1e6 / g, 2))))
-                print(lines[-1], flush=True)
+                emit([dict(base, row="sc_perft", position=name, depth=depth, nodes=want, kinds=with_kinds, max_frontier=frontier,
+                           ms=round(ms, 3), ms_min=round(lo, 3), ms_max=round(hi, 3), nodes_per_s=round(want / (ms * 1e-3), 1),
+                           kernels_ms=round(k_ms, 3), outside_share=round(1 - k_ms / ms, 4), generations=g,
+                           ns_per_generation=round(k_ms * 1e6 / g, 2))], args.out, "perft_rate")
         if not args.no_baseline:
             H = host_rules()
             s = C.c_void_p(H.sct_new())
@@ -88,14 +76,8 @@ def main():
             ms = (time.perf_counter() - t0) * 1e3
             H.sct_free(s)
             assert got == want, (name, got)
-            lines.append(json.dumps(dict(base, row="host_sct_perft_one_core", position=name, depth=depth, nodes=want, ms=round(ms, 1),
-                                         nodes_per_s=round(want / (ms * 1e-3), 1), runs=1)))
-            print(lines[-1], flush=True)
-    path = args.out or os.path.join(ROOT, "profiles", f"perft_rate_{today}.jsonl")
-    if path != os.devnull:
-        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
+            emit([dict(base, row="host_sct_perft_one_core", position=name, depth=depth, nodes=want, ms=round(ms, 1),
+                       nodes_per_s=round(want / (ms * 1e-3), 1), runs=1)], args.out, "perft_rate")
 
 
 if __name__ == "__main__":

@@ -1,8 +1,8 @@
 """Rate of reading SAN game records on the device (sc_encode_san_device: parse + encode in one call) against its floor, the same
 encoder without the parse (sc_encode_steps_device on the same games given as moves and children), on the 256-game trace set of
-tools/encode_device_rate.py rendered to SAN.  Prints one JSON line.
+tools/ratelib.py rendered to SAN.  Prints one JSON line and appends it to profiles/san_rate_<date>.jsonl (--out).
 
-  python tools/san_rate.py [--reps 7]
+  python tools/san_rate.py [--reps 7] [--out FILE]
 
 rows, all with the reference layout (int8 planes) and dist="legal":
   san_legal     sc_encode_san_device, every output but the dense dist
@@ -14,23 +14,14 @@ rows, all with the reference layout (int8 planes) and dist="legal":
 The SAN is written fully specified ("Ng1-f3", "e7xd8=Q", "O-O"): that needs the moving piece only, which a mailbox board here
 tracks -- the rules stay on the GPU.  The parsed moves must be the traces' moves, and both paths' dist_legal rows the same bits."""
 import argparse
-import ctypes as C
-import datetime
-import json
-import os
-import socket
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
+import numpy as np
 
-import numpy as np  # noqa: E402
+from ratelib import Hip, common_args, emit, ptr as p, record, require_device, spread, trace_set  # sets the package path
 
 import scamd  # noqa: E402
 import scamd.san  # noqa: E402
-from encode_device_rate import trace_set  # noqa: E402
 
 
 def _sq(s):
@@ -65,41 +56,15 @@ def render_san(uci_moves):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--blocks", type=int, default=10)
-    ap.add_argument("--channels", type=int, default=128)
+    common_args(ap, reps=7)
+    ap.add_argument("--out", default=None, help="result file (default profiles/san_rate_<date>.jsonl)")
     args = ap.parse_args()
-    L = scamd.lib()
-    if L.sc_device_count() <= 0:
-        raise SystemExit("no HIP device")
+    L = require_device()
     eng = scamd.Engine(args.blocks, args.channels, seed=1)
     games = trace_set(eng)
     eng.close()
-    hip = scamd.hip_runtime()
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipFree.argtypes = [C.c_void_p]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-    hip.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
-    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
-    stream, e0, e1 = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamCreate(C.byref(stream)) == 0
-    assert hip.hipEventCreate(C.byref(e0)) == 0 and hip.hipEventCreate(C.byref(e1)) == 0
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    bufs = []
-
-    def alloc(nbytes):
-        q = C.c_void_p()
-        assert hip.hipMalloc(C.byref(q), max(int(nbytes), 1)) == 0
-        bufs.append(q)
-        return q
-
-    def download(q, shape, dtype):
-        a = np.zeros(shape, dtype)
-        assert hip.hipMemcpy(p(a), q, a.nbytes, 2) == 0
-        return a
+    hip = Hip(L)
+    alloc, download, stream = hip.alloc, hip.download, hip.stream
 
     t0 = time.perf_counter()
     text = [render_san([s[0] for s in g]) for g in games]
@@ -121,24 +86,9 @@ def main():
     }
     rows = {}
     for name, call in calls.items():
-        def checked():
-            rc = call()
-            assert rc == 0, L.sc_last_error().decode()
-        checked()
-        assert hip.hipStreamSynchronize(stream) == 0
-        call_ms, dev_ms = [], []
-        for _ in range(args.reps):
-            t0_ = time.perf_counter()
-            hip.hipEventRecord(e0, stream)
-            checked()
-            hip.hipEventRecord(e1, stream)
-            assert hip.hipStreamSynchronize(stream) == 0
-            call_ms.append((time.perf_counter() - t0_) * 1e3)
-            ms = C.c_float(0)
-            hip.hipEventElapsedTime(C.byref(ms), e0, e1)
-            dev_ms.append(ms.value)
-        c, dm = statistics.median(call_ms), statistics.median(dev_ms)
-        rows[name] = {"call_ms": round(c, 3), "device_ms": round(dm, 3), "device_ms_min": round(min(dev_ms), 3), "device_ms_max": round(max(dev_ms), 3),
+        call_ms, _, dev_ms = hip.timed(call, args.reps)
+        c, (dm, lo, hi) = spread(call_ms)[0], spread(dev_ms)
+        rows[name] = {"call_ms": round(c, 3), "device_ms": round(dm, 3), "device_ms_min": round(lo, 3), "device_ms_max": round(hi, 3),
                       "plies_per_s": round(P / (c * 1e-3), 1), "device_plies_per_s": round(P / (dm * 1e-3), 1)}
         status = download(st_steps if name == "steps_legal" else st_san, n, np.int32)
         if status.any():
@@ -148,13 +98,11 @@ def main():
             raise SystemExit(f"{name}: the parsed moves are not the traces' moves")
     if not np.array_equal(download(dl_san, (P, 224), np.uint32), download(dl_steps, (P, 224), np.uint32)):
         raise SystemExit("dist_legal differs between the SAN path and the moves-and-children path")
-    for q in bufs:
-        hip.hipFree(q)
-    print(json.dumps({"tool": "san_rate", "host": socket.gethostname(), "date": datetime.date.today().isoformat(), "games": n, "plies": P,
-                      "reps": args.reps, "rows": rows,
-                      "san_over_steps_device": round(rows["san_legal"]["device_ms"] / rows["steps_legal"]["device_ms"], 3),
-                      "host_prepare": {"render_ms": round((t1 - t0) * 1e3, 1), "tokenize_ms": round(tokenize_ms, 1),
-                                       "token_bytes": int(tokens.nbytes), "moves_and_children_bytes": int(mv.nbytes + cm.nbytes + cn.nbytes + coff.nbytes)}}))
+    hip.close()
+    emit([record("san_rate", games=n, plies=P, reps=args.reps, rows=rows,
+                 san_over_steps_device=round(rows["san_legal"]["device_ms"] / rows["steps_legal"]["device_ms"], 3),
+                 host_prepare={"render_ms": round((t1 - t0) * 1e3, 1), "tokenize_ms": round(tokenize_ms, 1), "token_bytes": int(tokens.nbytes),
+                               "moves_and_children_bytes": int(mv.nbytes + cm.nbytes + cn.nbytes + coff.nbytes)})], args.out, "san_rate")
 
 
 if __name__ == "__main__":

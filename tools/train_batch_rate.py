@@ -1,6 +1,6 @@
 """Rate of building trainer-layout minibatches from the compact tensors: sc_gather_batch (k_gather_batch, one launch) next to the
 route that exists without it -- four torch ops on the same tensors (index_select, permute + float, zeros, scatter_add_) -- in the
-same visit, on the 256-game trace set of tools/encode_device_rate.py.  Appends one JSON line per row to
+same visit, on the 256-game trace set of tools/ratelib.py.  Appends one JSON line per row to
 profiles/train_batch_rate_<date>.jsonl and prints them.
 
   python tools/train_batch_rate.py [--reps 7] [--iters 20] [--batches 1024,8192]
@@ -18,21 +18,12 @@ loads and stores plus the launch -- the bound that applies where B workgroups do
 results are compared bit for bit before anything is timed."""
 import argparse
 import ctypes as C
-import datetime
-import json
-import os
-import socket
-import statistics
-import sys
 
 import torch  # before scamd: one HIP runtime in the process
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ratelib import common_args, emit, record, require_device, spread, timed_torch, trace_set  # sets the package path
 
 import scamd  # noqa: E402
-from encode_device_rate import trace_set  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # bench.py's figure
 READ_B, WRITE_B = 8548, 47392
@@ -50,16 +41,12 @@ def torch_route(src, rows):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=7)
+    common_args(ap, reps=7)
     ap.add_argument("--iters", type=int, default=20, help="calls per timed region")
     ap.add_argument("--batches", default="1024,8192")
-    ap.add_argument("--blocks", type=int, default=10)
-    ap.add_argument("--channels", type=int, default=128)
     ap.add_argument("--out", default=None, help="result file (default profiles/train_batch_rate_<date>.jsonl)")
     args = ap.parse_args()
-    L = scamd.lib()
-    if L.sc_device_count() <= 0:
-        raise SystemExit("no HIP device")
+    L = require_device()
     dev = torch.device("cuda", 0)
     torch.zeros(1, device=dev)
     eng = scamd.Engine(args.blocks, args.channels, seed=1)
@@ -70,20 +57,8 @@ def main():
     stream = torch.cuda.current_stream(0)
     tp = lambda t: C.c_void_p(t.data_ptr())
 
-    def timed(call):
-        for _ in range(args.iters):
-            call()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(args.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for _ in range(args.iters):
-                call()
-            e1.record(stream)
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1) / args.iters)
-        return statistics.median(ms), min(ms), max(ms)
+    def measure(call):
+        return spread(timed_torch(call, args.reps, args.iters, stream))
 
     def raw_call(rows, outs):
         B = int(rows.shape[0])
@@ -101,18 +76,17 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
     one = torch.zeros(1, dtype=torch.int32, device=dev)
-    floor = timed(raw_call(one, outputs(1)))
+    floor = measure(raw_call(one, outputs(1)))
     lines = []
-    base = {"tool": "train_batch_rate", "host": socket.gethostname(), "date": datetime.date.today().isoformat(), "games": len(games),
-            "plies": P, "reps": args.reps, "calls_per_region": args.iters, "read_bytes_per_sample": READ_B,
-            "write_bytes_per_sample": WRITE_B, "launch_floor_ms": round(floor[0], 5)}
+    base = record("train_batch_rate", games=len(games), plies=P, reps=args.reps, calls_per_region=args.iters, read_bytes_per_sample=READ_B,
+                  write_bytes_per_sample=WRITE_B, launch_floor_ms=round(floor[0], 5))
     for B in (int(x) for x in args.batches.split(",") if x):
         rows = (torch.randperm(P, generator=gen, device=dev)[:B] if B <= P else torch.randint(0, P, (B,), generator=gen, device=dev)).to(torch.int32)
         got, ref = scamd.gather_batch_torch(src, rows), torch_route(src, rows)
         equal = all(torch.equal(a, b) for a, b in zip(got, ref))
         outs = outputs(B)
-        res = {"gather_call": timed(raw_call(rows, outs)), "gather_torch": timed(lambda: scamd.gather_batch_torch(src, rows)),
-               "torch_route": timed(lambda: torch_route(src, rows))}
+        res = {"gather_call": measure(raw_call(rows, outs)), "gather_torch": measure(lambda: scamd.gather_batch_torch(src, rows)),
+               "torch_route": measure(lambda: torch_route(src, rows))}
         hbm_bound = B * (READ_B + WRITE_B) / (HBM_PEAK_GBS * 1e9) * 1e3
         t_med, t_lo, t_hi = res["torch_route"]
         for name, (med, lo, hi) in res.items():
@@ -123,14 +97,9 @@ def main():
                 # done when the median is no longer than the torch route's; the margin is that route's own spread
                 line.update(x_torch_route=round(med / t_med, 4), torch_route_spread_ms=round(t_hi - t_lo, 5),
                             no_slower_than_torch_route=bool(med <= t_med + (t_hi - t_lo)))
-            lines.append(json.dumps(line))
+            lines.append(line)
     eng.close()
-    path = args.out or os.path.join(ROOT, "profiles", f"train_batch_rate_{datetime.date.today().isoformat()}.jsonl")
-    if path != os.devnull:
-        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        with open(path, "a") as f:
-            f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+    emit(lines, args.out, "train_batch_rate")
 
 
 if __name__ == "__main__":
