@@ -344,6 +344,86 @@ int sc_moves_to_san_device_from(int device_id, int n_games, const sc_positions* 
  * be NULL); < 0: bad argument. */
 int sc_san_format(const uint64_t* tokens, uint32_t n, int fullmove, int black_first, const char* result, char* buf, size_t cap);
 
+/* ------------------------------------------------------------------ trace files read on the device */
+/* The text of n trace files (sc_trace_write_json / sc_selfplay_write_trace_json, the reference's Trace::save) -> the played moves,
+ * the children with their visit counts, the outcome and the optional "opening" / "fen" members, parsed by kernels and kept in
+ * device memory behind a handle, where sc_traces_encode_device reads them: no move or child comes back to the host on the way to
+ * the training tensors.
+ *
+ * This reads MACHINE-WRITTEN traces.  It is NOT a JSON validator: it refuses what the table below lists and may accept or refuse
+ * other text a strict parser would refuse ("[1 2]", "[ }"); such text never disturbs the other files of the call and never makes
+ * a count exceed the limits.
+ *   characters   the top level is one object; white space is space, \t, \n, \r; strings hold no backslash (no string the writers
+ *                produce needs one) and may hold bytes >= 0x80; true / false appear nowhere.
+ *   members      at depth 1, in any order and with any white space (the pretty form of the writer, json.dumps with any indent or
+ *                with separators=(",", ":"), CRLF line ends).  "steps": exactly once, an array (may be empty) of steps
+ *                [move string, one number or null, [children]]; a child is an array [move string, unsigned decimal integer <=
+ *                4294967295, ...]: what follows the count (Q, uct) is skipped and NOT parsed -- no float leaves this reader.
+ *                A move string is [a-h][1-8][a-h][1-8][nbrq]?.  "outcome": null, or an object of "winner" ("White", "Black" or null)
+ *                and "termination" (a name of the writer's table); absent: has_outcome 0.  "opening": an array of move strings.
+ *                "fen": a string of at most 127 bytes.  Any other member is ignored, whatever it holds.
+ *   limits       at most 4000 steps, at most SC_MAX_MOVES children per step; runs of up to 255 white-space bytes between tokens
+ *                are accepted, a longer run is read or refused with SC_TRACE_ERR_SPACE.
+ * A refused file has status -code, counts 0 and no entry in the packed arrays; the call still returns 0 and the set, the other
+ * files are not affected.  err_at: the byte offset in the file of the first defect -- the smallest offset wins, at one offset the
+ * smaller code; what is only known at the end of the text (an open string, open brackets, no "steps") counts at the file's length.
+ *   SC_TRACE_ERR_UNBALANCED  the text ends inside a string or with open brackets; a closing bracket closes nothing; the first
+ *                            token is not '{'; the file is empty
+ *   SC_TRACE_ERR_ESCAPE      a backslash inside a string (err_at: the backslash)
+ *   SC_TRACE_ERR_STEPS       no "steps" array at depth 1, or more than one
+ *   SC_TRACE_ERR_SHAPE       a step or a child is not an array that starts with a string; a step holds no children array or more
+ *                            than one; a child's second element is missing
+ *   SC_TRACE_ERR_MOVE        a move string (step, child or opening) is not UCI as above (err_at: its opening quote)
+ *   SC_TRACE_ERR_COUNT       a child's second element is not an unsigned integer in range: sign, fraction, exponent, null,
+ *                            overflow (err_at: the first byte of the token)
+ *   SC_TRACE_ERR_CHILDREN    a step has more than SC_MAX_MOVES children
+ *   SC_TRACE_ERR_PLIES       more than 4000 steps
+ *   SC_TRACE_ERR_OUTCOME     "outcome" is of another form
+ *   SC_TRACE_ERR_SPACE       more than 255 white-space bytes between two tokens where the reader had to step over them
+ *
+ * sc_traces_read: text holds the bytes of the n files one after another (host); file g is text[text_off[g] .. text_off[g+1]),
+ * text_off[n] < 2^32.  Synchronous: the host sizes the handle's arrays from the parsed totals, and the uploaded text is freed
+ * before the call returns.  n == 0 gives an empty set.  A non-monotonic text_off, or text_off[n] >= 2^32: -1 (found before a
+ * device is looked for).
+ * sc_traces_summary: per file, host arrays, any may be NULL: status int32 [n], err_at uint32 [n], n_steps / n_children / n_opening
+ * uint32 [n], outcome int32 [n][3] = has_outcome, termination, winner (sc_trace_info's conventions), has_fen int32 [n].
+ * sc_traces_get: host copies of games [g0, g0 + n), offsets rebased to 0, any may be NULL (sizes from sc_traces_summary):
+ * move_off [n+1], moves, child_off [plies + 1], child_mv, child_n, open_off [n+1], opening.  Moves are the library's uint16
+ * (from | to << 6 | promo << 12, n = 2 b = 3 r = 4 q = 5).
+ * sc_traces_fen: the "fen" member of file g: its length, or 0 without one; writes as sc_positions_fen.
+ * sc_traces_encode_device: games [g0, g0 + n) -> training tensors; outputs, layouts, pointer checks, stream contract and arena of
+ * sc_encode_steps_device, on the handle's device (or the engine's, which must be the same).  Row p of the outputs is ply
+ * p - move_off[g0] of the range.  The moves are copied on the device, the children are read in place; the handle must stay alive
+ * until the stream's work is done.  status[g] (device, required): 0; 1000 + i and -(i + 1) as sc_encode_steps_device;
+ * 300000 + code: the reader refused the file with that code (the game has no plies); 400000: the file has an "opening" or a
+ * "fen" member, so its steps do not start at the start position (such a game keeps its rows, whose contents are unspecified).
+ * sc_traces_last_timing: measurement aid (tools/trace_read_rate.py) -- HIP-event time of the two parse passes of the calling
+ * thread's last sc_traces_read (the counting pass with the scans of its counts, the emitting pass).
+ * Returns 0, or < 0 as every entry point (-3: no HIP device). */
+#define SC_TRACE_ERR_UNBALANCED 1
+#define SC_TRACE_ERR_ESCAPE 2
+#define SC_TRACE_ERR_STEPS 3
+#define SC_TRACE_ERR_SHAPE 4
+#define SC_TRACE_ERR_MOVE 5
+#define SC_TRACE_ERR_COUNT 6
+#define SC_TRACE_ERR_CHILDREN 7
+#define SC_TRACE_ERR_PLIES 8
+#define SC_TRACE_ERR_OUTCOME 9
+#define SC_TRACE_ERR_SPACE 10
+typedef struct sc_traces sc_traces;
+int sc_traces_read(int device_id, int n, const char* text, const uint64_t* text_off, sc_traces** out);
+void sc_traces_destroy(sc_traces*);
+int sc_traces_count(const sc_traces*);
+int sc_traces_summary(const sc_traces*, int32_t* status, uint32_t* err_at, uint32_t* n_steps, uint32_t* n_children,
+                      uint32_t* n_opening, int32_t* outcome, int32_t* has_fen);
+int sc_traces_get(const sc_traces*, int g0, int n, uint32_t* move_off, uint16_t* moves, uint32_t* child_off,
+                  uint16_t* child_mv, uint32_t* child_n, uint32_t* open_off, uint16_t* opening);
+int sc_traces_fen(const sc_traces*, int g, char* buf, int cap);
+int sc_traces_encode_device(sc_engine* engine_or_null, const sc_traces*, int g0, int n, int apply_mirror, int layout, void* stream,
+                            void* boards, void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal,
+                            int32_t* status);
+int sc_traces_last_timing(float* count_ms, float* emit_ms);
+
 /* ------------------------------------------------------------------ network on device tensors: forward, losses, agreement */
 /* sc_forward_batch on DEVICE pointers: boards int8 [n][8][8][112] and meta int32 [n][7] as layout 0 of sc_encode_steps_device
  * leaves them, logp float [n][4672] (may be NULL) and value float [n] in device memory of the engine's GPU.  The same kernels as

@@ -1,4 +1,5 @@
-// encode_steps.hip -- host side of libsc_engine.so: training tensors (sc_encode_steps, sc_encode_steps_device, sc_encode_san_device)
+// encode_steps.hip -- host side of libsc_engine.so: training tensors (sc_encode_steps, sc_encode_steps_device, sc_encode_san_device,
+// sc_traces_encode_device)
 // and, on the same walk and arena, moves written as SAN (sc_moves_to_san_device, sc_san_format).
 //
 // libsmartchess.chess_encode_steps (reference src/lib.rs:46-128) for a batch of recorded games; see include/sc_engine.h.
@@ -148,11 +149,12 @@ struct GameBatch {
 };
 }  // namespace
 
-// One encoder for the three kinds of source (EncodeSrc, host_common.hpp).  In the SAN kind k_san_parse also writes the games'
+// One encoder for the four kinds of source (EncodeSrc, host_common.hpp).  In the SAN kind k_san_parse also writes the games'
 // status, and the parsed moves stay in the arena between the two halves: nothing comes back to the host.
 int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const EncodeSrc& src, int apply_mirror, const DevEncodeOut& o,
                        hipStream_t st) {
     const bool has_ring = src.kind == EncodeSrc::RING, has_csr = src.kind == EncodeSrc::CSR, has_san = src.kind == EncodeSrc::SAN;
+    const bool has_dev = src.kind == EncodeSrc::DEV;
     GameBatch B(n_games, ply_off, src.bases, st);
     const uint32_t P = B.P, CH = 32768;   // CH: plies per launch of the per-ply kernels (bounds their legal-move / meta scratch: 15 MB)
     const uint32_t nchild = has_csr ? src.child_off[P] : 0, cap = std::max<uint32_t>(std::min(CH, P), 1);
@@ -180,6 +182,9 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const Enco
         if (P) HIPOK(hipMemcpyAsync(d_tok, src.tokens, (size_t)P * 8, hipMemcpyHostToDevice, st));
         scl::san_parse(n_games, d_tok, B.d_off, B.d_moves, o.status, B.bases, st);
         if (P && src.moves_out) HIPOK(hipMemcpyAsync(src.moves_out, B.d_moves, (size_t)P * 2, hipMemcpyDeviceToDevice, st));
+    } else if (has_dev) {   // the moves into the batch, the children read where the parsed set keeps them
+        if (P) HIPOK(hipMemcpyAsync(B.d_moves, src.moves, (size_t)P * 2, hipMemcpyDeviceToDevice, st));
+        ch = {src.child_mv, src.child_n, src.child_off, nullptr, nullptr};
     } else {
         if (P) HIPOK(hipMemcpyAsync(B.d_moves, src.moves, (size_t)P * 2, hipMemcpyHostToDevice, st));
         HIPOK(hipMemcpyAsync(d_coff, src.child_off, ((size_t)P + 1) * 4, hipMemcpyHostToDevice, st));
@@ -208,6 +213,7 @@ int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const Enco
             return 0;
         }));
     if (!has_san) scl::status_final(n_games, o.status, st);
+    if (has_dev) scl::trace_status(n_games, src.over, o.status, st);
     HIPOK(hipGetLastError());
     return 0;
 }
@@ -299,6 +305,21 @@ int sc_encode_san_device_from(sc_engine* e, int device_id, int n_games, const sc
     TRY(check_traces(n_games, tok_off, nullptr));
     if (tok_off[n_games] && !tokens) return fail("bad argument");
     return encode_device_core(c.dev, n_games, tok_off, EncodeSrc::san(tokens, moves, c.bases), apply_mirror, o, static_cast<hipStream_t>(stream));
+}
+
+int sc_traces_encode_device(sc_engine* e, const sc_traces* t, int g0, int n, int apply_mirror, int layout, void* stream, void* boards,
+                            void* meta, float* dist, float* dist_legal, uint16_t* legal_idx, int32_t* n_legal, int32_t* status) {
+    if (!t || g0 < 0 || n < 0 || (int64_t)g0 + n > t->n || !status) return fail("bad argument");
+    const DevEncodeOut o{layout, boards, meta, dist, dist_legal, legal_idx, n_legal, status};
+    TRY(use_device(e, t->device));
+    if (e && e->device != t->device)
+        return fail("sc_traces_encode_device: the traces live on device " + std::to_string(t->device) + ", the engine on device " + std::to_string(e->device));
+    TRY(check_device_outputs(o, t->device));
+    if (n == 0) return 0;
+    const uint32_t p0 = t->move_off[(size_t)g0];
+    return encode_device_core(t->device, n, traces_range_off(t, g0),
+                              EncodeSrc::dev(t->d_moves + p0, t->d_child_mv, t->d_child_n, t->d_child_off + p0, t->d_over + g0), apply_mirror, o,
+                              static_cast<hipStream_t>(stream));
 }
 
 int sc_moves_to_san_device(int device_id, int n_games, const uint16_t* moves, const uint32_t* move_off, void* stream, uint64_t* tokens,

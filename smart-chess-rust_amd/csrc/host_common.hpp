@@ -9,6 +9,8 @@
 
 #include <algorithm>
 #include <initializer_list>
+#include <map>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -193,17 +195,21 @@ struct DevEncodeOut {
 struct HostBases { const sc::Position* rec; const int32_t* idx; };
 // What an encode reads, one kind per call, and the games' optional bases.  ply_off is the call's in every kind.
 struct EncodeSrc {
-    enum Kind { CSR, RING, SAN } kind;
-    const uint16_t *moves, *child_mv;     // CSR: host arrays as sc_encode_steps takes them
-    const uint32_t *child_n, *child_off;
+    enum Kind { CSR, RING, SAN, DEV } kind;
+    const uint16_t *moves, *child_mv;     // CSR: host arrays as sc_encode_steps takes them.  DEV (sc_traces_encode_device): device arrays
+    const uint32_t *child_n, *child_off;  // of a parsed set -- moves / child_off of the range's first ply on, child_off global into child_mv / child_n
     const int32_t* rows;      // RING (sc_selfplay_encode_traces): host, the ring row of each requested game; the moves and children
     const sc::SpParams* p;    // are read from the ring's rows on the device
     const uint64_t* tokens;   // SAN (sc_encode_san_device): host, one per ply; the moves are parsed on the device, every ply's
     uint16_t* moves_out;      // children are its legal moves with count 1 on the move played.  device [P] or null: the parsed moves
     HostBases bases;
+    const int32_t* over;      // DEV: device [games], the codes the reader decided (0: the encoder's status stands)
     static EncodeSrc csr(const uint16_t* mv, const uint16_t* cmv, const uint32_t* cn, const uint32_t* coff, HostBases b) { return {CSR, mv, cmv, cn, coff, {}, {}, {}, {}, b}; }
     static EncodeSrc ring(const int32_t* rows, const sc::SpParams* p) { return {RING, {}, {}, {}, {}, rows, p, {}, {}, {}}; }
     static EncodeSrc san(const uint64_t* tokens, uint16_t* moves_out, HostBases b) { return {SAN, {}, {}, {}, {}, {}, {}, tokens, moves_out, b}; }
+    static EncodeSrc dev(const uint16_t* mv, const uint16_t* cmv, const uint32_t* cn, const uint32_t* coff, const int32_t* over) {
+        return {DEV, mv, cmv, cn, coff, {}, {}, {}, {}, HostBases{nullptr, nullptr}, over};
+    }
 };
 // pointers the kernels of a call read or write must be device memory of `dev`; null entries are skipped
 int check_device_ptrs(std::initializer_list<std::pair<const void*, const char*>> ptrs, int dev);
@@ -212,6 +218,25 @@ int check_device_outputs(const DevEncodeOut& o, int dev);
 int check_traces(int n_games, const uint32_t* move_off, const uint32_t* child_off);
 int encode_device_core(int dev, int n_games, const uint32_t* ply_off, const EncodeSrc& src, int apply_mirror, const DevEncodeOut& o,
                        hipStream_t st);
+
+// ------------------------------------------------------------------ trace files read on the device (traces.hip)
+// the packed arrays of n parsed files in device memory (trace_kernels.hip) and the host's copy of what is per file
+struct sc_traces {
+    int device = 0;
+    int n = 0;
+    uint16_t *d_moves = nullptr, *d_child_mv = nullptr, *d_opening = nullptr;
+    uint32_t *d_child_off = nullptr, *d_child_n = nullptr;   // d_child_off [plies + 1]: global, the total behind the last ply
+    int32_t* d_over = nullptr;   // [n]: 300000 + code of a refused file, 400000 with "opening" or "fen", else 0
+    std::vector<int32_t> status, outcome, has_fen;
+    std::vector<uint32_t> err_at, n_steps, n_children, n_opening;
+    std::vector<uint32_t> move_off, child_base, open_off;   // [n + 1]: the prefix sums of the counts
+    std::vector<char> fen;                                  // [n][128]
+    // the ply offsets of the games from g0 on, rebased to 0, one array per g0 asked for: an encode uploads them asynchronously,
+    // so they live as long as the handle
+    mutable std::mutex mu;
+    mutable std::map<int, std::vector<uint32_t>> range_off;
+};
+const uint32_t* traces_range_off(const sc_traces* t, int g0);
 
 // text to a file, whole or appended
 int write_text_file(const char* path, const std::string& text, bool append);

@@ -18,6 +18,7 @@ void exclusive_scan_u32(uint32_t n, const uint32_t* d_in, uint32_t* d_tile_sum, 
 #include "merge_types.hpp"
 #include "encode_types.hpp"
 #include "perft_types.hpp"
+#include "trace_types.hpp"
 
 struct sc_fen_fields;   // include/sc_engine.h
 
@@ -63,6 +64,12 @@ void san_clip(int n, const sc::PlyIndex& idx, const int32_t* d_status, uint64_t*
 // fen_kernels.hip: raw FEN fields -> validated records and their status (sc_positions_from_fen); the ep bit of Board.fen()
 void fen_positions(int n, const sc_fen_fields* d_fields, const int32_t* d_syntax, sc::Position* d_out, int32_t* d_status, hipStream_t s);
 void fen_ep_legal(int n, const sc::Position* d_rec, int32_t* d_ep_legal, hipStream_t s);
+// trace_kernels.hip: trace files read on the device (sc_traces_read).  trace_count: per file the status, the counts, the outcome and
+// the "fen" member; trace_emit: the packed arrays, at the bases the exclusive scans of the counts give; trace_status: the reader's
+// codes over the encoder's (sc_traces_encode_device)
+void trace_count(const sctr::Text& t, const sctr::Files& f, hipStream_t s);
+void trace_emit(const sctr::Text& t, const sctr::Files& f, const sctr::Packed& p, hipStream_t s);
+void trace_status(int n, const int32_t* d_over, int32_t* d_status, hipStream_t s);
 // nn_kernels.hip
 const char* nn_init();  // sets kernel attributes; returns error text or nullptr
 size_t tower_lds_bytes(int C);

@@ -121,6 +121,14 @@ ABI = {
     "sc_moves_to_san_device": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sc_moves_to_san_device_from": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_san_format": (_i, [_vp, C.c_uint32, _i, _i, C.c_char_p, C.c_char_p, C.c_size_t]),
+    "sc_traces_read": (_i, [_i, _i, _vp, _vp, C.POINTER(_vp)]),
+    "sc_traces_destroy": (None, [_vp]),
+    "sc_traces_count": (_i, [_vp]),
+    "sc_traces_summary": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_traces_get": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_traces_fen": (_i, [_vp, _i, C.c_char_p, _i]),
+    "sc_traces_encode_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_traces_last_timing": (_i, [C.POINTER(_f), C.POINTER(_f)]),
     "sc_selfplay_encode_traces": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_forward_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sc_score_positions": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
