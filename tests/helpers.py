@@ -1,11 +1,18 @@
-"""Test helpers: SAN parsing on top of the oracle's legal-move list, edge-case predicates, and the comparison of a device
-search tree with the oracle's (shared by the GPU search tests)."""
+"""Chess, the oracle and pure-Python data -- nothing here touches the package, the device or a process (tests/support.py does):
+  san_to_move                                  SAN parsing on top of the oracle's legal-move list
+  random_games, special_walk, random_steps     seeded games, and a game's steps with shuffled children and visit counts
+  bits, golden_boards                          the float32 -> uint32 view, the four golden network inputs
+  edge_features, line_features, EDGE_CATEGORIES, load_edge_lines      the edge-case predicates and their corpus
+  _same_tree, assert_same_tree_bits, _assert_same, GpuPredictEvaluator   a device search tree against the oracle's
+The named move lines and tables are tests/lines.py."""
 import ctypes as C
+import os
 import random
 
 import numpy as np
 
-PT = {"N": 2, "B": 3, "R": 4, "Q": 5, "K": 6}
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")   # support.GOLD; tools import this module without pytest
+PT ={"N": 2, "B": 3, "R": 4, "Q": 5, "K": 6}
 
 
 def san_to_move(st, san, orc):
@@ -70,6 +77,33 @@ def random_games(orc, n, maxlen, seed):
             mv.append(m)
         games.append((mv, st))
     return games
+
+
+def random_steps(orc, moves, rnd, zero_share=0.0):
+    """[(move, [(child, visits)])] of a game: every ply's legal moves in an order shuffled by `rnd`, visits drawn from 0..200.
+    With zero_share > 0 a draw of rnd.random() comes first for every child and makes that share of the counts 0 (then without
+    a randint); with zero_share == 0 no such draw is made, so the calls on `rnd` are those of the plain form"""
+    st = orc.State()
+    steps = []
+    for m in moves:
+        lm = st.legal_moves()
+        order = list(range(len(lm)))
+        rnd.shuffle(order)
+        if zero_share:
+            steps.append((m, [(lm[i], rnd.randint(0, 200) if rnd.random() < 1.0 - zero_share else 0) for i in order]))
+        else:
+            steps.append((m, [(lm[i], rnd.randint(0, 200)) for i in order]))
+        st.push(m)
+    return steps
+
+
+def bits(a):
+    """the bit patterns of float32 values: -0.0 is not +0.0, a NaN equals itself"""
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def golden_boards():
+    return np.load(os.path.join(_GOLDEN, "nn_ref_b1_c256.npz"))["boards"][[0, 3, 5, 7]]
 
 
 # ------------------------------------------------------------------ edge-case predicates (oracle primitives only)
@@ -434,8 +468,7 @@ def line_features(orc, uci):
 
 def load_edge_lines():
     import json
-    import os
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "edge_lines.json")) as fh:
+    with open(os.path.join(_GOLDEN, "edge_lines.json")) as fh:
         return json.load(fh)
 
 

@@ -6,10 +6,7 @@ import os
 import re
 
 import pytest
-from support import scamd_built  # noqa: F401
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
+from support import GOLD, ROOT, scamd_built  # noqa: F401
 
 
 def test_exports_exactly_the_declared_symbols(scamd):

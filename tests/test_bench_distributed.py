@@ -7,7 +7,7 @@ import socket
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT
 
 
 def _free_port():

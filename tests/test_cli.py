@@ -5,7 +5,8 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT
+
 CLI = os.path.join(ROOT, "smart-chess-rust_amd", "lib", "sc-selfplay")
 
 

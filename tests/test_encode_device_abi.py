@@ -8,9 +8,8 @@ import subprocess
 
 import numpy as np
 import pytest
-from support import scamd_built  # noqa: F401
+from support import ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("sc_encode_steps_device", "sc_selfplay_encode_traces")
 
 

@@ -2,54 +2,12 @@
 host (lib/libsc_rules_host.so): perft known answers and cross-checks against the oracle, which uses a
 different method (mailbox + make/test) -- so the two implementations pin each other."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
-import pytest
 
 from helpers import load_edge_lines, random_games
-from test_oracle_rules import PERFT
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "smart-chess-rust_amd")
-
-
-@pytest.fixture(scope="module")
-def H():
-    so = os.path.join(PKG, "lib", "libsc_rules_host.so")
-    src = os.path.join(PKG, "csrc", "rules_host_api.cpp")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(os.path.join(PKG, "csrc", f))
-                                                           for f in ("rules_host_api.cpp", "chess_rules.hpp", "chess_history.hpp")):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so, src])
-    L = C.CDLL(so)
-    L.sct_new.restype = C.c_void_p
-    L.sct_perft.restype = C.c_uint64
-    L.sct_pos_hash.restype = C.c_uint64
-    L.sct_rng.restype = C.c_uint64
-    L.sct_key.restype = C.c_uint64
-    L.sct_key_full.restype = C.c_uint64
-    L.sct_key.argtypes = [C.c_void_p]
-    L.sct_key_full.argtypes = [C.c_void_p]
-    L.sct_rng.argtypes = [C.c_uint64] * 5
-    for n in ("sct_free", "sct_reset", "sct_push", "sct_pop", "sct_encode", "sct_synth_eval"):
-        getattr(L, n).restype = None
-    L.sct_set_fen.argtypes = [C.c_void_p, C.c_char_p]
-    L.sct_push.argtypes = [C.c_void_p, C.c_uint16]
-    L.sct_move_index.argtypes = [C.c_uint16, C.c_int]
-    for n in ("sct_free", "sct_reset", "sct_pop", "sct_pos_hash", "sct_turn"):
-        getattr(L, n).argtypes = [C.c_void_p]
-    L.sct_legal_moves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sct_perft.argtypes = [C.c_void_p, C.c_int]
-    L.sct_is_repetition.argtypes = [C.c_void_p, C.c_int]
-    L.sct_outcome.argtypes = [C.c_void_p, C.c_void_p]
-    L.sct_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sct_board_diff_legal.argtypes = [C.c_void_p, C.c_void_p]
-    L.sct_synth_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
-
+from lines import PERFT
+from support import rules_host  # noqa: F401
 
 DEEP = {
     "r3k2r/p1ppqpb1/bn2pnp1/3PN3/1p2P3/2N2Q1p/PPPBBPPP/R3K2R w KQkq - 0 1": (4, 4085603),

@@ -8,10 +8,9 @@ import subprocess
 
 import numpy as np
 import pytest
-from support import scamd_built  # noqa: F401
-from test_oracle_rules import PERFT
+from lines import PERFT
+from support import ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "smart-chess-rust_amd")
 START = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR"
 REF39 = "1k1r4/1r5p/p4n1P/1ppP1P2/PP6/4PP1b/3B4/R1N1K3 b - - 0 39"

@@ -6,7 +6,8 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import scw  # noqa: E402
 

@@ -4,22 +4,17 @@ bad input is contained on the device; bad pointers are refused; and the replay b
 imports torch before scamd.  Device buffers come from hipMalloc on the HIP runtime libsc_engine.so uses (ctypes): this file does
 not import torch."""
 import ctypes as C
-import json
 import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import batch_ref
-from helpers import random_games
-from support import open_dev, _p, scamd_gpu  # noqa: F401
+from helpers import bits, random_games, random_steps
+from support import FILL, ROOT, _p, alloc_outputs, open_dev, run_torch_child, scamd_gpu, untouched  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILL = 0x5a
 N_LEGAL = (0, 1, 63, 64, 65, 128, 129, 192, 193, 218)   # the boundaries of the scatter's lane rounds
 KEYS = ("boards", "meta", "dist_legal", "legal_idx", "n_legal", "outcome")
 
@@ -27,10 +22,6 @@ KEYS = ("boards", "meta", "dist_legal", "legal_idx", "n_legal", "outcome")
 @pytest.fixture(scope="module")
 def dev(scamd):
     yield from open_dev(scamd, FILL)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def synthetic_source(n_src=37, seed=1):
@@ -91,13 +82,9 @@ def run_gather(scamd, dev, d_src, n_src, rows, mirror=None, want=(True, True, Tr
     return got, int(dev.read(n_bad, (1,), np.int32)[0])
 
 
-def untouched(a):
-    return (np.ascontiguousarray(a).view(np.uint8) == FILL).all()
-
-
 def assert_equal_ref(got, ref, what=""):
     for name, g, e in zip(("boards", "meta", "dist", "outcome"), got, ref):
-        assert np.array_equal(_bits(g), _bits(e)), (what, name)
+        assert np.array_equal(bits(g), bits(e)), (what, name)
 
 
 BATCHES = {
@@ -137,14 +124,14 @@ def test_each_output_may_be_null_and_an_empty_batch_writes_nothing(scamd, dev, s
             if i == skip:
                 assert untouched(got[i]), i
             else:
-                assert np.array_equal(_bits(got[i]), _bits(ref[i])), (skip, i)
+                assert np.array_equal(bits(got[i]), bits(ref[i])), (skip, i)
     # n_bad may be NULL too
     outs = [dev.alloc(len(rows) * n) for n in (7168 * 4, 28, 4672 * 4, 4)]
     rc = scamd.lib().sc_gather_batch(0, 37, len(rows), dev.upload(np.asarray(rows, np.int32)), None, *[d_src[k] for k in KEYS], dev.stream,
                                      *outs, None)
     assert rc == 0
     dev.sync()
-    assert np.array_equal(_bits(dev.read(outs[2], (len(rows), 4672), np.float32)), _bits(batch_ref.gather(src, rows)[2]))
+    assert np.array_equal(bits(dev.read(outs[2], (len(rows), 4672), np.float32)), bits(batch_ref.gather(src, rows)[2]))
     # n_batch = 0: a successful no-op, n_bad included
     got, n_bad = run_gather(scamd, dev, d_src, 37, rows, mir, n_batch=0)
     assert all(untouched(g) for g in got) and n_bad == int.from_bytes(bytes([FILL] * 4), "little")
@@ -173,7 +160,7 @@ def test_bad_input_is_contained(scamd, dev, source):
     good = [0, 3, 6, 7]
     for i, name in enumerate(("boards", "meta", "dist", "outcome")):
         keep = good if i == 2 else [0, 2, 3, 5, 6, 7]
-        assert np.array_equal(_bits(got[i][keep]), _bits(ref[i][keep])), name
+        assert np.array_equal(bits(got[i][keep]), bits(ref[i][keep])), name
     again, n_bad2 = run_gather(scamd, dev, d_src, n_src, rows, mir)
     assert n_bad2 == 4
     assert_equal_ref(again, got, "second call")
@@ -204,24 +191,10 @@ def test_bad_pointers_are_refused(scamd, dev, source):
 
 
 # ------------------------------------------------------------------ against the encoder
-def _random_steps(orc, moves, rnd):
-    st = orc.State()
-    steps = []
-    for m in moves:
-        lm = st.legal_moves()
-        order = list(range(len(lm)))
-        rnd.shuffle(order)
-        steps.append((m, [(lm[i], rnd.randint(0, 200)) for i in order]))
-        st.push(m)
-    return steps
-
-
 def _encode(scamd, dev, packed, n, P, mirror, layout):
     """sc_encode_steps_device -> the device buffers (left on the device) and the status"""
     mv, off, cm, cn, coff = packed
-    o = dict(boards=dev.alloc(P * 7168 * (4 if layout else 1)), meta=dev.alloc(P * 28), dist=dev.alloc(P * 4672 * 4) if layout else None,
-             dist_legal=None if layout else dev.alloc(P * 224 * 4), legal_idx=dev.alloc(P * 448), n_legal=dev.alloc(P * 4),
-             status=dev.alloc(n * 4))
+    o = alloc_outputs(dev, P, n, layout, skip=("moves", "dist_legal" if layout else "dist"))
     rc = scamd.lib().sc_encode_steps_device(None, 0, n, _p(mv), _p(off), _p(cm), _p(cn), _p(coff), int(mirror), layout, dev.stream,
                                             o["boards"], o["meta"], o["dist"], o["dist_legal"], o["legal_idx"], o["n_legal"], o["status"])
     assert rc == 0, scamd.lib().sc_last_error().decode()
@@ -236,7 +209,7 @@ def test_gather_equals_the_encoders_trainer_layout(scamd, orc, dev):
     and mirror = 1 -- which ties the kernel to a path the oracle pins"""
     rnd = random.Random(4)
     games = [g for g, _ in random_games(orc, 6, 100, seed=21) if g]
-    steps = [_random_steps(orc, g, rnd) for g in games]
+    steps = [random_steps(orc, g, rnd) for g in games]
     packed = scamd.pack_steps(steps)
     n, P = len(steps), int(packed[1][-1])
     assert 150 <= P <= 600
@@ -376,12 +349,7 @@ def test_replay_buffer_in_a_fresh_process(scamd, tmp_path):
     trainer-layout rows; (seed, epoch) repeats the order, another epoch or seed changes it; after an add that evicts, only rows
     of the surviving games are drawn; shapes and dtypes are the reference batch's"""
     pytest.importorskip("torch")
-    script = tmp_path / "child.py"
-    script.write_text(_CHILD)
-    r = subprocess.run([sys.executable, str(script), os.path.join(ROOT, "smart-chess-rust_amd")], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_torch_child(tmp_path, _CHILD, os.path.join(ROOT, "smart-chess-rust_amd"), timeout=600)
     E = out["E"]
     assert 60 <= E <= 140 and out["len"] == E, out
     assert out["n_batches"] == E // 8 and out["rows_distinct"] and out["bits_none"], out

@@ -6,31 +6,25 @@ the end of every ply -- on given visit counts, one wave per case.  Every asserti
 bit pattern of the f32 weight total.  The reference of a decision is the oracle's `orc_choose_child` (oracle/mcts.c), the
 reference of a single weight is the host libm's `powf` through ctypes (what Rust's `f32::powf` and the oracle call); numpy's own
 f32 power is no reference.  tests/test_oracle_mcts.py holds the oracle to a plain Python restatement on the same inputs."""
-import os
-
 import numpy as np
 import pytest
 
 import choice_cases as cc
+from helpers import GpuPredictEvaluator, bits
 from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _assert_cases_equal_oracle(scamd, orc, cases, what):
     n_act, nc, temp, u = cc.pack(cases)
     want_c, want_t = cc.oracle_choices(orc, n_act, nc, temp, u)
     got_c, got_t = scamd.choose_child(n_act, nc, temp, u)
-    bad = np.flatnonzero((got_c != want_c) | (_bits(got_t) != _bits(want_t)))
+    bad = np.flatnonzero((got_c != want_c) | (bits(got_t) != bits(want_t)))
     for i in bad[:20]:
         print(f"{what}: case {i}: nc={nc[i]} T={temp[i]!r} u={u[i]!r} counts={n_act[i, :nc[i]].tolist()} device choice={got_c[i]} "
-              f"total={got_t[i]!r} (0x{_bits(got_t)[i]:08x}); oracle choice={want_c[i]} total={want_t[i]!r} (0x{_bits(want_t)[i]:08x})")
+              f"total={got_t[i]!r} (0x{bits(got_t)[i]:08x}); oracle choice={want_c[i]} total={want_t[i]!r} (0x{bits(want_t)[i]:08x})")
     assert bad.size == 0, f"{what}: {bad.size} of {len(cases)} cases differ from the oracle (first: {bad[:10].tolist()})"
     return got_c, got_t
 
@@ -44,13 +38,13 @@ def test_weights_equal_host_powf(scamd, orc):
     want = np.array([cc.host_powf(F(n[0]), F(1.0) / F(T)) for n, T, _ in cases], np.float32)
     assert np.isfinite(want).all()
     orc_c, orc_t = cc.oracle_choices(orc, n_act, nc, temp, u)
-    assert np.array_equal(_bits(orc_t), _bits(want)) and not orc_c.any()
+    assert np.array_equal(bits(orc_t), bits(want)) and not orc_c.any()
     got_c, got_t = scamd.choose_child(n_act, nc, temp, u)
-    bad = np.flatnonzero(_bits(got_t) != _bits(want))
+    bad = np.flatnonzero(bits(got_t) != bits(want))
     for i in bad[:40]:
         n, T = cases[i][0][0], cases[i][1]
         p = F(1.0) / F(T)
-        print(f"count {n} power {p!r} (T={T}): device 0x{_bits(got_t)[i]:08x} host 0x{_bits(want)[i]:08x} "
+        print(f"count {n} power {p!r} (T={T}): device 0x{bits(got_t)[i]:08x} host 0x{bits(want)[i]:08x} "
               f"float64 {float(n) ** float(p)!r}")
     per_t = {T: int(sum(1 for i in bad if cases[i][1] == T)) for T in cc.TEMPS}
     assert bad.size == 0, f"{bad.size} of {len(cases)} weights differ from host powf; per temperature: {per_t}"
@@ -97,7 +91,7 @@ def test_temperature_zero_first_maximum(scamd, orc):
     cases = [(n, 0.0, F(0.5)) for n, _ in vecs]
     got_c, got_t = _assert_cases_equal_oracle(scamd, orc, cases, "first maximum")
     assert got_c.tolist() == [mx[0] for _, mx in vecs]
-    assert not _bits(got_t).any()
+    assert not bits(got_t).any()
 
 
 def test_temperature_zero_random_among_the_maxima(scamd):
@@ -119,7 +113,7 @@ def test_temperature_zero_random_among_the_maxima(scamd):
     bad = np.flatnonzero(got_c != np.array(want, np.int32))
     for i in bad[:20]:
         print(f"tie_random: nc={nc[i]} u={u[i]!r} counts={n_act[i, :nc[i]].tolist()} device {got_c[i]} want {want[i]}")
-    assert bad.size == 0 and not _bits(got_t).any()
+    assert bad.size == 0 and not bits(got_t).any()
     assert len(set(got_c.tolist())) > 6
 
 
@@ -160,7 +154,6 @@ def test_selfplay_games_exact_at_fractional_temperature(scamd, orc, temperature)
 def test_net_in_the_loop_games_exact_at_fractional_temperature(scamd, orc):
     """the same through the network and the fused one-launch step (k_step), at temperature 0.6: the oracle plays with the
     engine's `predict` as its evaluator (the pattern of test_net_in_the_loop_games_exact)"""
-    from test_gpu_netloop import GpuPredictEvaluator
     cfg = dict(rollout_num=40, num_steps=7, cpuct=2.5, temperature=0.6, temperature_switch=2, with_noise=False)
     eng = scamd.Engine(2, 128, seed=22, precision="bf16")
     sp = scamd.SelfPlay(eng, n_slots=64, n_games=64, seed=9, first_game_id=700, outcome_gate=100, **cfg)

@@ -5,60 +5,16 @@ use, the ring as a source, the layouts, the grouping by history records -- and d
 sampled games of the device result (assert_games_equal_oracle) and of the host result.  Device buffers come from hipMalloc on
 the HIP runtime libsc_engine.so uses (ctypes): this file does not import torch -- the torch interop runs in a child process of
 its own."""
-import json
 import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from helpers import random_games
-from support import dev_per_test, _p, scamd_gpu  # noqa: F401
+from helpers import random_games, random_steps
+from support import ROOT, _p, _read, alloc_outputs, dev_per_test, run_steps, run_torch_child, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _outputs(dev, P, n, layout):
-    P1 = max(P, 1)
-    b = dev.alloc(P1 * 7168 * (4 if layout else 1))
-    return dict(boards=b, meta=dev.alloc(P1 * 28), dist=dev.alloc(P1 * 4672 * 4), dist_legal=dev.alloc(P1 * 224 * 4),
-                legal_idx=dev.alloc(P1 * 448), n_legal=dev.alloc(P1 * 4), status=dev.alloc(max(n, 1) * 4))
-
-
-def _read(dev, o, P, n, layout):
-    return dict(boards=dev.read(o["boards"], (P, 112, 8, 8) if layout else (P, 8, 8, 112), np.float32 if layout else np.int8),
-                meta=dev.read(o["meta"], (P, 7), np.float32 if layout else np.int32), dist=dev.read(o["dist"], (P, 4672), np.float32),
-                dist_legal=dev.read(o["dist_legal"], (P, 224), np.float32), legal_idx=dev.read(o["legal_idx"], (P, 224), np.uint16),
-                n_legal=dev.read(o["n_legal"], (P,), np.int32), status=dev.read(o["status"], (n,), np.int32))
-
-
-def run_device(scamd, dev, games, mirror=False, layout=0):
-    """sc_encode_steps_device on a non-default stream; read back after synchronising that stream"""
-    mv, off, cm, cn, coff = scamd.pack_steps(games)
-    n, P = len(games), int(off[-1])
-    o = _outputs(dev, P, n, layout)
-    rc = scamd.lib().sc_encode_steps_device(None, 0, n, _p(mv), _p(off), _p(cm), _p(cn), _p(coff), int(mirror), layout, dev.stream,
-                                            o["boards"], o["meta"], o["dist"], o["dist_legal"], o["legal_idx"], o["n_legal"], o["status"])
-    assert rc == 0, scamd.lib().sc_last_error().decode()
-    dev.sync()
-    r = _read(dev, o, P, n, layout)
-    r["ply_off"] = off
-    return r
-
-
-def _random_steps(orc, moves, rnd):
-    st = orc.State()
-    steps = []
-    for m in moves:
-        lm = st.legal_moves()
-        order = list(range(len(lm)))
-        rnd.shuffle(order)
-        steps.append((m, [(lm[i], rnd.randint(0, 200)) for i in order]))
-        st.push(m)
-    return steps
 
 
 def assert_games_equal_oracle(orc, r, steps, sample, mirror=False):
@@ -102,10 +58,10 @@ def test_device_matches_host_path(scamd, orc, dev, mirror):
     rnd = random.Random(11)
     games = [g for g, _ in random_games(orc, 40, 120, seed=77) if g]
     games.append(games[0][:1])
-    steps = [_random_steps(orc, g, rnd) for g in games]
+    steps = [random_steps(orc, g, rnd) for g in games]
     steps.insert(3, [])   # a game without plies
     h = scamd.encode_steps_batch(steps, mirror)
-    d = run_device(scamd, dev, steps, mirror)
+    d = run_steps(scamd, dev, steps, mirror)
     assert (h["status"] == 0).all()
     assert_same_as_host(d, h)
     assert_games_equal_oracle(orc, d, steps, (0, len(steps) // 2, len(steps) - 1), mirror)
@@ -122,7 +78,7 @@ def test_device_errors_like_the_host_path(scamd, orc, dev):
     h = scamd.encode_steps_batch(cases)
     assert h["status"].tolist() == [1000, 1000, -1, -2, 1001, 0]
     for mirror in (False, True):
-        d = run_device(scamd, dev, cases, mirror)
+        d = run_steps(scamd, dev, cases, mirror)
         assert_same_as_host(d, scamd.encode_steps_batch(cases, mirror), skip=_first_bad_ply(h["status"]))
 
 
@@ -157,7 +113,7 @@ def test_long_game_among_many_short_ones(scamd, orc, dev):
     games = _long_and_short(orc)
     batch = [games[1]] * 750 + [games[0]] + [games[1]] * 750
     h = scamd.encode_steps_batch(batch)
-    d = run_device(scamd, dev, batch)
+    d = run_steps(scamd, dev, batch)
     assert (d["status"] == 0).all()
     assert_same_as_host(d, h)
     assert_games_equal_oracle(orc, d, batch, (0, 750, 1500))
@@ -177,7 +133,7 @@ def test_host_slices_and_record_groups_differ(scamd, orc):
     assert_games_equal_oracle(orc, r, batch, (0, 1, 750, 1500))
     rnd = random.Random(2)
     base = [g for g, _ in random_games(orc, 30, 150, seed=5) if len(g) >= 40]
-    steps = [_random_steps(orc, g, rnd) for g in (base * 5)[:110]]
+    steps = [random_steps(orc, g, rnd) for g in (base * 5)[:110]]
     steps.insert(55, long_game)
     r = scamd.encode_steps_batch(steps)
     sl = _slices(r["ply_off"])
@@ -188,18 +144,18 @@ def test_host_slices_and_record_groups_differ(scamd, orc):
 def test_more_plies_than_one_host_chunk(scamd, orc, dev):
     rnd = random.Random(2)
     base = [g for g, _ in random_games(orc, 30, 150, seed=5) if len(g) >= 40]
-    steps = [_random_steps(orc, g, rnd) for g in (base * 5)[:110]]
+    steps = [random_steps(orc, g, rnd) for g in (base * 5)[:110]]
     h = scamd.encode_steps_batch(steps)
     assert int(h["ply_off"][-1]) > 8192
-    assert_same_as_host(run_device(scamd, dev, steps), h)
+    assert_same_as_host(run_steps(scamd, dev, steps), h)
 
 
 def test_layouts_agree_and_sparse_equals_dense(scamd, orc, dev):
     rnd = random.Random(5)
-    steps = [_random_steps(orc, g, rnd) for g, _ in random_games(orc, 12, 90, seed=9) if g]
+    steps = [random_steps(orc, g, rnd) for g, _ in random_games(orc, 12, 90, seed=9) if g]
     for mirror in (False, True):
-        ref = run_device(scamd, dev, steps, mirror, layout=0)
-        tr = run_device(scamd, dev, steps, mirror, layout=1)
+        ref = run_steps(scamd, dev, steps, mirror, layout=0)
+        tr = run_steps(scamd, dev, steps, mirror, layout=1)
         assert np.array_equal(tr["boards"], ref["boards"].astype(np.float32).transpose(0, 3, 1, 2))
         assert np.array_equal(tr["meta"], ref["meta"].astype(np.float32))
         for k in ("dist", "dist_legal", "legal_idx", "n_legal", "status"):
@@ -215,7 +171,7 @@ def test_bad_pointers_are_refused(scamd, dev):
     games = [[("e2e4", [])]]
     mv, off, cm, cn, coff = scamd.pack_steps(games)
     L = scamd.lib()
-    o = _outputs(dev, 1, 1, 0)
+    o = alloc_outputs(dev, 1, 1, 0)
     host = np.zeros(7168, np.int8)
     st_host = np.zeros(1, np.int32)
     rc = L.sc_encode_steps_device(None, 0, 1, _p(mv), _p(off), _p(cm), _p(cn), _p(coff), 0, 0, dev.stream, _p(host), None, None, None,
@@ -243,7 +199,7 @@ def _encode_traces(scamd, sp, dev, games, mirror=False, layout=0):
     if rc:
         return rc, None
     P = int(off[-1])
-    o = _outputs(dev, P, len(games), layout)
+    o = alloc_outputs(dev, P, len(games), layout)
     rc = L.sc_selfplay_encode_traces(sp.h, len(games), _p(g), int(mirror), layout, dev.stream, _p(off), o["boards"], o["meta"], o["dist"],
                                      o["dist_legal"], o["legal_idx"], o["n_legal"], o["status"])
     assert rc == 0, L.sc_last_error().decode()
@@ -341,12 +297,7 @@ def test_torch_interop_in_a_fresh_process(scamd, tmp_path):
     """torch imported first, then scamd: one HIP runtime in the process, encode_steps_torch / training_tensors equal the host
     path on cuda:0, and a loss on them runs (a child process: this one keeps its own runtime)"""
     pytest.importorskip("torch")
-    script = tmp_path / "child.py"
-    script.write_text(_CHILD)
-    r = subprocess.run([sys.executable, str(script), os.path.join(ROOT, "smart-chess-rust_amd")], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_torch_child(tmp_path, _CHILD, os.path.join(ROOT, "smart-chess-rust_amd"), timeout=600)
     assert len(out["hip_runtimes"]) == 1, out
     assert out["host_equal"] and out["trainer_equal"] and out["outcome_equal"] and out["ring_equal"], out
     assert np.isfinite(out["loss"]) and out["grad_finite"], out

@@ -11,8 +11,8 @@ import pytest
 
 from helpers import _same_tree
 from san_ref import one_hot_steps, san_of, yardstick_moves
-from support import TENSORS, _p, _read, _sizes, assert_bit_equal, dev_per_test, run_san, scamd_gpu  # noqa: F401
-from test_oracle_rules import PERFT
+from lines import PERFT
+from support import TENSORS, _p, _read, alloc_outputs, assert_bit_equal, dev_per_test, run_san, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -350,8 +350,7 @@ def _walk(orc, text, n, seed):
 
 
 def _run_from(scamd, dev, call, n, P, head, mirror, layout, with_moves):
-    o = {k: dev.alloc(nb) for k, nb in _sizes(P, layout).items() if with_moves or k != "moves"}
-    o["status"] = dev.alloc(max(n, 1) * 4)
+    o = alloc_outputs(dev, P, n, layout, skip=() if with_moves else ("moves",))
     tail = [o[k] for k in TENSORS] + ([o["moves"]] if with_moves else []) + [o["status"]]
     rc = call(None, 0, n, *head, int(mirror), layout, dev.stream, *tail)
     assert rc == 0, scamd.lib().sc_last_error().decode()

@@ -10,11 +10,9 @@ import numpy as np
 import pytest
 
 from helpers import random_games
-from support import scamd_gpu  # noqa: F401
+from support import GOLD, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _tv(a, b):

@@ -11,50 +11,29 @@ bounds.  tests/test_heads_ref.py holds the CPU oracle to the same closed forms, 
 sets and shows that six subtly wrong nets fail.  Engines are built from weight blobs, one per probe net.
 
 Every comparison prints its measured maximum, the bound at that element and the largest share of a bound that was used."""
-import os
 from contextlib import closing
 
 import numpy as np
 import pytest
 
 import heads_ref as hr
-import scw
 import tower_ref as tw
-from support import scamd_gpu  # noqa: F401
+from helpers import bits, golden_boards
+from support import IDS, INST, engine_from_state, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-INST = [(128, "bf16"), (256, "bf16"), (128, "fp8"), (256, "fp8")]
-IDS = [f"{C}_{p}" for C, p in INST]
-
-
-def _engine(scamd, tmp_path, sd, nb, C, prec):
-    tw.representable(sd, prec)
-    path = str(tmp_path / "w.scw")
-    scw.write_scw(path, sd, nb, C)
-    eng = scamd.Engine(n_res_blocks=nb, channels=C, weights=path, precision=prec)
-    assert eng.precision == prec and eng.channels == C
-    return eng
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _golden_boards():
-    return np.load(os.path.join(GOLD, "nn_ref_b1_c256.npz"))["boards"][[0, 3, 5, 7]]
 
 
 def _value_set():
     """every plane x every pixel as a lone impulse (7168 rows), the dense set of the trunk tests, six multi-impulse boards"""
-    b = np.concatenate([hr.impulse_positions(), tw.dense_boards(_golden_boards()), hr.random_boards(6)])
+    b = np.concatenate([hr.impulse_positions(), tw.dense_boards(golden_boards()), hr.random_boards(6)])
     return b, hr.metas(len(b))
 
 
 def _policy_set():
     """16 multi-impulse boards (every pixel a pattern of its own), the dense set, four lone impulses"""
     imp = hr.impulse_positions()
-    return np.concatenate([hr.random_boards(16), tw.dense_boards(_golden_boards()), imp[[0, 1000, 3333, 7167]]])
+    return np.concatenate([hr.random_boards(16), tw.dense_boards(golden_boards()), imp[[0, 1000, 3333, 7167]]])
 
 
 def _values(eng, boards, meta, size=2048):
@@ -72,9 +51,9 @@ def _batch_edges(label, eng, boards, meta, big_v=None, big_lp=None):
         assert s.stop <= n
         lp, v = eng.forward(boards[s], meta[s], want_logp=big_lp is not None)
         if big_v is not None:
-            assert np.array_equal(_bits(v), _bits(big_v[s])), (label, size)
+            assert np.array_equal(bits(v), bits(big_v[s])), (label, size)
         if big_lp is not None:
-            assert np.array_equal(_bits(lp), _bits(big_lp[s])), (label, size)
+            assert np.array_equal(bits(lp), bits(big_lp[s])), (label, size)
 
 
 # ---------------------------------------------------------------------------------- the latent the heads start from
@@ -83,16 +62,16 @@ def test_latent_is_the_sign_pattern(scamd, tmp_path, C, prec):
     """the residual stream after the stem and at the end of a one-block net, rounded as the head convs round it, is G[c] [sign +] bit
     for bit, on lone impulses, dense and multi-impulse boards, for every probe net"""
     imp = hr.impulse_positions()
-    boards = np.concatenate([imp[::61], tw.dense_boards(_golden_boards()), hr.random_boards(4)])
+    boards = np.concatenate([imp[::61], tw.dense_boards(golden_boards()), hr.random_boards(4)])
     for k in range(len(hr.nets(C))):
         sd = hr.net(C, prec, k)
         want = hr.latent_form(sd, C, prec, boards)
-        with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
             for stage in (0, 1000):
                 x = eng.debug(boards, np.zeros((len(boards), 7), np.int32), stage)
                 assert np.isfinite(x).all()
                 got = tw.r_act(x, prec)
-                assert np.array_equal(_bits(got + 0.0), _bits(want)), (k, stage, int((got != want).sum()))
+                assert np.array_equal(bits(got + 0.0), bits(want)), (k, stage, int((got != want).sum()))
                 gap = np.abs(x - want).max()
                 print(f"{C} {prec} net {k} stage {stage}: latent operand equals the pattern; max |fp32 stream - pattern| {gap:.2e}")
 
@@ -107,7 +86,7 @@ def test_value_head(scamd, tmp_path, C, prec):
     for k in range(len(hr.nets(C))):
         sd = hr.net(C, prec, k)
         ref, bd, _ = hr.form_v(sd, C, prec, boards, meta)
-        with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
             v = _values(eng, boards, meta)
             top = max(top, tw.compare(f"{C} {prec} (v) net {k}, {len(boards)} positions", v, ref, bd))
             assert np.array_equal(np.sign(v), np.sign(ref))
@@ -127,14 +106,14 @@ def test_policy_head(scamd, tmp_path, C, prec):
     for k, big72 in [(k, False) for k in range(len(hr.nets(C)))] + [(0, True)]:
         sd = hr.net(C, prec, k, big72=big72)
         ref, bd = hr.form_p(sd, C, prec, boards)
-        with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
             lp, _ = eng.forward(boards, meta)
             top = max(top, tw.compare(f"{C} {prec} (p) net {k}{' big72' if big72 else ''}", lp, ref, bd))
             one, _ = eng.forward(boards[3:4], meta[3:4])
-            assert np.array_equal(_bits(one), _bits(lp[3:4]))
+            assert np.array_equal(bits(one), bits(lp[3:4]))
             wide = np.concatenate([boards] * 5)[:129]
             lpw, _ = eng.forward(wide, hr.metas(129))
-            assert np.array_equal(_bits(lpw), _bits(np.concatenate([lp] * 5)[:129])), k
+            assert np.array_equal(bits(lpw), bits(np.concatenate([lp] * 5)[:129])), k
     print(f"{C} {prec} (p): largest share of a bound {top:.3f}")
 
 
@@ -149,7 +128,7 @@ def test_heads_at_every_depth(scamd, tmp_path, C, prec):
     got = {}
     for nb in (0, 1, 3):
         sd = hr.net(C, prec, 1, nb=nb)
-        with closing(_engine(scamd, tmp_path, sd, nb, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, nb, C, prec)) as eng:
             got[nb] = eng.forward(boards, meta)
         assert np.isfinite(got[nb][0]).all() and np.isfinite(got[nb][1]).all()
         ref, bd, _ = hr.form_v(sd, C, prec, boards, meta)
@@ -157,4 +136,4 @@ def test_heads_at_every_depth(scamd, tmp_path, C, prec):
         ref, bd = hr.form_p(sd, C, prec, boards)
         tw.compare(f"{C} {prec} (r) logp, {nb} blocks", got[nb][0], ref, bd)
     for nb in (1, 3):
-        assert np.array_equal(_bits(got[nb][0]), _bits(got[0][0])) and np.array_equal(_bits(got[nb][1]), _bits(got[0][1])), nb
+        assert np.array_equal(bits(got[nb][0]), bits(got[0][0])) and np.array_equal(bits(got[nb][1]), bits(got[0][1])), nb

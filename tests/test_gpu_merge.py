@@ -3,23 +3,18 @@ bit for bit -- there is no tolerance in this feature.  Device buffers come from 
 (ctypes), pre-filled with 0x5a, and the stream is not the default one: this file does not import torch; the replay buffer on top
 runs in a child process that imports torch before scamd."""
 import ctypes as C
-import json
 import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import batch_ref
 import merge_ref
-from helpers import random_games
-from support import open_dev, _p, scamd_gpu  # noqa: F401
+from helpers import random_games, random_steps
+from support import FILL, ROOT, _p, open_dev, run_torch_child, scamd_gpu, untouched  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILL = 0x5a
 KEYS = merge_ref.KEYS
 OUT = KEYS + ("count", "first")
 ROW_BYTES = dict(boards=7168, meta=28, dist_legal=896, legal_idx=448, n_legal=4, outcome=4, count=4, first=4)
@@ -36,10 +31,6 @@ def dev(scamd):
 def _same(a, b):
     a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-def untouched(a):
-    return (np.ascontiguousarray(a).view(np.uint8) == FILL).all()
 
 
 def upload(dev, src):
@@ -271,24 +262,12 @@ def test_null_outputs_and_refusals(scamd, dev, duplicates):
 
 
 # ------------------------------------------------------------------ 8: encoder data
-def _random_steps(orc, moves, rnd):
-    st = orc.State()
-    steps = []
-    for m in moves:
-        lm = st.legal_moves()
-        order = list(range(len(lm)))
-        rnd.shuffle(order)
-        steps.append((m, [(lm[i], rnd.randint(0, 200)) for i in order]))
-        st.push(m)
-    return steps
-
-
 def test_encoded_games_with_twins(scamd, orc, dev):
     """every game encoded twice in one call, with visit counts of its own each time: every ply has a twin, ply 0 is one large
     group; the merged rows feed sc_gather_batch"""
     rnd = random.Random(7)
     games = [g for g, _ in random_games(orc, 5, 50, seed=23) if g]
-    steps = [_random_steps(orc, g, rnd) for g in games]
+    steps = [random_steps(orc, g, rnd) for g in games]
     steps += [[(m, [(c, rnd.randint(0, 200)) for c, _ in ch]) for m, ch in st] for st in steps]
     mv, off, cm, cn, coff = scamd.pack_steps(steps)
     n, P = len(steps), int(off[-1])
@@ -494,12 +473,7 @@ print(json.dumps(out))
 def test_replay_buffer_unique_in_a_fresh_process(scamd, tmp_path):
     """torch imported first, then scamd (a child process: this one keeps its own runtime)"""
     pytest.importorskip("torch")
-    script = tmp_path / "child.py"
-    script.write_text(_CHILD)
-    r = subprocess.run([sys.executable, str(script), os.path.join(ROOT, "smart-chess-rust_amd"), os.path.join(ROOT, "tests")],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_torch_child(tmp_path, _CHILD, os.path.join(ROOT, "smart-chess-rust_amd"), os.path.join(ROOT, "tests"), timeout=600)
     assert out["G"] < out["P"] and out["G_buffer"] < out["E"], out
     assert out["merge_equals_yardstick"] and out["unique_by_ply"] and out["ply0"] == [12, 1], out
     assert out["plain_unchanged"] and out["merged_equals_yardstick"] and out["merged_is_kept"], out

@@ -13,18 +13,15 @@ prior in the last bit and shows up here.
 
 Second half: the same comparison in distribution against the fp32 oracle network (what the reference's libtorch backend
 computes, py/module.py:135-154), where bf16 / fp8 operand rounding makes the trees diverge chaotically."""
-import os
-
 import numpy as np
 import pytest
 
-from helpers import GpuPredictEvaluator, _assert_same, random_games  # noqa: F401
+from helpers import GpuPredictEvaluator, _assert_same, random_games
+from lines import WIDE
 from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-WIDE = ("e2e3 d7d5 d1g4 d8d6 f1b5 e8d8 b1c3 d6h2 c3d5 h2d6 h1h6 d6a3 b2b3 a3a4 c1b2 c7c5 b2e5 a4b3").split()
 LINES = [
     [],                                                        # start position: history planes empty
     ["e2e4", "c7c5", "g1f3"],                                  # Black to move: rotated view, short history

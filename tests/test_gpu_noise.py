@@ -20,9 +20,9 @@ import numpy as np
 import pytest
 
 import noise_ref as nr
-from helpers import load_edge_lines
+from helpers import _same_tree, bits, load_edge_lines
+from lines import WIDE, WIDE137, pushed
 from support import scamd_gpu  # noqa: F401
-from test_gpu_parity2 import WIDE, WIDE137, _pushed, _same_tree
 
 pytestmark = pytest.mark.gpu
 MAXC = 224
@@ -49,10 +49,6 @@ def _root(nc):
     if nc == 2:      # a check evasion (tests/golden/edge_lines.json): 3 ... Qh4+ against e4 / f3, two replies
         return _edge_line("king_xray_step_walk0", 4), None
     return {20: [], 64: WIDE137[:38], 65: WIDE137[:56], 63: WIDE137[:78], 82: WIDE, 128: WIDE137[:108], 137: WIDE137}[nc], None
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _assert_equals_replay(dev, seed, games, plies, sims, nc, what, cap=True):
@@ -101,7 +97,7 @@ def test_every_sample_equals_the_replay(scamd, orc, nc):
     set_position(fen=...), which the device accepts.  Measured figures per width: the module's docstring."""
     from scamd.fen import Positions
     moves, fen = _root(nc)
-    st = orc.State(fen) if fen else _pushed(orc, moves)
+    st = orc.State(fen) if fen else pushed(orc, moves)
     assert len(st.legal_moves()) == nc and st.outcome() is None
     seed, first = 8, (0 if nc == 20 else 1000 + nc)
     sp = scamd.SelfPlay(None, n_slots=64, n_games=64, rollout_num=400, num_steps=4, evaluator="synth", with_noise=True, seed=seed,
@@ -127,7 +123,7 @@ def test_every_sample_equals_the_replay(scamd, orc, nc):
 def test_a_single_reply_draws_nothing(scamd, orc):
     """a root with ONE child takes no arg-max and draws no noise: the buffer keeps the host's bytes"""
     line = _edge_line("ep_evades_pawn_check_walk1", 5)
-    assert len(_pushed(orc, line).legal_moves()) == 1
+    assert len(pushed(orc, line).legal_moves()) == 1
     sp = scamd.SelfPlay(None, n_slots=2, n_games=2, rollout_num=400, num_steps=4, evaluator="synth", with_noise=True, seed=8)
     sp.set_position(1, line)
     sp.set_noise(1, np.full(MAXC, SENTINEL, np.float32))
@@ -164,7 +160,7 @@ def _assert_same_bits(a, b, keys, what):
     assert keys
     for k in keys:
         assert k in a and k in b, (what, k)
-        assert a[k][1] == b[k][1] and np.array_equal(_bits(a[k][2]), _bits(b[k][2])), (what, k, a[k][0], b[k][0])
+        assert a[k][1] == b[k][1] and np.array_equal(bits(a[k][2]), bits(b[k][2])), (what, k, a[k][0], b[k][0])
 
 
 def test_key_is_seed_game_ply_simulation_child(scamd):
@@ -198,10 +194,10 @@ def test_key_is_seed_game_ply_simulation_child(scamd):
     assert set(Wr) == {(10, 2, s) for s in range(1, 6)}
     _assert_same_bits(Wr, Y, sorted(Wr), "set_position at ply 2")
     # anything else in the key changes the sample
-    assert len({tuple(_bits(v[2]).tolist()) for v in Y.values()}) == len(Y)
+    assert len({tuple(bits(v[2]).tolist()) for v in Y.values()}) == len(Y)
     firsts = {}
     for (g, p, s), v in Y.items():
-        firsts.setdefault((p, s), set()).add(int(_bits(v[2])[0]))
+        firsts.setdefault((p, s), set()).add(int(bits(v[2])[0]))
     assert all(len(f) == 110 for f in firsts.values())       # child 0 alone tells the 110 games apart at every (ply, simulation)
     # ... and the key is the replay's: every sample of Y, by root width
     by_nc = {}
@@ -224,7 +220,7 @@ def test_search_lockstep_exact_on_device_noise(scamd, orc, line, n_root, R):
     `prior * (1 - epsilon) + noise * epsilon` mix and the uct words of the path that draws on the device"""
     sp = scamd.SelfPlay(None, n_slots=2, n_games=2, rollout_num=R, num_steps=140, cpuct=2.5, with_noise=True, epsilon=0.15,
                         evaluator="synth", external_noise=False, seed=3)
-    st = _pushed(orc, line)
+    st = pushed(orc, line)
     nc = len(st.legal_moves())
     assert n_root in (None, nc)
     sp.set_position(1, line)
@@ -266,7 +262,7 @@ def test_fused_step_and_two_launch_form_draw_the_same_bits(scamd):
             assert sp.timing(reset=False)["tower_launches"] >= 20
         assert sp.stats()["error_flags"] == 0
         sp.close()
-    assert np.array_equal(_bits(got[0]), _bits(got[1]))
+    assert np.array_equal(bits(got[0]), bits(got[1]))
     sims, games = np.meshgrid(np.arange(1, 21), 7 + np.arange(64), indexing="ij")
     for form, a in zip(("one launch", "two launches"), got):
         _assert_equals_replay(a[1:, :, :20], 8, games.ravel(), 0, sims.ravel(), 20, form)

@@ -10,11 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from support import scamd_gpu  # noqa: F401
+from support import ROOT, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAY = os.path.join(ROOT, "smart-chess-rust_amd", "lib", "sc-play")
 SALT_A, SALT_B = 11, 22
 SEARCH = dict(rollout_num=20, cpuct=1.5, temperature=0.0, temperature_switch=0)

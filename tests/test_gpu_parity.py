@@ -11,12 +11,11 @@ import os
 import numpy as np
 import pytest
 
-from helpers import _same_tree, random_games  # noqa: F401
-from support import scamd_gpu  # noqa: F401
+from helpers import _same_tree, random_games, random_steps
+from lines import pushed
+from support import GOLD, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 RTOL = ATOL = 1e-2   # reference convention, scripts/eval_speed.py:40-43
 
 
@@ -288,18 +287,6 @@ def test_selfplay_net_is_deterministic(scamd):
 
 
 # ------------------------------------------------------------------ trace -> training tensors
-def _random_steps(orc, moves, rnd):
-    st = orc.State()
-    steps = []
-    for m in moves:
-        lm = st.legal_moves()
-        order = list(range(len(lm)))
-        rnd.shuffle(order)
-        steps.append((m, [(lm[i], rnd.randint(0, 200)) for i in order]))
-        st.push(m)
-    return steps
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("mirror", [False, True])
 def test_encode_steps_bit_exact(scamd, orc, mirror):
@@ -310,7 +297,7 @@ def test_encode_steps_bit_exact(scamd, orc, mirror):
     rnd = random.Random(11)
     games = [g for g, _ in random_games(orc, 40, 120, seed=77) if g]
     games.append(games[0][:1])
-    steps = [_random_steps(orc, g, rnd) for g in games]
+    steps = [random_steps(orc, g, rnd) for g in games]
     r = scamd.encode_steps_batch(steps, mirror)
     assert (r["status"] == 0).all()
     off = r["ply_off"]
@@ -459,7 +446,7 @@ def test_interactive_play_handle(scamd, orc):
     best = max(c[1] for c in ch)
     assert mv == next(c[0] for c in ch if c[1] == best)
     assert pl.inspect()[3] == [] and pl.moves == line + [mv]
-    pl.apply_move(orc.State.legal_uci(_pushed(orc, pl.moves))[0])
+    pl.apply_move(orc.State.legal_uci(pushed(orc, pl.moves))[0])
     pl.mcts(5)
     assert pl.sp.tree(0)["n"][0] == 5 and len(pl.moves) == 4
     pl.close()
@@ -467,7 +454,7 @@ def test_interactive_play_handle(scamd, orc):
     eng = scamd.Engine(1, 128, seed=2)
     pn = scamd.Play(eng, initial_moves=["d2d4"])
     steps, pri, val = pn.inference()
-    st2 = _pushed(orc, ["d2d4"])
+    st2 = pushed(orc, ["d2d4"])
     assert steps == st2.legal_uci() and 0.9 < float(pri.sum()) <= 1.0 and -1.0 <= val <= 1.0   # (sum + 1e-5) renormalisation
     b, m = pn.encode()
     ob, om = st2.encode()
@@ -476,13 +463,6 @@ def test_interactive_play_handle(scamd, orc):
     assert sum(c[1] for c in pn.inspect()[3]) == 7
     pn.close()
     eng.close()
-
-
-def _pushed(orc, moves):
-    st = orc.State()
-    for m in moves:
-        st.push(m)
-    return st
 
 
 @pytest.mark.gpu
@@ -515,7 +495,7 @@ def test_single_call_search(scamd, orc):
     pl.mcts(40, cpuct=1.5)
     _, _, q, ref = pl.inspect()
     assert rq == q and [(c[0], c[1], c[2]) for c in ch] == ref
-    assert [c[0] for c in ch] == _pushed(orc, line).legal_uci() and sum(c[1] for c in ch) == 39
+    assert [c[0] for c in ch] == pushed(orc, line).legal_uci() and sum(c[1] for c in ch) == 39
     assert abs(sum(c[3] for c in ch) - 1.0) < 0.1
     pl.close()
     eng.close()
@@ -575,7 +555,7 @@ def test_encode_steps_chunking(scamd, orc):
     rnd = random.Random(2)
     base = [g for g, _ in random_games(orc, 30, 150, seed=5) if len(g) >= 40]
     games = (base * 5)[:110]
-    steps = [_random_steps(orc, g, rnd) for g in games]
+    steps = [random_steps(orc, g, rnd) for g in games]
     total = sum(len(s) for s in steps)
     assert total > 8192
     r = scamd.encode_steps_batch(steps)

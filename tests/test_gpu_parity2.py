@@ -8,35 +8,12 @@ import os
 import numpy as np
 import pytest
 
-from helpers import _same_tree, random_games  # noqa: F401
-from support import scamd_gpu  # noqa: F401
+from helpers import _same_tree, random_games
+from lines import MATED, WIDE, WIDE137, pushed
+from support import GOLD, ROOT, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 RTOL = ATOL = 1e-2   # reference convention, scripts/eval_speed.py:40-43
-
-# 18 plies from the start position to a White-to-move position with 82 legal moves (found by a beam search on the
-# oracle's move generator, tools/find_wide_position.py): the root of a search from here has more than 64 children
-WIDE = ("e2e3 d7d5 d1g4 d8d6 f1b5 e8d8 b1c3 d6h2 c3d5 h2d6 h1h6 d6a3 b2b3 a3a4 c1b2 c7c5 b2e5 a4b3").split()
-# 112 plies to a White-to-move position with 137 legal moves (seven white queens; found by a promotion-driven greedy search on
-# the oracle's move generator): a root with more than 128 children -- the third round of lanes of the descent's wide level
-WIDE137 = ("h2h4 g8h6 a2a4 h6g4 f2f4 g4h6 a4a5 h6g4 d2d4 g4f2 e1f2 b8a6 h4h5 a6b4 c2c4 b4c2 "
-           "d1c2 d7d5 c4c5 e8d7 f4f5 d7e8 c2a4 b7b5 a5b6 c7c6 a4c6 c8d7 c6d5 f7f6 b6b7 d8c8 "
-           "c5c6 e8d8 d5a5 d8e8 c6d7 e8f7 a5a2 c8c4 a2c4 e7e6 b7a8q f7g8 d7d8q g8f7 f5e6 f7g8 "
-           "g2g4 a7a5 d4d5 g7g6 h5h6 f6f5 g4g5 a5a4 e6e7 g8f7 e7e8q f7g8 b2b4 f5f4 e2e4 f4f3 "
-           "e4e5 a4a3 e5e6 a3a2 e6e7 a2b1q a1a6 b1f5 d5d6 f5f7 d6d7 f7d5 a6g6 h7g6 e7f8q g8h7 "
-           "d8e7 d5f7 d7d8q h8g8 e8f7 h7h8 h6h7 g8f8 b4b5 f8g8 b5b6 g8e8 b6b7 e8g8 b7b8q g8e8 "
-           "h1h2 e8g8 c4c2 g8e8 e7e4 e8g8 a8a3 g8e8 f7e8 h8g7 f2g3 f3f2 e8e5 g7f7 h7h8q f2g1b").split()
-MATED = ["f2f3", "e7e5", "g2g4", "d8h4"]   # White is checkmated: a game set to this line ends after its first search
-
-
-def _pushed(orc, moves):
-    st = orc.State()
-    for m in moves:
-        st.push(m)
-    return st
-
 
 # ---------------------------------------------------------------------------------- find_max (a3)
 def test_find_max_device_forms(scamd):
@@ -70,7 +47,7 @@ def test_search_with_exact_ties_lockstep(scamd, orc, evaluator, oeval, line):
     Node pools, uct words and paths equal the oracle after every simulation -- with <= 64 and with > 64 children."""
     R = 200
     sp = scamd.SelfPlay(None, n_slots=1, n_games=1, rollout_num=R, num_steps=30, cpuct=2.5, with_noise=False, evaluator=evaluator, seed=3)
-    st = _pushed(orc, line)
+    st = pushed(orc, line)
     n_root = len(st.legal_moves())
     assert n_root == (82 if line else 20)
     sp.set_position(0, line)
@@ -99,7 +76,7 @@ def test_search_wide_root_lockstep_exact(scamd, orc):
     R = 180
     sp = scamd.SelfPlay(None, n_slots=2, n_games=2, rollout_num=R, num_steps=40, cpuct=2.5, with_noise=True, epsilon=0.15,
                         evaluator="synth", external_noise=True, seed=3)
-    st = _pushed(orc, WIDE)
+    st = pushed(orc, WIDE)
     sp.set_position(1, WIDE)
     srch = orc.Search(st)
     rnd = np.random.RandomState(1)
@@ -130,7 +107,7 @@ def test_search_root_with_more_than_128_children_lockstep_exact(scamd, orc, eval
     children 136, 135, ... from the third round of lanes)."""
     R = 220
     sp = scamd.SelfPlay(None, n_slots=2, n_games=2, rollout_num=R, num_steps=130, cpuct=2.5, with_noise=False, evaluator=evaluator, seed=3)
-    st = _pushed(orc, WIDE137)
+    st = pushed(orc, WIDE137)
     assert len(st.legal_moves()) == 137 and st.turn == 1
     sp.set_position(1, WIDE137)
     srch = orc.Search(st)

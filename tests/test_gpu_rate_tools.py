@@ -19,7 +19,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT
+
 GOLDEN = os.path.join(ROOT, "tests", "golden", "rate_tool_lines.json")
 NET = ["--blocks", "2", "--channels", "128"]
 CASES = {

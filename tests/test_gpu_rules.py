@@ -4,18 +4,15 @@ of the search, against the CPU oracle on positions chosen for being hard: the ed
 on every ply and two plies below its final positions, games that play special moves whenever they can, and every position
 four and five plies from the start (perft 4 and 5, known answers that do not depend on the oracle)."""
 import ctypes as C
-import os
 import random
 
 import numpy as np
 import pytest
 
-from helpers import edge_features, load_edge_lines, mv_parts, random_games, special_walk
-from test_gpu_parity import _random_steps, _same_tree
+from helpers import _same_tree, edge_features, load_edge_lines, mv_parts, random_games, random_steps, special_walk
 from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAXC = 224
 HIST_BUDGET = 512 << 20     # bytes of history scratch per sc_encode_positions call: n * (longest line + 2) * 80
 
@@ -246,7 +243,7 @@ def test_encode_steps_on_edge_lines(scamd, orc, mirror):
         names.append(e["category"])
     games += [g for g, _ in random_games(orc, 30, 150, seed=8) if g]
     names += ["random"] * (len(games) - len(names))
-    steps = [_random_steps(orc, g, rnd) for g in games]   # children: the legal moves shuffled, counts 0..200
+    steps = [random_steps(orc, g, rnd) for g in games]   # children: the legal moves shuffled, counts 0..200
     r = scamd.encode_steps_batch(steps, mirror)
     assert (r["status"] == 0).all()
     off = r["ply_off"]

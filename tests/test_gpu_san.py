@@ -5,8 +5,6 @@ children: every legal move, count 1 on the move played and 0 elsewhere.  Device 
 libsc_engine.so uses (ctypes): this file does not import torch -- the torch interop runs in a child process of its own."""
 import json
 import os
-import subprocess
-import sys
 from collections import Counter
 
 import numpy as np
@@ -14,11 +12,9 @@ import pytest
 
 import helpers as H
 from san_ref import PINNED_RIVAL, one_hot_steps, san_of, yardstick_moves
-from support import TENSORS, _p, _sizes, assert_bit_equal, dev_per_test, run_san, run_steps, scamd_gpu  # noqa: F401
+from support import GOLD, ROOT, TENSORS, _p, _sizes, assert_bit_equal, dev_per_test, run_san, run_steps, run_torch_child, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 RESERVED = 0xFFFFFFFFFFFFFFFF
 
 
@@ -253,13 +249,9 @@ def test_torch_scoring_in_a_fresh_process(scamd, golden, tmp_path):
     """torch imported first, then scamd: encode_san_torch on the reference's own ten validation games with their winners, and
     score_torch on that dict, equal score_torch on encode_steps_torch of the yardstick's moves bit for bit"""
     pytest.importorskip("torch")
-    script, job = tmp_path / "child.py", tmp_path / "job.json"
-    script.write_text(_CHILD)
+    job = tmp_path / "job.json"
     job.write_text(json.dumps({"csv": os.path.join(GOLD, "ref_sample_games.csv"), "steps": golden["steps"][:10]}))
-    r = subprocess.run([sys.executable, str(script), os.path.join(ROOT, "smart-chess-rust_amd"), str(job)], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_torch_child(tmp_path, _CHILD, os.path.join(ROOT, "smart-chess-rust_amd"), str(job), timeout=600)
     assert out["status_ok"] and out["moves_equal"] and out["tensors_equal"] and out["outcome_equal"] and out["score_equal"], out
     assert out["n"] == sum(len(g) for g in golden["steps"][:10]) and np.isfinite(out["loss1"]) and out["n_nonfinite"] == 0, out
     assert out["compare_self"] == [out["n"], 0.0, 0.0], out

@@ -17,11 +17,9 @@ import pytest
 
 import helpers as H
 from san_ref import cpu_game
-from support import dev_per_test, _p, scamd_gpu  # noqa: F401
+from support import GOLD, ROOT, _p, dev_per_test, run_torch_child, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 PLAY = os.path.join(ROOT, "smart-chess-rust_amd", "lib", "sc-play")
 GUARD = 4   # words behind each output
 FILL64, FILL32 = 0x5a5a5a5a5a5a5a5a, 0x5a5a5a5a
@@ -419,12 +417,8 @@ print(json.dumps({"sans": sans, "status": status.tolist(), "based": based, "st2"
 
 def test_moves_to_san_on_a_torch_stream(scamd, orc, golden, tmp_path):
     pytest.importorskip("torch")
-    script, job = tmp_path / "child.py", tmp_path / "job.json"
-    script.write_text(_CHILD)
+    job = tmp_path / "job.json"
     job.write_text(json.dumps({"games": [[orc.uci(m) for m in g] for g in golden["moves"][:10]], "fen": THREE_QUEENS}))
-    r = subprocess.run([sys.executable, str(script), os.path.join(ROOT, "smart-chess-rust_amd"), str(job)], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_torch_child(tmp_path, _CHILD, os.path.join(ROOT, "smart-chess-rust_amd"), str(job), timeout=600)
     assert out["status"] == [0] * 10 + [-3, 0] and out["sans"] == golden["words"][:10] + [["e4", "e5"], []]
     assert out["st2"] == [0, 0] and out["based"] == [["Qh4e1"], ["Nf3"]]

@@ -7,7 +7,6 @@ computed from the data: K = 14 roundings per term (the kernels' summation tree i
 EPS_EXP = 2^-23 (expf: 1 ulp in HIP's math-function table).  Device buffers come from hipMalloc on the engine's HIP runtime; the
 torch wrappers run in a child process."""
 import ctypes as C
-import json
 import os
 import random
 import subprocess
@@ -17,29 +16,15 @@ import numpy as np
 import pytest
 
 import score_ref
-from helpers import random_games
-from support import dev_per_module, _p, scamd_gpu  # noqa: F401
+from helpers import random_games, random_steps
+from support import GOLD, ROOT, _p, dev_per_module, run_torch_child, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 GUARD = 0x5a5a5a5a
 
 
 def _at(p, nbytes):
     return C.c_void_p(p.value + int(nbytes))
-
-
-def _random_steps(orc, moves, rnd):
-    st = orc.State()
-    steps = []
-    for m in moves:
-        lm = st.legal_moves()
-        order = list(range(len(lm)))
-        rnd.shuffle(order)
-        steps.append((m, [(lm[i], rnd.randint(0, 200) if rnd.random() < 0.8 else 0) for i in order]))
-        st.push(m)
-    return steps
 
 
 class Positions:
@@ -50,7 +35,7 @@ class Positions:
         base = [g for g, _ in random_games(orc, n_games, maxlen, seed=seed) if g]
         # after 1. a4 the rook move a1-a2 is legal: action 0 (tests/test_encode_device_abi.py)
         base.append([orc.from_uci(u) for u in ("a2a4", "h7h6", "a1a3", "h6h5")])
-        steps = [_random_steps(orc, g, rnd) for g in base * repeat]
+        steps = [random_steps(orc, g, rnd, zero_share=0.2) for g in base * repeat]
         mv, off, cm, cn, coff = scamd.pack_steps(steps)
         n, P = len(steps), int(off[-1])
         self.P, self.dev = P, dev
@@ -419,12 +404,7 @@ def test_selfplay_to_losses_in_a_fresh_process(scamd, tmp_path):
     "reference", dist="legal"), score_torch with the playing engine -> finite loss1 equal to the yardstick on the same tensors;
     forward_torch and compare_torch next to the host entry points; the trainer layout is refused by name"""
     import torch  # noqa: F401  (a missing torch is a failure here, not a reason to skip)
-    script = tmp_path / "child.py"
-    script.write_text(_CHILD)
-    r = subprocess.run([sys.executable, str(script), os.path.join(ROOT, "smart-chess-rust_amd"), os.path.join(ROOT, "tests")],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_torch_child(tmp_path, _CHILD, os.path.join(ROOT, "smart-chess-rust_amd"), os.path.join(ROOT, "tests"), timeout=900)
     print(out)
     assert out["finished"] == 64 and out["P"] > 64 and out["n_nonfinite"] == 0, out
     assert np.isfinite(out["loss1"]) and np.isfinite(out["loss2"]) and np.isfinite(out["pi_entropy"]), out

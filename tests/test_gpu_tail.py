@@ -16,14 +16,11 @@ import pytest
 
 import scw
 import tail_ref as tr
-from support import scamd_gpu  # noqa: F401
-from test_gpu_netloop import WIDE, GpuPredictEvaluator, _assert_same
-from test_gpu_parity2 import WIDE137
+from helpers import GpuPredictEvaluator, _assert_same, bits
+from lines import WIDE, WIDE137
+from support import GOLD, IDS, INST, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-INST = [(128, "bf16"), (256, "bf16"), (128, "fp8"), (256, "fp8")]
-IDS = [f"{C}_{p}" for C, p in INST]
 SEED = 17
 
 
@@ -52,10 +49,6 @@ def _engine(scamd, tmp_path, Cw, precision, b=None, vp=None, gain=None):
     return eng
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 # ---------------------------------------------------------------------------------- a. log-softmax
 @pytest.mark.parametrize("Cw,precision", INST, ids=IDS)
 def test_log_softmax_equals_the_closed_form(scamd, tmp_path, Cw, precision):
@@ -73,8 +66,8 @@ def test_log_softmax_equals_the_closed_form(scamd, tmp_path, Cw, precision):
         print(f"{Cw} {precision} {name}: max |logp - closed form| {err.max():.2e} (bound {bd[np.argmax(err)]:.2e}; largest share of the "
               f"bound {(err / bd).max():.3f}; bound at |logp| <= 40: {bd[near].max():.2e})")
         assert np.isfinite(lp).all() and (err <= bd).all(), (name, err.max(), bd[np.argmax(err / bd)])
-        assert all(np.array_equal(_bits(r), _bits(lp[0])) for r in lp), name                  # the probe removes the input
-        assert np.array_equal(_bits(lp[0]).reshape(73, 64), np.repeat(_bits(lp[0])[::64], 64).reshape(73, 64)), name
+        assert all(np.array_equal(bits(r), bits(lp[0])) for r in lp), name                  # the probe removes the input
+        assert np.array_equal(bits(lp[0]).reshape(73, 64), np.repeat(bits(lp[0])[::64], 64).reshape(73, 64)), name
         got[name] = lp[0].astype(np.float64)
     d = np.abs(got["low"] - got["levels"])
     bd = tr.logp_bound(tr.bias_patterns()["low"]) + tr.logp_bound(tr.bias_patterns()["levels"])
@@ -100,7 +93,7 @@ def _check_priors(eng, label, rows, n_rows, logp_of_row, arg_err_of_row):
         legal[r] = idx.astype(np.uint16)
     pri, val = eng.predict(boards, meta, legal)
     _, val_f = eng.forward(boards, meta, want_logp=False)
-    assert np.array_equal(_bits(val), _bits(val_f)), label                  # empty rows between the others change no value
+    assert np.array_equal(bits(val), bits(val_f)), label                  # empty rows between the others change no value
     assert all(len(pri[r]) == 0 for r in range(1, n_rows, 2))
     worst = dict(rel=0.0, bound=0.0, share=0.0, gap=0.0, gap_bound=0.0)
     for r, n, sname, idx in rows:
@@ -152,7 +145,7 @@ def test_priors_at_every_lane_round_width_natural_nets(scamd, tmp_path, Cw, prec
                 assert lp5.min() < -30, lp5.min()      # else raise the gain
             rows, n_rows = _prior_rows(lp5, np.random.default_rng(4))
             lp, _ = eng.forward(*_inputs(n_rows))
-            assert np.array_equal(_bits(lp[:5]), _bits(lp5))
+            assert np.array_equal(bits(lp[:5]), bits(lp5))
             _check_priors(eng, f"{Cw} {precision} {label} (min logp {lp.min():.1f})", rows, n_rows, lambda r: lp[r], lambda r, idx: 0.0)
 
 
@@ -179,10 +172,10 @@ def test_argmax_branch_on_exact_ties(scamd, tmp_path, Cw, precision):
         with closing(_engine(scamd, tmp_path, Cw, precision, b=b)) as eng:
             pri, val = eng.predict(boards, meta, legal)
             hot, val_a = eng.predict(boards, meta, legal, argmax=True)
-        assert np.array_equal(_bits(val), _bits(val_a)), name
+        assert np.array_equal(bits(val), bits(val_a)), name
         for p, h, idx, w in zip(pri, hot, legal, want):
             ties = np.flatnonzero(idx // 64 == top)
-            assert ties[-1] == w and len(set(_bits(p[ties]))) == 1 and (p[ties] > np.delete(p, ties).max()).all(), (name, len(idx))
+            assert ties[-1] == w and len(set(bits(p[ties]))) == 1 and (p[ties] > np.delete(p, ties).max()).all(), (name, len(idx))
             assert np.array_equal(h, np.eye(len(idx), dtype=np.float32)[w]), (name, len(idx), int(np.argmax(h)), w)
     print(f"{Cw} {precision}: one-hot at the last of the tied maxima at widths 65, 129, 193, 218")
 
@@ -207,9 +200,9 @@ def test_value_equals_the_closed_form(scamd, tmp_path, Cw, precision):
                 assert (np.abs(np.abs(v) - 1) <= 2.0 ** -23).all() and np.array_equal(np.sign(v), 2.0 * grid[:, 0] - 1)
             for n in (1, 64, 65):
                 _, vn = eng.forward(boards[:n], grid[:n], want_logp=False)
-                assert np.array_equal(_bits(vn), _bits(v[:n])), (vname, n)
+                assert np.array_equal(bits(vn), bits(v[:n])), (vname, n)
             _, v2 = eng.predict(boards, grid, [np.arange(3, dtype=np.uint16)] * len(grid))
-            assert np.array_equal(_bits(v2), _bits(v)), vname
+            assert np.array_equal(bits(v2), bits(v)), vname
 
 
 # ---------------------------------------------------------------------------------- e. the search's copy of the tail
@@ -265,7 +258,7 @@ def test_search_copy_of_the_tail(scamd, orc, tmp_path, Cw, precision, n_slots):
             t = h.tree(slot)
             n = len(st.legal_moves())
             _assert_same(t, srch.dump(), ev, name)
-            assert t["n_child"][0] == n and np.array_equal(_bits(t["prior"][1:1 + n]), _bits(ev.priors[0])), name
+            assert t["n_child"][0] == n and np.array_equal(bits(t["prior"][1:1 + n]), bits(ev.priors[0])), name
             idx = np.asarray([orc.move_index(m, st.turn) for m in st.legal_moves()], np.int64)
             ref = tr.priors_from_logp(lp_ref, idx)
             bd, rel = tr.prior_bound(lp_ref, idx, lp_bd[idx])
@@ -276,7 +269,7 @@ def test_search_copy_of_the_tail(scamd, orc, tmp_path, Cw, precision, n_slots):
             print(f"{Cw} {precision} {n_slots} slots {name}: max rel prior error {(err / ref).max():.2e} (bound {rel.max():.2e}); "
                   f"|q[0] - closed form| {v_err:.2e} (bound {v_bd:.2e})")
             assert (err <= bd).all() and rel.max() < tr.CEIL_PRIOR, name
-            assert t["n"][0] == 1 and _bits(t["q"][0]) == _bits(ev.values[0]) and v_err <= v_bd, (name, t["q"][0], v_ref)
+            assert t["n"][0] == 1 and bits(t["q"][0]) == bits(ev.values[0]) and v_err <= v_bd, (name, t["q"][0], v_ref)
             if name == "fen218":
                 assert meta[1] == 303 and tr.bf16_rne(np.float32(303)) == 304
                 done = 1

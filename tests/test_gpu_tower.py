@@ -9,29 +9,16 @@ bounds are a handful of float32 roundings counted from the code; tests/test_towe
 forms and bounds and checks that no bound exceeds 1e-4 of its row's maximum.  Engines are built from weight blobs, one per probe net.
 
 Every comparison prints its measured maximum, the bound at that element and the largest share of a bound that was used."""
-import os
 from contextlib import closing
 
 import numpy as np
 import pytest
 
-import scw
 import tower_ref as tw
-from support import scamd_gpu  # noqa: F401
+from helpers import golden_boards
+from support import IDS, INST, engine_from_state, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-INST = [(128, "bf16"), (256, "bf16"), (128, "fp8"), (256, "fp8")]
-IDS = [f"{C}_{p}" for C, p in INST]
-
-
-def _engine(scamd, tmp_path, sd, nb, C, prec):
-    tw.representable(sd, prec)
-    path = str(tmp_path / "w.scw")
-    scw.write_scw(path, sd, nb, C)
-    eng = scamd.Engine(n_res_blocks=nb, channels=C, weights=path, precision=prec)   # debug() sizes its output by these
-    assert eng.precision == prec and eng.channels == C
-    return eng
 
 
 def _debug(eng, boards, stage):
@@ -42,18 +29,14 @@ def _debug(eng, boards, stage):
     return out
 
 
-def _bits(a):
+def bits_zero_folded(a):
     """the bits of a float32 array with -0 read as +0 (ReLU is one v_max_f32, which may keep the sign of a zero)"""
     return (np.ascontiguousarray(a, np.float32) + np.float32(0)).view(np.uint32)
 
 
-def _golden_boards():
-    return np.load(os.path.join(GOLD, "nn_ref_b1_c256.npz"))["boards"][[0, 3, 5, 7]]
-
-
 def _dense(n):
     """n differing inputs for the probes that remove the input"""
-    b = tw.dense_boards(_golden_boards())
+    b = tw.dense_boards(golden_boards())
     return b[np.arange(n) % len(b)]
 
 
@@ -71,7 +54,7 @@ def test_stem_impulse(scamd, tmp_path, C, prec):
     """(a) a single 1 at (plane, pixel) under natural stem weights: every pixel for 8 planes, six pixels for all 112"""
     sd = tw.net_a(C, prec)
     pl, px = tw.stem_positions()
-    with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+    with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
         got = _debug(eng, tw.impulse_board(pl, px), 0)
     _chunked(f"{C} {prec} (a)", got, lambda s: tw.form_a(sd, prec, pl[s], px[s]), len(pl))
 
@@ -80,11 +63,11 @@ def test_stem_impulse(scamd, tmp_path, C, prec):
 def test_stem_exact_sums(scamd, tmp_path, C, prec):
     """(b) grid stem weights on golden positions, an all-ones and an all-zero board"""
     sd = tw.net_b(C, prec)
-    boards = tw.dense_boards(_golden_boards())
-    with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+    boards = tw.dense_boards(golden_boards())
+    with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
         got = _debug(eng, boards, 0)
     tw.compare(f"{C} {prec} (b)", got, *tw.form_b(sd, boards))
-    assert all(np.array_equal(_bits(got[-1, 0]), _bits(r)) for r in got[-1])       # the all-zero board: every pixel the bias row
+    assert all(np.array_equal(bits_zero_folded(got[-1, 0]), bits_zero_folded(r)) for r in got[-1])       # the all-zero board: every pixel the bias row
 
 
 # ---------------------------------------------------------------------------------- c, d: the block convs, impulses
@@ -94,7 +77,7 @@ def test_conv2_impulse(scamd, tmp_path, C, prec):
     for off in tw.sigmas(C):
         sd, v0, v1 = tw.net_c(C, prec, off)
         ch, px = tw.conv_positions(C, off)
-        with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
             boards = tw.impulse_board(ch - off, px)
             x0, got = _debug(eng, boards, 0), _debug(eng, boards, 1)
         ref0, bd0 = tw.x0_impulse(len(ch), C, ch, px, v0[prec])
@@ -109,7 +92,7 @@ def test_conv1_impulse(scamd, tmp_path, C, prec):
     for off in tw.sigmas(C):
         sd, v0 = tw.net_d(C, prec, off)
         ch, px = tw.conv_positions(C, off)
-        with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
             got = _debug(eng, tw.impulse_board(ch - off, px), 1)
         _chunked(f"{C} {prec} (d) stem map +{off}", got, lambda s: tw.form_d(sd, prec, 0, ch[s], px[s], v0[prec]), len(ch))
 
@@ -121,17 +104,17 @@ def test_block_convs_exact_sums(scamd, tmp_path, C, prec):
     pixels; the probe removes the input, so 7 differing boards give the same bits"""
     boards = _dense(7)
     sd, kap, kap1 = tw.net_e2(C, prec)
-    with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+    with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
         got = _debug(eng, boards, 1)
     ref, bd = tw.form_e2(sd, 0, kap, kap1)
     tw.compare(f"{C} {prec} (e) conv2", got[:1], ref[None], bd[None])
-    assert all(np.array_equal(_bits(got[0]), _bits(g)) for g in got)
+    assert all(np.array_equal(bits_zero_folded(got[0]), bits_zero_folded(g)) for g in got)
     sd, kap = tw.net_e1(C, prec)
-    with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+    with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
         got = _debug(eng, boards, 1)
     ref, bd, keep, alts = tw.form_e1(sd, prec, 0, kap)
     tw.compare(f"{C} {prec} (e) conv1", got[:1], ref[None], bd[None], keep[None], alts)
-    assert all(np.array_equal(_bits(got[0]), _bits(g)) for g in got)
+    assert all(np.array_equal(bits_zero_folded(got[0]), bits_zero_folded(g)) for g in got)
 
 
 @pytest.mark.parametrize("C,prec", INST, ids=IDS)
@@ -141,12 +124,12 @@ def test_squeeze_excitation_exact_sums(scamd, tmp_path, C, prec):
     boards = _dense(5)
     for bname in tw.betas(C):
         sd, kap, beta = tw.net_f(C, prec, bname)
-        with closing(_engine(scamd, tmp_path, sd, 1, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, 1, C, prec)) as eng:
             x0, got = _debug(eng, boards, 0), _debug(eng, boards, 1)
         assert np.array_equal(x0, np.broadcast_to(np.maximum(kap, 0), x0.shape))   # the constant stem, exactly
         ref, bd, _, z = tw.form_f(sd, 0, kap, beta)
         tw.compare(f"{C} {prec} (f) {bname} (z from {z.min():.1f} to {z.max():.1f})", got[0, :1], ref[None], bd[None])
-        assert all(np.array_equal(_bits(got[0, 0]), _bits(r)) for g in got for r in g)
+        assert all(np.array_equal(bits_zero_folded(got[0, 0]), bits_zero_folded(r)) for g in got for r in g)
 
 
 # ---------------------------------------------------------------------------------- g: block position and ring carry
@@ -159,10 +142,10 @@ def test_block_position_and_ring_carry(scamd, tmp_path, C, prec):
     boards = tw.impulse_board(ch, px)
     for k in range(3):
         sd, v0, v1 = tw.net_c(C, prec, 0, nb=3, blk=k)
-        with closing(_engine(scamd, tmp_path, sd, 3, C, prec)) as eng:
+        with closing(engine_from_state(scamd, tmp_path, sd, 3, C, prec)) as eng:
             st = {s: _debug(eng, boards, s) for s in (0, 1, 2, 3, 1000)}
         for s in range(1, k + 1):
-            assert np.array_equal(_bits(st[s]), _bits(st[0])), (k, s)
+            assert np.array_equal(bits_zero_folded(st[s]), bits_zero_folded(st[0])), (k, s)
         _chunked(f"{C} {prec} (g) block {k + 1} of 3", st[k + 1], lambda s: tw.form_c(sd, prec, k, ch[s], px[s], v0[prec], v1[prec]), len(ch))
         for s in list(range(k + 2, 4)) + [1000]:
-            assert np.array_equal(_bits(st[s]), _bits(st[k + 1])), (k, s)
+            assert np.array_equal(bits_zero_folded(st[s]), bits_zero_folded(st[k + 1])), (k, s)

@@ -6,17 +6,14 @@ import json
 import os
 import random
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import trace_text_ref as ref
-from support import scamd_gpu  # noqa: F401
+from support import ROOT, run_torch_child, scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SUMMARY = ("status", "n_steps", "n_children", "n_opening", "has_fen")
 FEN = "r1bqkbnr/pppp1ppp/2n5/4p3/4P3/5N2/PPPP1PPP/RNBQKB1R w KQkq - 2 3"
 
@@ -359,12 +356,7 @@ def test_encoder_on_parsed_traces_in_a_fresh_process(scamd, tmp_path):
     (both layouts, all three dist modes, mirror off and on, a sub-range, a non-default stream), a host pointer is refused, and
     the reader's statuses stand over the encoder's"""
     pytest.importorskip("torch")
-    script = tmp_path / "child.py"
-    script.write_text(_CHILD)
-    r = subprocess.run([sys.executable, str(script), os.path.join(ROOT, "smart-chess-rust_amd"), str(tmp_path)], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    out = json.loads(r.stdout.strip().splitlines()[-1])
+    out = run_torch_child(tmp_path, _CHILD, os.path.join(ROOT, "smart-chess-rust_amd"), str(tmp_path), timeout=600)
     assert out["plies"] > 100 and out["games_equal"] and out["outcomes_equal"], out
     assert out["tensors_equal"] and out["sub_range_equal"] and out["stream_equal"], out
     assert out["host_pointer"] == [-1, True] and out["host_status"] == [-1, -1], out

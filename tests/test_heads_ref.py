@@ -8,8 +8,6 @@ scales).  On the
 full position sets of the GPU tests, with no oracle in the loop: balance of every +- row, exactness of every sum and the tie
 margins (asserted inside the forms), the separation of the 16384 feature columns, the bound ceilings, and that one grid unit in a
 single FC1 output moves the value by a hundred bounds.  Last, six deliberately wrong nets must FAIL the comparison."""
-import os
-
 import numpy as np
 import pytest
 
@@ -17,15 +15,10 @@ import heads_ref as hr
 import scw
 import tail_ref as tr
 import tower_ref as tw
+from helpers import golden_boards
+from support import IDS, INST
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-INST = [(128, "bf16"), (256, "bf16"), (128, "fp8"), (256, "fp8")]
-IDS = [f"{C}_{p}" for C, p in INST]
 MODE = {"fp32": {}, "bf16": dict(emulate_bf16=True), "fp8": dict(emulate_fp8=True)}
-
-
-def _golden_boards():
-    return np.load(os.path.join(GOLD, "nn_ref_b1_c256.npz"))["boards"][[0, 3, 5, 7]]
 
 
 def _oracle(orc, sd, nb, C, mode, boards, meta):
@@ -41,18 +34,18 @@ def _subset(n_imp, n_rand):
     """a spread of lone impulses (first and last plane and pixel among them), the dense set and a few multi-impulse boards"""
     imp = hr.impulse_positions()
     i = np.unique(np.linspace(0, len(imp) - 1, n_imp).astype(int))
-    b = np.concatenate([imp[i], tw.dense_boards(_golden_boards()), hr.random_boards(n_rand)])
+    b = np.concatenate([imp[i], tw.dense_boards(golden_boards()), hr.random_boards(n_rand)])
     return b, hr.metas(len(b))
 
 
 def _full_value_set():
-    b = np.concatenate([hr.impulse_positions(), tw.dense_boards(_golden_boards()), hr.random_boards(6)])
+    b = np.concatenate([hr.impulse_positions(), tw.dense_boards(golden_boards()), hr.random_boards(6)])
     return b, hr.metas(len(b))
 
 
 def _policy_set():
     imp = hr.impulse_positions()
-    return np.concatenate([hr.random_boards(16), tw.dense_boards(_golden_boards()), imp[[0, 1000, 3333, 7167]]])
+    return np.concatenate([hr.random_boards(16), tw.dense_boards(golden_boards()), imp[[0, 1000, 3333, 7167]]])
 
 
 # ---------------------------------------------------------------------------------- the oracle against the closed forms

@@ -6,9 +6,8 @@ import re
 
 import numpy as np
 import pytest
-from support import scamd_built  # noqa: F401
+from support import ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sc_selfplay_set_match": ["sc_selfplay*", "sc_engine*", "sc_engine*", "uint64_t", "uint64_t", "int"],
        "sc_selfplay_match_tally": ["sc_selfplay*", "int64_t"]}
 

@@ -10,9 +10,7 @@ import numpy as np
 import pytest
 
 import merge_ref
-from support import _p, scamd_built  # noqa: F401
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, _p, scamd_built  # noqa: F401
 
 
 def _hand_case():

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import noise_ref as nr
-from test_engine_rules_host import H  # noqa: F401
+from support import rules_host  # noqa: F401
 
 N_DRAWS = 2_000_000
 KEY = dict(seed=8, game=5, ply=0)

@@ -6,9 +6,8 @@ import re
 
 import numpy as np
 import pytest
-from support import scamd_built  # noqa: F401
+from support import ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sc_selfplay_set_openings": 5, "sc_selfplay_get_opening": 4}
 
 

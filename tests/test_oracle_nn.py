@@ -7,8 +7,7 @@ import numpy as np
 import pytest
 
 import scw
-
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
+from support import GOLD
 
 
 @pytest.mark.parametrize("nb", [1, 10, 19, 20])

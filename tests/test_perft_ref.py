@@ -10,9 +10,8 @@ import numpy as np
 import pytest
 
 import perft_ref
-from support import _p, scamd_built  # noqa: F401
+from support import ROOT, _p, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL_ROWS = [(fen, d) for fen, rows in perft_ref.TABLE.items() for d, row in rows.items() if row[0] <= perft_ref.SMALL]
 
 

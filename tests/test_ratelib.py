@@ -9,9 +9,8 @@ import sys
 import pytest
 
 import ratelib
-from support import scamd_built  # noqa: F401
+from support import ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOLS = ("encode_device_rate", "san_rate", "san_write_rate", "score_rate", "merge_rate", "train_batch_rate", "fen_rate", "perft_rate",
          "match_time")
 

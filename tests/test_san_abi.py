@@ -8,10 +8,8 @@ import subprocess
 
 import numpy as np
 import pytest
-from support import scamd_built  # noqa: F401
+from support import GOLD, ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 RESERVED = 0xFFFFFFFFFFFFFFFF
 
 

@@ -8,9 +8,7 @@ import pytest
 
 import helpers as H
 from san_ref import PINNED_RIVAL, cpu_game, san_of, yardstick_moves
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
+from support import GOLD, ROOT
 
 
 @pytest.fixture(scope="module")

@@ -7,9 +7,8 @@ import subprocess
 
 import numpy as np
 import pytest
-from support import scamd_built  # noqa: F401
+from support import ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAY = os.path.join(ROOT, "smart-chess-rust_amd", "lib", "sc-play")
 NEW = (("sc_moves_to_san_device", 7), ("sc_moves_to_san_device_from", 9), ("sc_san_format", 7), ("sc_selfplay_write_pgn", 8))
 

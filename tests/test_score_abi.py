@@ -12,9 +12,8 @@ import numpy as np
 import pytest
 
 import score_ref
-from support import _p, scamd_built  # noqa: F401
+from support import ROOT, _p, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sc_forward_device": 7, "sc_score_positions": 15, "sc_compare_engines": 9}
 
 

@@ -13,8 +13,9 @@ import pytest
 
 import scw
 import tail_ref as tr
+from lines import WIDE
+from support import GOLD
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 MODES = {0: {}, 1: dict(emulate_bf16=True), 2: dict(emulate_fp8=True)}
 _CACHE = {}
 
@@ -29,7 +30,6 @@ def _inputs():
 
 def _eval_roots(orc, net):
     """orc_eval_net on roots of 20, 82 and 218 legal moves -> [(width, action indices, priors, the net's logp row)]"""
-    from test_gpu_netloop import WIDE
     fn = orc.lib().orc_eval_net
     fn.restype, fn.argtypes = None, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     res = []

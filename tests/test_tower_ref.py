@@ -7,23 +7,16 @@ the bounds around the closed forms.  That pins the closed forms and the probes t
 The oracle sums in another order and normalises in float64, so the same bounds must hold for it: the probes are order-free.  On the
 full position sets of the GPU tests, with no oracle in the loop: representability, exact sums, tie margins, bound ceilings, the share
 of rows that form (d) leaves out and its coverage of (input channel, tap).  Last, three deliberately wrong blobs must FAIL."""
-import os
-
 import numpy as np
 import pytest
 
 import scw
 import tower_ref as tw
+from helpers import golden_boards
+from support import IDS, INST
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-INST = [(128, "bf16"), (256, "bf16"), (128, "fp8"), (256, "fp8")]
-IDS = [f"{C}_{p}" for C, p in INST]
 MODE = {"bf16": dict(emulate_bf16=True), "fp8": dict(emulate_fp8=True)}
 META = np.zeros(7, np.int32)
-
-
-def _golden_boards():
-    return np.load(os.path.join(GOLD, "nn_ref_b1_c256.npz"))["boards"][[0, 3, 5, 7]]
 
 
 def _latents(orc, sd, n_blocks, C, prec, boards):
@@ -51,7 +44,7 @@ def test_oracle_stem_forms(orc, C, prec):
     tw.compare(f"oracle {C} {prec} (a)", _latents(orc, sd, 0, C, prec, tw.impulse_board(pl, px)), ref, bd)
     sd = tw.net_b(C, prec)
     tw.representable(sd, prec)
-    boards = tw.dense_boards(_golden_boards())
+    boards = tw.dense_boards(golden_boards())
     ref, bd = tw.form_b(sd, boards)
     tw.compare(f"oracle {C} {prec} (b)", _latents(orc, sd, 0, C, prec, boards), ref, bd)
 
@@ -75,7 +68,7 @@ def test_oracle_conv_impulse_forms(orc, C, prec):
 @pytest.mark.parametrize("C,prec", INST, ids=IDS)
 def test_oracle_exact_sum_forms(orc, C, prec):
     """(e) for both convs and (f) on the 1-block net; the inputs differ, the latents must not"""
-    boards = tw.dense_boards(_golden_boards()[:1])
+    boards = tw.dense_boards(golden_boards()[:1])
     sd, kap, kap1 = tw.net_e2(C, prec)
     tw.representable(sd, prec)
     lat = _latents(orc, sd, 1, C, prec, boards)
@@ -142,7 +135,7 @@ def test_bounds_stay_under_the_ceiling(C, prec):
     pl, px = tw.stem_positions()
     worst["a"] = max(tw.row_ceiling(*tw.form_a(sd, prec, pl[s], px[s])) for s in tw.chunks(len(pl)))
     sd = tw.net_b(C, prec)
-    boards = tw.dense_boards(_golden_boards())
+    boards = tw.dense_boards(golden_boards())
     worst["b"] = tw.row_ceiling(*tw.form_b(sd, boards))
     for b in boards[[0, -2, -1]]:
         assert tw.sums_are_exact(np.float64(b).reshape(1, 64, 112), sd["conv_block.0.weight"], sd["conv_block.0.bias"], (0, 7, 27, 60, 63))
@@ -238,7 +231,7 @@ def test_wrong_blobs_are_caught(orc):
             pl, px = np.asarray([3, 17, 30, 64]), np.asarray([27, 0, 63, 12])
             boards, (ref, bd) = tw.impulse_board(pl, px), tw.form_a(sd, prec, pl, px)
         else:
-            boards = tw.dense_boards(_golden_boards())
+            boards = tw.dense_boards(golden_boards())
             ref, bd = tw.form_b(sd, boards)
         assert share(f"right stem ({form})", _latents(orc, sd, 0, C, prec, boards), ref, bd) <= 1
         W = sd["conv_block.0.weight"].copy()

@@ -6,9 +6,7 @@ import os
 
 import pytest
 import trace_text_ref as ref
-from support import scamd_built  # noqa: F401
-
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
+from support import GOLD, scamd_built  # noqa: F401
 
 
 @pytest.fixture(scope="module")

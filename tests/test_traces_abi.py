@@ -8,9 +8,8 @@ import subprocess
 
 import numpy as np
 import pytest
-from support import scamd_built  # noqa: F401
+from support import ROOT, scamd_built  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = (("sc_traces_read", 5), ("sc_traces_destroy", 1), ("sc_traces_count", 1), ("sc_traces_summary", 8), ("sc_traces_get", 10),
                 ("sc_traces_fen", 4), ("sc_traces_encode_device", 14), ("sc_traces_last_timing", 2))
 

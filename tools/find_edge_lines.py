@@ -186,9 +186,9 @@ def generate(seed):
 
     for name, cat, line, note in HAND:
         add(name, cat, line.split(), note)
-    from test_gpu_parity2 import WIDE, WIDE137
-    add("wide82", "wide64", WIDE, "82 legal moves (tests/test_gpu_parity2.py WIDE)")
-    add("wide137", "wide128", WIDE137, "137 legal moves, seven white queens (tests/test_gpu_parity2.py WIDE137)")
+    from lines import WIDE, WIDE137
+    add("wide82", "wide64", WIDE, "82 legal moves (tests/lines.py WIDE)")
+    add("wide137", "wide128", WIDE137, "137 legal moves, seven white queens (tests/lines.py WIDE137)")
     # a second >128 position: WIDE137 plus one quiet pair of moves that keeps White's count above 128
     st = orc.State()
     for u in WIDE137:

@@ -1,6 +1,6 @@
 """Finds a short move list from the start position to a position with MANY legal moves (default: more than 64, the
 width of a wavefront: the root of a search from there takes the four-round arg-max of the descent).  Beam search on the
-CPU oracle's move generator; test tooling only -- the result is pasted into tests/test_gpu_parity2.py (WIDE).
+CPU oracle's move generator; test tooling only -- the result is pasted into tests/lines.py (WIDE).
 
     python tools/find_wide_position.py [target_legal_moves=80] [max_plies=60]
 """
