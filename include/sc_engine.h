@@ -801,6 +801,42 @@ int sc_selfplay_debug_cycles(sc_selfplay*, int enable, unsigned long long* out);
 int sc_trace_write_json(const char* path, const sc_trace_info* info, const uint16_t* step_move, const float* step_q,
                         const int32_t* child_off, const uint16_t* child_move, const int32_t* child_n,
                         const float* child_q, const float* child_uct);
+/* ------------------------------------------------------------------ trace files written on the device */
+/* Search records -> the text of trace files, formatted by kernels: the bytes are EXACTLY those of sc_trace_write_json /
+ * sc_selfplay_write_trace_json (key order, two-space pretty form, null for a non-finite value, -0.0, "fen" and "opening" behind
+ * "steps", [] for no steps or no children, no trailing newline).  One call formats n games; the text of game g is
+ * text[text_off[g] .. text_off[g + 1]) and comes to the host in one copy.  The work runs on a non-blocking stream of the
+ * writer's own and the calls return when the text is on the host.
+ *
+ * sc_trace_format_f32: the number formatter alone, on the host (no GPU is needed; the kernels compile the same source, which
+ * uses integer arithmetic only): text[i][0 .. len[i]) is the shortest decimal that reads back as the float64 v[i] widens to, in
+ * ryu's pretty layout as the host writer prints it ("null" for a non-finite value); len[i] <= 24, no final zero.
+ * sc_traces_format: host arrays in, host text out.  info [n] (n_steps must equal step_off[g + 1] - step_off[g]; has_outcome,
+ * termination, winner as sc_trace_info), step_off [n + 1] from 0, step_move / step_q one per step, child_off [steps + 1] from 0
+ * into child_move / child_n / child_q / child_uct (at most SC_MAX_MOVES children per step, at most 4000 steps per game),
+ * open_off [n + 1] into opening (NULL: no game has an "opening" member), fens [n] (NULL, or NULL entries: no "fen" member; the
+ * text must need no JSON escape).  text_off [n + 1] is always filled.  text == NULL is the sizing call.  If cap <
+ * text_off[n] the call returns -1 and writes no text.  n == 0 is valid.  Argument errors are found before a device is looked for
+ * (-3: no HIP device).
+ * sc_selfplay_traces_json: the same for finished games of a handle, games[0..n) handle-local indices, read from the trace ring
+ * rows IN PLACE; "opening" and "fen" come from the handle's lines.  Readiness as sc_selfplay_encode_traces: returns 1 if a
+ * requested game has not finished, 2 if its row has been overwritten or released (2 wins over 1); nothing is written then.  If
+ * every requested game is held (trace_hold, reported by the last sc_selfplay_poll) the rows are read without waiting for the
+ * handle's stream, while its simulation steps run; the call has finished reading them when it returns, so the next
+ * sc_selfplay_poll may release them.  Otherwise the handle's work is completed first.  A poisoned handle: SC_ERR_HANDOFF.
+ * sc_selfplay_write_traces_json: the above, and game i's text written to paths[i].  The pinned staging buffer belongs to the
+ * handle and grows on demand.
+ * sc_traces_format_last_timing: measurement aid (tools/trace_write_rate.py) -- HIP-event time of the counting pass and of the
+ * emitting passes (with their scans) of the calling thread's last call of the three above. */
+int sc_trace_format_f32(int n, const float* v, char* text /*[n][24]*/, uint8_t* len);
+int sc_traces_format(int device_id, int n, const sc_trace_info* info, const uint32_t* step_off, const uint16_t* step_move,
+                     const float* step_q, const uint32_t* child_off, const uint16_t* child_move, const int32_t* child_n,
+                     const float* child_q, const float* child_uct, const uint32_t* open_off, const uint16_t* opening,
+                     const char* const* fens, char* text, uint64_t cap, uint64_t* text_off);
+int sc_selfplay_traces_json(sc_selfplay*, int n, const int32_t* games, char* text, uint64_t cap, uint64_t* text_off);
+int sc_selfplay_write_traces_json(sc_selfplay*, int n, const int32_t* games, const char* const* paths);
+int sc_traces_format_last_timing(float* count_ms, float* emit_ms);
+
 /* utility: UCI text of a move (src/chess.rs:513-519); returns strlen */
 int sc_move_uci(uint16_t move, char* buf8);
 /* libsmartchess.chess_encode_move(turn, move) (reference src/lib.rs:37-44; src/chess.rs:544-550, queenmoves.rs,

@@ -121,6 +121,8 @@ extern "C" {
                              child_off: *mut i32, child_move: *mut u16, child_n: *mut i32, child_q: *mut f32,
                              child_uct: *mut f32) -> c_int;
     fn sc_selfplay_write_trace_json(sp: *mut ScSelfplay, game: c_int, path: *const c_char) -> c_int;
+    // the files of a poll round in one call: the text is formatted on the device from the held ring rows
+    fn sc_selfplay_write_traces_json(sp: *mut ScSelfplay, n: c_int, games: *const i32, paths: *const *const c_char) -> c_int;
     // evaluation matches (scripts/leader-board, src/play.rs:318-343): n_games on n_slots recycled slots, both colour assignments
     fn sc_selfplay_set_match(sp: *mut ScSelfplay, a: *mut ScEngine, b: *mut ScEngine, synth_salt_a: u64, synth_salt_b: u64,
                              colours: c_int) -> c_int;
@@ -322,6 +324,15 @@ impl<'a> SelfPlay<'a> {
     pub fn write_trace(&mut self, game: i32, path: &str) {
         let p = CString::new(path).unwrap();
         check(unsafe { sc_selfplay_write_trace_json(self.handle, game as c_int, p.as_ptr()) }, "sc_selfplay_write_trace_json");
+    }
+
+    /// the trace files of finished `games` (handle-local indices) in one call; the bytes are `write_trace`'s
+    pub fn write_traces(&mut self, games: &[i32], paths: &[&str]) {
+        assert_eq!(games.len(), paths.len());
+        let owned: Vec<CString> = paths.iter().map(|p| CString::new(*p).unwrap()).collect();
+        let ptrs: Vec<*const c_char> = owned.iter().map(|p| p.as_ptr()).collect();
+        check(unsafe { sc_selfplay_write_traces_json(self.handle, games.len() as c_int, games.as_ptr(), ptrs.as_ptr()) },
+              "sc_selfplay_write_traces_json");
     }
 }
 

@@ -241,6 +241,23 @@ const uint32_t* traces_range_off(const sc_traces* t, int g0);
 // text to a file, whole or appended
 int write_text_file(const char* path, const std::string& text, bool append);
 
+// ------------------------------------------------------------------ trace files written on the device (trace_write.hip)
+// What a writer keeps between calls: its non-blocking stream, the events around its two passes, the device arena and text
+// buffer and the pinned host buffer the text comes back to, all grown on demand.  sc_traces_format has one per call, a
+// self-play handle keeps one (a hipFree per call would wait for the handle's step launches)
+struct TraceWriter {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevBuf<char> arena, text;
+    char* pinned = nullptr;
+    size_t pinned_cap = 0;
+    TraceWriter() = default;
+    TraceWriter(const TraceWriter&) = delete;
+    TraceWriter& operator=(const TraceWriter&) = delete;
+    ~TraceWriter() { release(); }
+    void release();   // (the owner's device is current)
+};
+
 // ------------------------------------------------------- self-play (selfplay.hip, match_play.hip, selfplay_io.hip, debug_calls.hip)
 struct sc_selfplay {
     sc_engine* engine = nullptr;
@@ -282,6 +299,8 @@ struct sc_selfplay {
     // waits for it before it releases rows
     hipEvent_t enc_ev = nullptr;
     bool enc_pending = false;
+    // sc_selfplay_traces_json / sc_selfplay_write_traces_json: the handle's trace writer, created by the first such call
+    TraceWriter* writer = nullptr;
     // search wave + tower in one launch (step_kernels.hip).  Chosen at creation: only with at most one game per compute
     // unit and a single group -- with more games than CUs the separate search launch runs all of them at once while the
     // fused workgroups (83 KB of LDS: one per CU) would take turns, and with several interleaved groups one group's search
@@ -310,6 +329,11 @@ static int sp_alloc(sc_selfplay* sp, T** ptr, size_t n, bool zero = true) {
 std::vector<float> choice_weights(float temperature, int n_max);
 
 int sp_refuse(const sc_selfplay* sp);   // the error of a poisoned handle
+// A row that sc_selfplay_poll has reported and holds (trace_hold) is final, and no kernel writes it until the next poll releases it
+bool row_held(const sc_selfplay* sp, int row, uint64_t want_id);
+// the ring row may belong to an earlier game (the wanted one has not started), to a later one (overwritten) or be released
+enum RowState { ROW_READY, ROW_NOT_FINISHED, ROW_GONE };
+RowState row_state(const sc_selfplay* sp, int row, uint64_t want_id, const sc::TraceHdr& h);
 // The opening of a host read or write: set the device, complete the last enqueued simulation (expand / backward / ply transition:
 // host reads see a fully backed-up state), wait for the stream; with `latch` also look at the device's error word, and refuse a
 // poisoned handle

@@ -19,6 +19,7 @@ void exclusive_scan_u32(uint32_t n, const uint32_t* d_in, uint32_t* d_tile_sum, 
 #include "encode_types.hpp"
 #include "perft_types.hpp"
 #include "trace_types.hpp"
+#include "trace_write_types.hpp"
 
 struct sc_fen_fields;   // include/sc_engine.h
 
@@ -70,6 +71,11 @@ void fen_ep_legal(int n, const sc::Position* d_rec, int32_t* d_ep_legal, hipStre
 void trace_count(const sctr::Text& t, const sctr::Files& f, hipStream_t s);
 void trace_emit(const sctr::Text& t, const sctr::Files& f, const sctr::Packed& p, hipStream_t s);
 void trace_status(int n, const int32_t* d_over, int32_t* d_status, hipStream_t s);
+// trace_write_kernels.hip: trace files written on the device (sc_traces_format, sc_selfplay_traces_json); the argument blocks are
+// trace_write_types.hpp's.  trace_write_count: the bytes of every ply into d_seg_len[p.seg[.]] (the frames' lengths are the
+// host's; exclusive_scan_u32 then gives o.seg_off).  trace_write_emit: the frames and the plies of a group of games into o.text
+void trace_write_count(const sctw::Plies& p, const sctw::Steps& s, uint32_t* d_seg_len, hipStream_t st);
+void trace_write_emit(const sctw::Plies& p, const sctw::Steps& s, const sctw::Frames& f, const sctw::Out& o, hipStream_t st);
 // nn_kernels.hip
 const char* nn_init();  // sets kernel attributes; returns error text or nullptr
 size_t tower_lds_bytes(int C);

@@ -281,6 +281,7 @@ int main(int argc, char** argv) {
     // [0]: the games with --white-checkpoint's network as White, [1] (--swap): as Black; White won / Black won / draw / no outcome
     long long res[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     std::vector<int32_t> finished;
+    std::vector<std::string> paths;
     for (int g = 0; g < total; g++) {
         sc_trace_info info{};
         if (sc_selfplay_get_trace(sp, g, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) continue;
@@ -288,11 +289,14 @@ int main(int argc, char** argv) {
         const int set = a.swap ? (int)(info.game_id & 1) : 0;
         res[set][!info.has_outcome ? 3 : info.winner == 1 ? 0 : info.winner == 0 ? 1 : 2]++;
         const int number = (int)(a.swap ? info.game_id / 2 : info.game_id) + 1;
-        std::string path = out_name(a, set ? a.swap_output : a.output, number);
-        if (sc_selfplay_write_trace_json(sp, g, path.c_str())) {
-            fprintf(stderr, "%s\n", sc_last_error());
-            rc = 1;
-        }
+        paths.push_back(out_name(a, set ? a.swap_output : a.output, number));
+    }
+    // every trace file in one call: the text is formatted on the device (sc_selfplay_write_traces_json)
+    std::vector<const char*> cpaths;
+    for (const std::string& p : paths) cpaths.push_back(p.c_str());
+    if (sc_selfplay_write_traces_json(sp, (int)finished.size(), finished.data(), cpaths.data())) {
+        fprintf(stderr, "%s\n", sc_last_error());
+        rc = 1;
     }
     if (a.has_pgn && sc_selfplay_write_pgn(sp, (int)finished.size(), finished.data(), a.pgn.c_str(), 0,
                                            player_name(a.white_checkpoint, a.white_seed).c_str(),

@@ -273,6 +273,7 @@ void sc_selfplay_destroy(sc_selfplay* sp) {
         (void)hipEventSynchronize(sp->enc_ev);
         (void)hipEventDestroy(sp->enc_ev);
     }
+    delete sp->writer;
     if (sp->own_stream && sp->stream) (void)hipStreamDestroy(sp->stream);
     delete sp;
 }

@@ -6,14 +6,11 @@
 #include "san_tokens.hpp"
 #include "trace_json.hpp"
 
-// A row that sc_selfplay_poll has reported and holds (trace_hold) is final, and no kernel writes it until the next poll releases it
-static bool row_held(const sc_selfplay* sp, int row, uint64_t want_id) {
+bool row_held(const sc_selfplay* sp, int row, uint64_t want_id) {
     return sp->p.trace_hold && sp->reported[(size_t)row] == want_id + 1 &&
            std::find(sp->to_release.begin(), sp->to_release.end(), row) != sp->to_release.end();
 }
-// the ring row may belong to an earlier game (the wanted one has not started), to a later one (overwritten) or be released
-enum RowState { ROW_READY, ROW_NOT_FINISHED, ROW_GONE };
-static RowState row_state(const sc_selfplay* sp, int row, uint64_t want_id, const sc::TraceHdr& h) {
+RowState row_state(const sc_selfplay* sp, int row, uint64_t want_id, const sc::TraceHdr& h) {
     if (h.state == sc::TR_FREE) return sp->reported[(size_t)row] > want_id ? ROW_GONE : ROW_NOT_FINISHED;
     if (h.game_id > want_id) return ROW_GONE;
     return h.game_id < want_id || h.state != sc::TR_DONE ? ROW_NOT_FINISHED : ROW_READY;

@@ -195,17 +195,26 @@ static int run_gpu(const Args& a, int gpu, int first, int count, int* finished_w
         }
         if (rc) break;
         if (active > 0 && !more) rc = sc_selfplay_enqueue_interleaved(sps.data(), (int)sps.size(), chunk);
-        for (size_t i = 0; i < todo.size() && !rc; i++) {
+        // the round's games of a group in ONE call: their text is formatted on the device from the held rows and comes back in
+        // one copy (sc_selfplay_write_traces_json); todo holds each group's games one after another
+        for (size_t i = 0; i < todo.size() && !rc;) {
             sc_selfplay* sp = sps[todo[i].first];
-            sc_trace_info info{};
-            if (sc_selfplay_get_trace(sp, todo[i].second, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) {
-                rc = 1;
-                break;
+            std::vector<int32_t> games;
+            std::vector<std::string> paths;
+            for (; i < todo.size() && sps[todo[i].first] == sp && !rc; i++) {
+                sc_trace_info info{};
+                if (sc_selfplay_get_trace(sp, todo[i].second, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) {
+                    rc = 1;
+                    break;
+                }
+                with_outcome += info.has_outcome;
+                games.push_back(todo[i].second);
+                paths.push_back(trace_name(a, info.game_id + 1));
             }
-            with_outcome += info.has_outcome;
-            std::string path = trace_name(a, info.game_id + 1);
-            if (sc_selfplay_write_trace_json(sp, todo[i].second, path.c_str())) rc = 1;
-            else written++;
+            std::vector<const char*> cpaths;
+            for (const std::string& p : paths) cpaths.push_back(p.c_str());
+            if (!rc && sc_selfplay_write_traces_json(sp, (int)games.size(), games.data(), cpaths.data())) rc = 1;
+            else if (!rc) written += (int)games.size();
         }
         if (rc || (active == 0 && !more)) break;
     }

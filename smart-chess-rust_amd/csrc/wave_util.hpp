@@ -47,6 +47,18 @@ __device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
     return v;
 }
 
+// the exclusive prefix sum of v over the lanes of the wave (off the hot path, every lane active); *total = the wave's sum
+__device__ inline uint32_t wave_excl_scan_u32(uint32_t v, uint32_t* total) {
+    const int lane = (int)(threadIdx.x & 63u);
+    uint32_t incl = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t x = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += x;
+    }
+    *total = __shfl(incl, 63, 64);
+    return incl - v;
+}
+
 // Synchronisation inside the search functions (dev_expand, dev_select, finish_game): each game is searched by ONE wavefront -- the whole
 // workgroup of k_mcts, or wave 0 of the tower's workgroup in the fused step kernel (k_step), where a workgroup barrier would wait for
 // waves that never come.  A wave's LDS and vector-memory operations take effect in program order; what is needed between a store by one

@@ -129,6 +129,11 @@ ABI = {
     "sc_traces_fen": (_i, [_vp, _i, C.c_char_p, _i]),
     "sc_traces_encode_device": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_traces_last_timing": (_i, [C.POINTER(_f), C.POINTER(_f)]),
+    "sc_trace_format_f32": (_i, [_i, _vp, _vp, _vp]),
+    "sc_traces_format": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "sc_traces_format_last_timing": (_i, [C.POINTER(_f), C.POINTER(_f)]),
+    "sc_selfplay_traces_json": (_i, [_vp, _i, _vp, _vp, C.c_uint64, _vp]),
+    "sc_selfplay_write_traces_json": (_i, [_vp, _i, _vp, _vp]),
     "sc_selfplay_encode_traces": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_forward_device": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sc_score_positions": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

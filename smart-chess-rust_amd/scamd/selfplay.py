@@ -184,6 +184,28 @@ class SelfPlay(_Handle):
     def write_trace(self, game, path):
         _check(self.L.sc_selfplay_write_trace_json(self.h, game, path.encode()))
 
+    def traces_json(self, games):
+        """sc_selfplay_traces_json: the trace-file text of finished games (handle-local indices), formatted on the GPU from the
+        trace ring in one call -> list of bytes, each what write_trace writes for the game.  Raises EngineError with .code 1 if
+        a game has not finished, 2 if its ring row has been overwritten or released."""
+        games = list(games)
+        g = np.ascontiguousarray(games or [0], np.int32)
+        n = len(games)
+        off = np.zeros(n + 1, np.uint64)
+        _check(self.L.sc_selfplay_traces_json(self.h, n, _p(g), None, 0, _p(off)))
+        text = np.zeros(max(int(off[n]), 1), np.uint8)
+        _check(self.L.sc_selfplay_traces_json(self.h, n, _p(g), _p(text), int(off[n]), _p(off)))
+        return [text[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+
+    def write_traces(self, games, paths):
+        """sc_selfplay_write_traces_json: the files write_trace writes for `games`, formatted on the GPU in one call"""
+        games, paths = list(games), [p.encode() for p in paths]
+        if len(games) != len(paths):
+            raise ValueError("one path per game")
+        g = np.ascontiguousarray(games or [0], np.int32)
+        arr = (C.c_char_p * max(len(paths), 1))(*paths)
+        _check(self.L.sc_selfplay_write_traces_json(self.h, len(games), _p(g), arr))
+
     def write_pgn(self, games, path, append=False, white=None, black=None, event=None):
         """finished games (handle-local indices) as PGN, rendered on the GPU in one call (sc_selfplay_write_pgn)"""
         games = list(games)
@@ -204,9 +226,9 @@ class SelfPlay(_Handle):
             active = self.stats()["games_active"]
             if active:
                 self.enqueue(chunk)
-            for g in fin:
-                self.write_trace(g, path_of(self.cfg.first_game_id + g))
-                written += 1
+            if fin:   # the round's games in one call, formatted on the GPU from their held rows
+                self.write_traces(fin, [path_of(self.cfg.first_game_id + g) for g in fin])
+                written += len(fin)
             if not active and not fin:
                 return written
 

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import EngineError, _check, _count, _Handle, _p, _stream, _torch, lib, move_uci
+from .binding import EngineError, _check, _count, _Handle, _moves, _p, _stream, _torch, lib, move_uci
 from .training import _device_outputs, _finish_outputs
 
 # SC_TRACE_ERR_* (include/sc_engine.h): status[g] = -code of a refused file
@@ -114,6 +114,69 @@ def read(sources, device=0):
     off = np.zeros(len(blobs) + 1, np.uint64)
     off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
     return Traces(b"".join(blobs), off, device)
+
+
+def pack_traces(traces):
+    """trace dicts in SelfPlay.trace's shape (steps [(uci, q, [(uci, N, Q, uct), ...]), ...], outcome; optional "opening": list of
+    moves, "fen": str) -> the argument list of sc_traces_format behind its device and count, up to `fens` (numpy arrays are kept
+    alive by the list)"""
+    from .binding import TERMINATION, TraceInfo
+    term = {v: k for k, v in TERMINATION.items()}
+    n = len(traces)
+    info = (TraceInfo * max(n, 1))()
+    steps = [s for t in traces for s in t["steps"]]
+    ch = [c for s in steps for c in s[2]]
+    step_off, open_off = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint32)
+    for g, t in enumerate(traces):
+        oc = t.get("outcome")
+        info[g].n_steps = len(t["steps"])
+        info[g].n_children_total = sum(len(s[2]) for s in t["steps"])
+        info[g].has_outcome = int(oc is not None)
+        info[g].termination = term[oc["termination"]] if oc else 0
+        info[g].winner = {"White": 1, "Black": 0, None: -1}[oc["winner"]] if oc else -1
+        info[g].game_id = int(t.get("game_id", 0))
+        step_off[g + 1] = step_off[g] + len(t["steps"])
+        open_off[g + 1] = open_off[g] + len(t.get("opening") or ())
+    child_off = np.zeros(len(steps) + 1, np.uint32)
+    child_off[1:] = np.cumsum([len(s[2]) for s in steps], dtype=np.uint64)
+    sm, sq = _moves([s[0] for s in steps]), np.asarray([s[1] for s in steps] or [0], np.float32)
+    cm, cn = _moves([c[0] for c in ch]), np.asarray([c[1] for c in ch] or [0], np.int32)
+    cq, cu = np.asarray([c[2] for c in ch] or [0], np.float32), np.asarray([c[3] for c in ch] or [0], np.float32)
+    op = _moves([m for t in traces for m in (t.get("opening") or ())])
+    fens = (C.c_char_p * max(n, 1))(*[t["fen"].encode() if t.get("fen") else None for t in traces])
+    return [info, _p(step_off), _p(sm), _p(sq), _p(child_off), _p(cm), _p(cn), _p(cq), _p(cu), _p(open_off), _p(op), fens], \
+        (step_off, sm, sq, child_off, cm, cn, cq, cu, open_off, op)
+
+
+def format(traces, device=0):
+    """sc_traces_format: the trace-file text of every trace dict, formatted on the GPU in one call -> list of bytes, each exactly
+    what write_trace_json writes for it (a trace may also carry "opening" and "fen", written behind "steps")"""
+    L = lib()
+    n = len(traces)
+    args, keep = pack_traces(traces)
+    off = np.zeros(n + 1, np.uint64)
+    _check(L.sc_traces_format(device, n, *args, None, 0, _p(off)))
+    text = np.zeros(max(int(off[n]), 1), np.uint8)
+    _check(L.sc_traces_format(device, n, *args, _p(text), int(off[n]), _p(off)))
+    del keep
+    return [text[int(off[g]):int(off[g + 1])].tobytes() for g in range(n)]
+
+
+def write(paths, traces, device=0):
+    """format(traces), trace g written to paths[g]"""
+    paths = list(paths)
+    if len(paths) != len(traces):
+        raise ValueError("one path per trace")
+    for p, t in zip(paths, format(traces, device)):
+        with open(p, "wb") as f:
+            f.write(t)
+
+
+def format_last_timing():
+    """(count_ms, emit_ms) of this thread's last device format call (sc_traces_format_last_timing)"""
+    a, b = C.c_float(0), C.c_float(0)
+    lib().sc_traces_format_last_timing(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def encode_traces_torch(traces, g0=0, n=None, apply_mirror=False, layout="trainer", dist="dense", engine=None):
