@@ -674,6 +674,43 @@ int sc_selfplay_get_opening(sc_selfplay*, int game, uint16_t* moves, int cap);
 int sc_selfplay_set_openings_from(sc_selfplay*, int n_lines, const sc_positions* bases, const int32_t* base_idx, const uint16_t* moves,
                                   const uint32_t* move_off, int32_t* status);
 int sc_selfplay_get_opening_fen(sc_selfplay*, int game, char* buf, int cap);
+/* Match play against an outside opponent (the reference's `play --black-type stockfish`, src/play.rs:38-59, 89-142): the handle
+ * searches the engine's plies, the opponent's moves come from the host and are played on the device in many slots at once.
+ * sc_selfplay_set_external: before the first enqueue, on a handle with rollout_factor = 0 and outcome_gate = -1 (the opponent is
+ * never handed a finished position: the reference checks the outcome after every ply).  engine (or NULL: the handle's) evaluates
+ * the engine's plies, synth_salt is the synthetic evaluators' player.  colours: 0 the engine is White in every game, 1 White in the
+ * even games of the handle and Black in the odd ones, 2 Black in every game.  Any n_games >= 1 on any n_slots, with or without a
+ * trace ring; a finished game's slot goes on with the next game, and any game may start at any ply boundary.  On such a handle
+ * sc_selfplay_enqueue_sims, _enqueue_interleaved, _run, _set_players, _set_match and _set_openings[_from] return -1.
+ * A round: sc_selfplay_external_wait -> the opponent's answers -> sc_selfplay_push_moves, repeated while slots wait (a game that
+ * starts with the opponent as White appears in a second pass), then sc_selfplay_external_search.
+ * sc_selfplay_external_search: -1 while a slot waits for the opponent (the count of the last sc_selfplay_external_wait; where moves
+ * were pushed since, or on a fresh handle, the wait kernel runs first and the call completes the handle's work).  Otherwise it
+ * enqueues one searched ply of every live game -- rollout_num simulation steps in the handle's launch form, the expansions that end
+ * the ply, the boundary kernels that count finished games and start the next -- and does not synchronise: two handles with
+ * own_stream = 1 can be overlapped.  sc_selfplay_get_stats().games_active == 0 is the end of the match.
+ * sc_selfplay_external_wait: completes the handle's work; returns the number n of slots that wait for the opponent, in ascending
+ * slot order.  slots / games (handle-local indices) / plies (from the start position) [cap]; fens: n zero-terminated texts, the
+ * text of sc_selfplay_get_fen, entry i at fen_off[i], fen_off[n] the bytes used; moves: each waiting game's moves so far, from its
+ * live trace row (for `position startpos moves ...`), entry i at move_off[i] .. move_off[i + 1].  Any output may be NULL; n > cap
+ * or too small a text or move buffer returns -1 and writes nothing.
+ * sc_selfplay_push_moves: plays moves[i] in slot slots[i] on ANY handle whose listed slots stand at a ply boundary (sim = 0, a fresh
+ * one-node root: after sc_selfplay_set_position, or between two plies), an interactive one-slot handle included.  Completes the
+ * pending work first.  status[i] (may be NULL): 0 the game goes on, 1 this move ended it (outcome, num_steps), -1 the move is not
+ * legal there, -2 the slot does not stand at such a boundary or, on an external handle, the engine is to move; a refused entry
+ * changes nothing.  Returns the number of refused entries; -1 for a slot out of range or listed twice.  n = 0 is fine.  On an
+ * external handle the boundary kernels run behind the moves: a game ended by a pushed move is counted and its slot refilled.
+ * The pushed ply is recorded as the reference records an outside player's ply: children = all legal moves in the generator's
+ * order, visit count 1 on the move played and 0 elsewhere, every value 0.
+ * sc_selfplay_match_tally serves an external handle with a = the engine and b = the opponent; sc_selfplay_poll, _get_trace,
+ * _write_trace_json, _traces_json, _write_pgn (`white` names the engine), _get_fen and _get_slot work unchanged on its games.
+ * sc_selfplay_encode_traces accepts these games: the opponent's plies carry one-hot visit counts, as the reference's traces of
+ * such games do. */
+int sc_selfplay_set_external(sc_selfplay*, sc_engine* engine_or_null, uint64_t synth_salt, int colours);
+int sc_selfplay_external_search(sc_selfplay*);
+int sc_selfplay_external_wait(sc_selfplay*, int cap, int32_t* slots, int32_t* games, int32_t* plies, char* fens, uint64_t fens_cap,
+                              uint32_t* fen_off, uint16_t* moves, uint32_t moves_cap, uint32_t* move_off);
+int sc_selfplay_push_moves(sc_selfplay*, int n, const int32_t* slots, const uint16_t* moves, int32_t* status);
 int sc_selfplay_timing(sc_selfplay*, int reset, float* ms_total, float* ms_nn, int64_t* nn_launches);
 /* Kernel launches per simulation step this handle uses with SC_EVAL_NET (steps bracketed for sc_selfplay_timing always use 3):
  * 1 = the fused step kernel with value_head.ffn.0 inside (whole 64-slot blocks, every workgroup resident, and no other

@@ -39,11 +39,11 @@ def build(force=False, verbose=False):
     hdrs.append(os.path.join(HERE, "..", "include", "sc_engine.h"))
     common = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
     objs = []
-    for src, extra in (("mcts_kernels.hip", ["-ffp-contract=off"]), ("encode_kernels.hip", ["-ffp-contract=off"]),
+    for src, extra in (("mcts_kernels.hip", ["-ffp-contract=off"]), ("external_kernels.hip", ["-ffp-contract=off"]), ("encode_kernels.hip", ["-ffp-contract=off"]),
                        ("nn_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
                        ("score_kernels.hip", ["-ffp-contract=off"]),
                        ("batch_kernels.hip", []), ("merge_kernels.hip", []), ("perft_kernels.hip", []), ("scan_kernels.hip", []), ("san_kernels.hip", []), ("san_write_kernels.hip", []), ("fen_kernels.hip", []), ("trace_kernels.hip", []), ("trace_write_kernels.hip", []), ("positions.hip", []), ("traces.hip", []), ("trace_write.hip", []), ("perft.hip", []), ("engine.hip", []), ("encode_steps.hip", []), ("device_calls.hip", []),
-                       ("selfplay.hip", []), ("match_play.hip", []), ("selfplay_io.hip", []), ("debug_calls.hip", [])):
+                       ("selfplay.hip", []), ("match_play.hip", []), ("external_play.hip", []), ("selfplay_io.hip", []), ("debug_calls.hip", [])):
         s = os.path.join(CSRC, src)
         o = os.path.join(BUILD, src.replace(".hip", ".o"))
         if force or _newer(o, [s] + hdrs):

@@ -284,6 +284,15 @@ struct sc_selfplay {
     sc_engine* player[2] = {nullptr, nullptr};
     uint64_t salt[2] = {0, 0};
     long long* d_match_sum = nullptr;   // sc_selfplay_match_tally: the tally summed over the slots [8]
+    // an outside opponent (sc_selfplay_set_external, external_play.hip): 0, or 1 + colours -- the external_mode of the kernels.
+    // ext_waiting: the slots that waited for the opponent at the last sc_selfplay_external_wait, -1 when a push or a search has
+    // changed that since.  The device arrays of k_external_wait and k_push_moves, [n_slots] each, made by the first call that needs them
+    int external = 0;
+    int ext_waiting = -1;
+    int32_t *d_ext_list = nullptr, *d_ext_count = nullptr, *d_ext_epl = nullptr, *d_push_slots = nullptr, *d_push_status = nullptr;
+    sc::Position* d_ext_recs = nullptr;
+    int4* d_ext_info = nullptr;
+    uint16_t* d_push_moves = nullptr;
     // opening lines (sc_selfplay_set_openings): the lines' position records on the device, replayed once, and the host's copy of
     // the moves (sc_selfplay_get_opening, the trace JSON).  open_lines.n = 0: none
     sc::MatchLines open_lines{nullptr, nullptr, 0};
@@ -338,6 +347,10 @@ RowState row_state(const sc_selfplay* sp, int row, uint64_t want_id, const sc::T
 // host reads see a fully backed-up state), wait for the stream; with `latch` also look at the device's error word, and refuse a
 // poisoned handle
 int sp_quiesce(sc_selfplay* sp, bool latch);
+// n simulation steps in the handle's launch form (the body of sc_selfplay_enqueue_sims, which refuses an external handle), and the
+// first half of the launch the next step would start with, where one is pending (selfplay.hip)
+int sp_enqueue_steps(sc_selfplay* sp, int n);
+void sp_flush(sc_selfplay* sp);
 // the opening line of handle-local game `game` (sc_selfplay_set_openings): its length, *moves = its first move; 0 without lines
 int sp_opening(const sc_selfplay* sp, int game, const uint16_t** moves);
 // the base of that line (sc_selfplay_set_openings_from) as FEN text, or null for a line from the start position

@@ -39,6 +39,15 @@ void match_boundary(const sc::SpParams& p, const sc::MatchLines& lines, hipStrea
 void open_lines(int n_lines, const uint16_t* d_moves, const uint32_t* d_move_off, sc::Position* d_tab, const uint32_t* d_rec_off,
                 int32_t* d_status, const sc::Bases& bases, hipStream_t s);
 void match_tally(const int32_t* d_tally, int n_slots, long long* d_out, hipStream_t s);   // [n_slots][2][4] -> [8]
+// external_kernels.hip (compiled with -ffp-contract=off): an outside opponent.  external_mode: 0, or 1 + colours of
+// sc_selfplay_set_external.  push_moves: entry i plays d_moves[i] in slot d_slots[i] -> d_status[i] (-2 / -1 / 0 / 1).
+// external_boundary: count the games that ended, draw the next ones in slot order, start them (three launches).  external_wait: the slots that wait for the
+// opponent in slot order -> *d_count, and per entry the slot, its root record, its ep bit and {game, ply, trace row, plies recorded}
+void push_moves(const sc::SpParams& p, int n, const int32_t* d_slots, const uint16_t* d_moves, int32_t* d_status, int external_mode,
+                hipStream_t s);
+void external_boundary(const sc::SpParams& p, int external_mode, hipStream_t s);
+void external_wait(const sc::SpParams& p, int external_mode, int32_t* d_list, int32_t* d_count, sc::Position* d_recs, int32_t* d_ep_legal,
+                   int4* d_info, hipStream_t s);
 // encode_kernels.hip (compiled with -ffp-contract=off); the argument blocks are encode_types.hpp's
 void encode_positions(const sc::GameWalk& w, const sc::PlyRows& rows, int32_t* outcome, hipStream_t s);   // one position per "game"
 // training tensors (sc_encode_steps, sc_encode_steps_device, sc_selfplay_encode_traces): see encode_kernels.hip

@@ -55,6 +55,7 @@ extern "C" {
 
 int sc_selfplay_set_players(sc_selfplay* sp, sc_engine* white, sc_engine* black, uint64_t salt_white, uint64_t salt_black) {
     if (!sp) return fail("null handle");
+    if (sp->external) return fail("set_players: the handle plays an outside opponent (sc_selfplay_set_external)");
     if (sp->sim_steps_enqueued != 0) return fail("set_players must precede the first enqueue");
     if (sp->cfg.n_games != sp->cfg.n_slots) return fail("match play needs n_games == n_slots (lockstep plies, no slot recycling)");
     TRY(match_players_check(sp, white, black));
@@ -68,6 +69,7 @@ int sc_selfplay_set_match(sc_selfplay* sp, sc_engine* a, sc_engine* b, uint64_t 
         return fail("null handle");
     }
     if (sp->poisoned) return sp_refuse(sp);
+    if (sp->external) return fail("set_match: the handle plays an outside opponent (sc_selfplay_set_external)");
     if (sp->sim_steps_enqueued != 0 || sp->match) return fail("set_match must precede the first enqueue (and any other choice of players)");
     if (colours != 0 && colours != 1) return fail("set_match: colours must be 0 (a is White in every game) or 1 (a and b alternate as White)");
     TRY(match_players_check(sp, a, b));
@@ -101,6 +103,7 @@ int sc_selfplay_set_openings_from(sc_selfplay* sp, int n_lines, const sc_positio
                                   const uint32_t* move_off, int32_t* status) {
     if (!sp) return fail("null handle");
     if (sp->poisoned) return sp_refuse(sp);
+    if (sp->external) return fail("set_openings: opening lines against an outside opponent are not supported (sc_selfplay_set_external)");
     if (!sp->p.match_recycle) return fail("set_openings needs a handle set up by sc_selfplay_set_match");
     if (sp->sim_steps_enqueued != 0) return fail("set_openings must precede the first enqueue");
     if (n_lines < 1 || !move_off) return fail("set_openings: bad argument");
@@ -217,7 +220,7 @@ int sc_selfplay_match_tally(sc_selfplay* sp, int64_t out[8]) {
         return fail("null handle");
     }
     if (!out) return fail("null argument");
-    if (!sp->p.match_recycle) return fail("match_tally needs a handle set up by sc_selfplay_set_match");
+    if (!sp->p.match_recycle && !sp->external) return fail("match_tally needs a handle set up by sc_selfplay_set_match");
     TRY(sp_quiesce(sp, true));
     scl::match_tally(sp->p.match_tally(), sp->p.n_slots, sp->d_match_sum, sp->stream);
     HIPOK(hipGetLastError());

@@ -73,8 +73,9 @@ static void match_tail_params(const sc_selfplay* sp, sc::SpParams& q, int64_t t)
 // Match play with slot recycling.  The search launches never start a game (total_games = 0: a slot whose game ends goes idle);
 // games start at the ply boundaries, t % rollout == 0, between the two halves of launch t: after the expansions that end the
 // ply, k_match_boundary counts the games that ended and starts those whose White is the player of launch t, (t / rollout) & 1.
+// (An external handle, sc_selfplay_set_external, has its own boundary kernels and runs them itself: external_play.hip.)
 static void match_search_params(const sc_selfplay* sp, sc::SpParams& q) {
-    if (sp->p.match_recycle) q.total_games = 0;
+    if (sp->p.match_recycle || sp->external) q.total_games = 0;
 }
 static void match_boundary(const sc_selfplay* sp, int64_t t) {
     sc::SpParams q = sp->p;
@@ -82,7 +83,7 @@ static void match_boundary(const sc_selfplay* sp, int64_t t) {
     scl::match_boundary(q, sp->open_lines, sp->stream);
 }
 // complete the last enqueued simulation; a following enqueue would have done the same work in its first launch
-static void sp_flush(sc_selfplay* sp) {
+void sp_flush(sc_selfplay* sp) {
     if (sp->pending_final) {
         sc::SpParams q = sp->p;
         match_tail_params(sp, q, sp->sim_steps_enqueued - 1);
@@ -309,6 +310,13 @@ static int bracket_end(sc_selfplay* sp, bool sampled, int slot) {
 
 int sc_selfplay_enqueue_sims(sc_selfplay* sp, int n) {
     if (!sp || n < 0) return fail("bad argument");
+    if (sp->external) return fail("a handle with an outside opponent is stepped by sc_selfplay_external_search (sc_selfplay_set_external)");
+    return sp_enqueue_steps(sp, n);
+}
+
+}  // extern "C"
+
+int sp_enqueue_steps(sc_selfplay* sp, int n) {
     if (sp->poisoned) return sp_refuse(sp);
     HIPOK(hipSetDevice(sp->device));
     hipStream_t s = sp->stream;
@@ -379,6 +387,8 @@ int sc_selfplay_enqueue_sims(sc_selfplay* sp, int n) {
     HIPOK(hipGetLastError());
     return 0;
 }
+
+extern "C" {
 
 int sc_selfplay_enqueue_interleaved(sc_selfplay** handles, int n_handles, int n) {
     if (!handles || n_handles <= 0 || n < 0) return fail("bad argument");

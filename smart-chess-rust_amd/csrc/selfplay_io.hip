@@ -282,7 +282,9 @@ int sc_selfplay_write_pgn(sc_selfplay* sp, int n, const int32_t* games, const ch
     for (int i = 0; i < n; i++) {
         const sc_trace_info& t = info[(size_t)i];
         if (status[(size_t)i]) return fail("write_pgn: game " + std::to_string(games[i]) + ": move " + std::to_string(-status[(size_t)i] - 1) + " is not legal");
-        const bool swapped = sp->p.match_colours && (games[i] & 1);   // the White of game k is player k & 1 (sc_selfplay_set_match)
+        // the White of game k is player k & 1 (sc_selfplay_set_match); against an outside opponent `white` names the engine
+        // (sc_selfplay_set_external: colours = external - 1)
+        const bool swapped = sp->external ? sp->external == 3 || (sp->external == 2 && (games[i] & 1)) : sp->p.match_colours && (games[i] & 1);
         const char* result = !t.has_outcome ? "*" : t.winner == 1 ? "1-0" : t.winner == 0 ? "0-1" : "1/2-1/2";
         text += pgn_tag("Event", event ? event : "?");
         text += pgn_tag("Round", std::to_string(t.game_id));

@@ -100,6 +100,10 @@ ABI = {
     "sc_selfplay_set_players": (_i, [_vp, _vp, _vp, C.c_uint64, C.c_uint64]),
     "sc_selfplay_set_match": (_i, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _i]),
     "sc_selfplay_match_tally": (_i, [_vp, _vp]),
+    "sc_selfplay_set_external": (_i, [_vp, _vp, C.c_uint64, _i]),
+    "sc_selfplay_external_search": (_i, [_vp]),
+    "sc_selfplay_external_wait": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp]),
+    "sc_selfplay_push_moves": (_i, [_vp, _i, _vp, _vp, _vp]),
     "sc_selfplay_set_openings": (_i, [_vp, _i, _vp, _vp, _vp]),
     "sc_selfplay_get_opening": (_i, [_vp, _i, _vp, _i]),
     "sc_selfplay_enable_timing": (_i, [_vp, _i]),

@@ -42,6 +42,47 @@ class SelfPlay(_Handle):
         self._players = (a, b)   # keep the engines alive
         _check(self.L.sc_selfplay_set_match(self.h, a.h if a else None, b.h if b else None, salt_a, salt_b, colours))
 
+    def set_external(self, engine=None, salt=0, colours=0):
+        """an outside opponent (sc_selfplay_set_external): the handle searches the engine's plies only -- colours 0: the engine is
+        White in every game, 1: in the even games, 2: in none -- and is stepped by external_wait / push_moves / external_search
+        (scamd.external.play_external is the loop)"""
+        self._players = (engine,)   # keep the engine alive
+        _check(self.L.sc_selfplay_set_external(self.h, engine.h if engine else None, salt, colours))
+
+    def external_search(self):
+        """sc_selfplay_external_search: one searched ply of every live game, enqueued; refused while a slot waits for the opponent"""
+        _check(self.L.sc_selfplay_external_search(self.h))
+
+    def external_wait(self, moves=False):
+        """sc_selfplay_external_wait: the slots that wait for the opponent's move, in slot order -> list of dicts with slot, game
+        (handle-local), ply, fen and, with moves=True, the game's moves so far as UCI strings"""
+        G = self.cfg.n_slots
+        slots, games, plies = (np.zeros(G, np.int32) for _ in range(3))
+        fens, foff = np.zeros(G * 96, np.uint8), np.zeros(G + 1, np.uint32)
+        mcap = G * self.cfg.num_steps if moves else 0
+        mv, moff = np.zeros(max(mcap, 1), np.uint16), np.zeros(G + 1, np.uint32)
+        n = _count(self.L.sc_selfplay_external_wait(self.h, G, _p(slots), _p(games), _p(plies), _p(fens), fens.size, _p(foff),
+                                                    _p(mv) if moves else None, mcap, _p(moff) if moves else None))
+        text = fens.tobytes()
+        out = []
+        for i in range(n):
+            r = dict(slot=int(slots[i]), game=int(games[i]), ply=int(plies[i]), fen=text[foff[i]:foff[i + 1] - 1].decode())
+            if moves:
+                r["moves"] = [move_uci(m) for m in mv[moff[i]:moff[i + 1]]]
+            out.append(r)
+        return out
+
+    def push_moves(self, slots, moves):
+        """sc_selfplay_push_moves: plays moves[i] (UCI string or uint16) in slot slots[i] -> status per entry: 0 the game goes on,
+        1 the move ended it, -1 not a legal move, -2 the slot does not stand at a ply boundary with the pusher to move"""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = slots.size
+        if len(moves) != n:
+            raise ValueError("one move per slot")
+        status = np.zeros(max(n, 1), np.int32)
+        _count(self.L.sc_selfplay_push_moves(self.h, n, _p(slots) if n else None, _p(_moves(moves)) if n else None, _p(status)))
+        return [int(x) for x in status[:n]]
+
     def set_openings(self, lines):
         """sc_selfplay_set_openings: game k of a match handle starts from line opening_of_game(k, len(lines), colours); a line
         is a list of UCI strings or uint16 moves (empty: the start position), or a pair (fen, moves): the moves start from that
