@@ -299,9 +299,12 @@ __device__ __forceinline__ void conv_mma32(int xoff, const bf16_t* __restrict__ 
 struct LnStat {
     float rstd[2], nm[2];   // per pixel tile: 1/sigma and -mean/sigma
 };
-// ReLU is a single v_max_f32 (which maps NaN to 0, unlike torch.relu): a NaN anywhere in the network reaches some
-// LayerNorm's variance first, so ln_reduce records it in `bad` and the kernel poisons its outputs at the end --
-// non-finite results stay visible to the caller (reference: warning at src/backends/torch.rs:129-135).
+// ReLU is a single v_max_f32 (which maps NaN to 0, unlike torch.relu), and the fp8 image store clamps with v_med3_f32 (which
+// maps NaN to one of its bounds).  A NaN in a conv operand or a conv bias reaches some LayerNorm's variance first, so
+// ln_reduce records it in `bad` and the kernel poisons its outputs at the end -- non-finite results stay visible to the
+// caller (reference: warning at src/backends/torch.rs:129-135).  A NaN in a parameter behind the variance (a LayerNorm
+// gain or bias, an SE or FC bias) may meet the ReLU or the clamp first: the loader finds those and plants a NaN in a conv
+// bias of the same part of the network (weights.hpp: pack).
 template <int CT>
 __device__ inline void ln_reduce(const f32x16 (&acc)[CT][2], LnStat& L, int count, int wave, int lane, float* s_stat2,
                                  int& parity, int& bad SC_STAMP_ARG) {

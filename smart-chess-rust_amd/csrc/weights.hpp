@@ -421,6 +421,20 @@ inline Packed pack(const HostWeights& w, bool v32 = true) {
             p.wf[L.f_phead2 + 256 + c] = w.t[pt + 7][c];
         }
     }
+    // A non-finite per-channel parameter must stay visible in the outputs (nn_tower32.hpp: LnStat), but only a value that reaches a
+    // LayerNorm variance is seen there.  A LayerNorm bias goes straight into a ReLU (v_max_f32) or the fp8 store's clamp
+    // (v_med3_f32), an FC1 bias into a ReLU, and all of these turn a NaN into a finite number.  So the parameters are looked at
+    // here, once, and a finding is planted where the kernels do see it: as a NaN in the first conv bias of the part it belongs to
+    // -- the stem (both outputs), the value conv (the value only), the first policy conv (the priors only).  (The scale table
+    // behind f_scales holds ints.)
+    auto any_bad = [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; i++)
+            if (!isfinite(p.wf[i])) return true;
+        return false;
+    };
+    if (any_bad(L.f_stem, L.f_vhead)) p.wf[L.f_stem] = NAN;
+    if (any_bad(L.f_vhead, L.f_phead1) || any_bad(L.f_fc1b, L.f_scales)) p.wf[L.f_vhead] = NAN;
+    if (any_bad(L.f_phead1, L.f_fc1b)) p.wf[L.f_phead1] = NAN;
     return p;
 }
 

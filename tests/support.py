@@ -151,11 +151,12 @@ def untouched(a, fill=FILL):
     return (np.ascontiguousarray(a).view(np.uint8) == fill).all()
 
 
-def engine_from_state(scamd, tmp_path, sd, nb, C, prec):
-    """an Engine of nb blocks, C channels and precision prec on the weights sd, written as a blob and loaded from it"""
+def engine_from_state(scamd, tmp_path, sd, nb, C, prec, skip=()):
+    """an Engine of nb blocks, C channels and precision prec on the weights sd, written as a blob and loaded from it; skip: the
+    names that tower_ref.representable leaves out"""
     import scw
     import tower_ref as tw
-    tw.representable(sd, prec)
+    tw.representable(sd, prec, skip)
     path = str(tmp_path / "w.scw")
     scw.write_scw(path, sd, nb, C)
     eng = scamd.Engine(n_res_blocks=nb, channels=C, weights=path, precision=prec)   # debug() sizes its output by these

@@ -548,22 +548,31 @@ def test_fused_step_kernel_equals_the_two_launch_form(scamd, C, precision, n_slo
     eng.close()
 
 
-@pytest.mark.parametrize("where", ["trunk", "policy", "value"])
-def test_non_finite_parameters_stay_visible_per_head(scamd, tmp_path, where):
+NON_FINITE = {"trunk": "res_blocks.0.conv1.bias", "policy": "policy_head.model.0.bias", "value": "value_head.conv.0.bias",
+              "trunk_ln": "res_blocks.0.bn1.bias", "policy_ln": "policy_head.model.1.bias"}
+
+
+@pytest.mark.parametrize("where", list(NON_FINITE))
+@pytest.mark.parametrize("prec", ["bf16", "fp8"])
+def test_non_finite_parameters_stay_visible_per_head(scamd, tmp_path, prec, where):
     """a NaN in the network is not swallowed by a ReLU (hardware max maps NaN to 0; the reference warns on non-finite values,
-    src/backends/torch.rs:129-135): in the trunk it reaches both outputs, in one head only that head's output -- the heads
-    are separate branches (py/module.py:136-152), the other output equals the clean network's bit for bit"""
+    src/backends/torch.rs:129-135) or by the fp8 image store (its clamp, v_med3_f32, maps NaN to a bound): in the trunk it reaches
+    both outputs, in one head only that head's output -- the heads are separate branches (py/module.py:136-152), the other output
+    equals the clean network's bit for bit.  A conv bias reaches a LayerNorm variance; a LayerNorm bias (`_ln`) meets the ReLU or the
+    clamp first and is found by the loader"""
     import scw
     sd = scw.prng_state_dict(2, 128, 7)
     clean = str(tmp_path / "clean.scw")
     scw.write_scw(clean, sd, 2, 128)
-    key = {"trunk": "res_blocks.0.conv1.bias", "policy": "policy_head.model.0.bias", "value": "value_head.conv.0.bias"}[where]
+    key = NON_FINITE[where]
+    where = where.split("_")[0]
     sd[key] = sd[key].copy()
     sd[key][3] = np.nan
     bad = str(tmp_path / "bad.scw")
     scw.write_scw(bad, sd, 2, 128)
     g = np.load(os.path.join(GOLD, "nn_ref_b1_c256.npz"))
-    a, b = scamd.Engine(weights=clean), scamd.Engine(weights=bad)
+    a, b = scamd.Engine(weights=clean, precision=prec), scamd.Engine(weights=bad, precision=prec)
+    assert a.precision == b.precision == prec
     la, va = a.forward(g["boards"][:3], g["meta"][:3])
     lb, vb = b.forward(g["boards"][:3], g["meta"][:3])
     assert np.isfinite(la).all() and np.isfinite(va).all()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import heads_ref as hr
+import rounding_ref as rr
 import scw
 import tail_ref as tr
 import tower_ref as tw
@@ -162,3 +163,20 @@ def test_wrong_nets_are_caught(orc, C, mode):
     moved = lp.reshape(len(lp), 73, 64).copy()
     moved[:, :, [20, 21]] = moved[:, :, [21, 20]]
     assert share("logits, two pixels exchanged", moved.reshape(len(lp), -1), ref_p, bd_p) > 1
+
+
+# ---------------------------------------------------------------------------------- operand rounding at the decision points
+@pytest.mark.parametrize("C,prec", INST, ids=IDS)
+@pytest.mark.parametrize("site", ["4", "5"])
+def test_oracle_meets_the_rounding_forms_of_the_heads(orc, site, C, prec):
+    """rounding_ref.check_site on site 4 (policy LayerNorm -> policy conv2, the one signed conversion: both signs of every e4m3
+    decision point) and site 5 (value LayerNorm -> bf16 features, bf16 at both precisions)"""
+    n = rr.check_site(orc, site, C, prec)
+    assert n == (2 * 3 * 126 if rr.precisions(site, prec) == "fp8" else 3 * 3 * 128)
+
+
+@pytest.mark.parametrize("prec", tw.PRECS)
+@pytest.mark.parametrize("site", ["4", "5"])
+def test_wrong_rounding_rules_are_caught_in_the_heads(orc, site, prec):
+    """truncation, ties away from zero and, in e4m3, flushed subnormals, a clamp at 240 and no clamp: rounding_ref.check_wrong_rules"""
+    rr.check_wrong_rules(orc, site, 128, prec)

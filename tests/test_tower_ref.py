@@ -237,3 +237,44 @@ def test_wrong_blobs_are_caught(orc):
         W = sd["conv_block.0.weight"].copy()
         W[:, 16:32] = 0
         assert share(f"stem ({form}), k-16 group zeroed", _latents(orc, dict(sd, **{"conv_block.0.weight": W}), 0, C, prec, boards), ref, bd) > 1
+
+
+# ---------------------------------------------------------------------------------- operand rounding at the decision points
+import rounding_ref as rr  # noqa: E402
+
+
+def test_r_act_is_nearest_even_after_the_clamp():
+    """tower_ref.r_act against the brute-force rule (the nearest finite code of the table of all codes, ties to the even code, the
+    clamp first) on every decision point of the rounding tests, both signs, the values beyond 448 and the zeros; the landmarks that
+    DESIGN records; and every wrong rule of the tests differs from the right one somewhere on these points"""
+    for fmt in tw.PRECS:
+        v = np.concatenate([g for g, _ in rr.groups(fmt)])
+        v = np.concatenate([v, -v, [0.0, -0.0]]).astype(np.float32)
+        want, got = rr.convert(v, fmt), tw.r_act(v, fmt)
+        print(f"{fmt}: r_act against the brute-force rule on {len(v)} points: {(want != got).sum()} mismatches")
+        assert np.array_equal(want, got) and np.array_equal(np.signbit(want), np.signbit(got))
+        assert len(v) == 2 + 2 * (3 * 126 + len(rr.BIG) if fmt == "fp8" else 3 * 3 * 128)
+        for rule in rr.RULES[fmt]:
+            bad = rr.convert(v, fmt, rule)
+            assert ((bad != want) & ~(np.isnan(bad) & np.isnan(want))).any(), rule
+    r8 = lambda x: float(tw.r_act(np.float32(x), "fp8"))
+    assert r8(2.0 ** -10) == 0 and r8(3 * 2.0 ** -10) == 2.0 ** -8 and r8(7.5 * 2.0 ** -9) == 2.0 ** -6 and r8(2.0 ** -9) == 2.0 ** -9
+    assert all(r8(x) == 448 and r8(-x) == -448 for x in rr.BIG) and len(rr.midpoints("fp8")) == 126
+    assert np.isnan(rr.convert(np.float32(480), "fp8", "noclamp")) and rr.convert(np.float32(464), "fp8", "noclamp") == 448
+    rb = lambda x: float(tw.r_act(np.float32(x), "bf16"))
+    assert rb(1 + 2.0 ** -8) == 1 and rb(1 + 3 * 2.0 ** -8) == 1 + 2.0 ** -6 and rb(2 - 2.0 ** -8) == 2
+
+
+@pytest.mark.parametrize("C,prec", INST, ids=IDS)
+@pytest.mark.parametrize("site", ["1", "2", "3", "6p", "6h"])
+def test_oracle_meets_the_rounding_forms_of_the_trunk(orc, site, C, prec):
+    """rounding_ref.check_site on sites 1, 2, 3 and 6 (pool and hidden vector): all decision points of the site's operand format"""
+    n = rr.check_site(orc, site, C, prec)
+    assert n == (3 * 126 if rr.precisions(site, prec) == "fp8" else 3 * 3 * 128)
+
+
+@pytest.mark.parametrize("prec", tw.PRECS)
+@pytest.mark.parametrize("site", ["1", "2", "3", "6p", "6h"])
+def test_wrong_rounding_rules_are_caught_in_the_trunk(orc, site, prec):
+    """truncation, ties away from zero and, in e4m3, flushed subnormals, a clamp at 240 and no clamp: rounding_ref.check_wrong_rules"""
+    rr.check_wrong_rules(orc, site, 128, prec)
