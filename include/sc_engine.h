@@ -831,7 +831,7 @@ int sc_selfplay_debug_break_handoff(sc_selfplay*, int missing);
 int sc_debug_clear_handoff_failure(int device_id);
 /* developer aid: stamps of the last launch, out[n_slots][32]: 0..7 the search's cycle stamps (tools/dbg_cycles.py); 24..27 the
  * one-launch step's phases on the 100 MHz wall clock (kernel entry, leaf selected, network done, value-FC tile done: bench.py's
- * per-phase split); the rest written by experiment builds only (tools/dbg_tail.py, tools/dbg_expand.py) */
+ * per-phase split); the rest unused */
 int sc_selfplay_debug_cycles(sc_selfplay*, int enable, unsigned long long* out);
 
 /* utility: trace-file JSON writer on caller-provided arrays (no GPU needed) */

@@ -175,12 +175,8 @@ int sc_engine_create(const sc_net_config* cfg, const char* weights_path, int dev
     }
     if (cfg->precision != SC_PREC_BF16 && cfg->precision != SC_PREC_FP8) return fail("unknown precision");
     if (cfg->precision == SC_PREC_FP8) hw.fp8 = true;   // (an SCW2 fp8 blob sets it by itself)
-    // Both trunk widths run the channel-major 32x32x16 tower.  Experiment builds also carry the
-    // pixel-major 16x16x32 kernel; SC_TOWER_V=1 selects it there (developer switch, ignored by the production build).
-    const int tv = getenv("SC_TOWER_V") ? atoi(getenv("SC_TOWER_V")) : 0;
-    bool v32 = tv != 1;
-    if (!scl::tower_variant_available(hw.C, v32)) v32 = true;
-    scw::Packed pk = scw::pack(hw, v32);
+    // Both trunk widths run the channel-major 32x32x16 tower.
+    scw::Packed pk = scw::pack(hw);
     sc_engine* e = new sc_engine();
     e->device = device_id;
     // every failure from here on goes through sc_engine_destroy (stream, weight blobs)
@@ -262,11 +258,6 @@ static int forward_host(sc_engine* e, int n, const int8_t* boards, const int32_t
         HIPOK(hipMemcpyAsync(e->d_lidx.p, lidx_rows, (size_t)n * 224 * 2, hipMemcpyHostToDevice, s));
         HIPOK(hipMemcpyAsync(e->d_nlegal.p, nlegal, (size_t)n * 4, hipMemcpyHostToDevice, s));
     }
-#ifdef SC_EXP   // experiment builds: the same launches back to back first (steady clocks for in-kernel stamps, tools/dbg_clock.py)
-    for (int rep = getenv("SC_EXP_REPEAT") ? atoi(getenv("SC_EXP_REPEAT")) : 0; rep > 0; rep--)
-        enqueue_forward(e, n, e->d_boards.p, e->d_meta.p, 8, lidx_rows ? e->d_lidx.p : nullptr, lidx_rows ? e->d_nlegal.p : nullptr,
-                        e->d_prior.p, e->d_value.p, logp ? e->d_logp.p : nullptr, dbg ? e->d_dbg.p : nullptr, dbg_stage, s);
-#endif
     enqueue_forward(e, n, e->d_boards.p, e->d_meta.p, 8, lidx_rows ? e->d_lidx.p : nullptr, lidx_rows ? e->d_nlegal.p : nullptr,
                     e->d_prior.p, e->d_value.p, logp ? e->d_logp.p : nullptr, dbg ? e->d_dbg.p : nullptr, dbg_stage, s);
     HIPOK(hipGetLastError());

@@ -299,7 +299,7 @@ struct sc_selfplay {
     std::vector<uint16_t> open_moves;
     std::vector<uint32_t> open_move_off;   // [n + 1]
     std::vector<std::string> open_fens;    // [n] or empty: the base of each line as Board.fen() prints it, "" for the start position
-    scnn::bf16_t* d_hval = nullptr;  // value-head features of the current leaves [n_slots][64][256]
+    scnn::bf16_t* d_hval = nullptr;  // value-head features of the current leaves [n_slots][16384], in the tower's accumulator order
     float* d_vpart = nullptr;        // split-K partials of value_head.ffn.0 [ksplit][n_slots][128]
     // streaming drain (sc_selfplay_poll): per trace-ring row, the game id last reported to the host (+1; 0 = none)
     std::vector<uint64_t> reported;

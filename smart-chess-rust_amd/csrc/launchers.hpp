@@ -87,8 +87,6 @@ void trace_write_count(const sctw::Plies& p, const sctw::Steps& s, uint32_t* d_s
 void trace_write_emit(const sctw::Plies& p, const sctw::Steps& s, const sctw::Frames& f, const sctw::Out& o, hipStream_t st);
 // nn_kernels.hip
 const char* nn_init();  // sets kernel attributes; returns error text or nullptr
-size_t tower_lds_bytes(int C);
-bool tower_variant_available(int C, bool tower32);   // production builds carry one tower kernel per trunk width
 void tower(const scnn::TowerArgs& a, hipStream_t s);
 void value_fc1(const scnn::Fc1Args& a, hipStream_t s);
 // step_kernels.hip: search wave + tower in one launch (slot g = position g; a.n_pos must equal p.n_slots)

@@ -79,14 +79,8 @@ __device__ __forceinline__ bf16x8 lds_frag(int byte_off) { return *reinterpret_c
 
 // 16-byte weight fragment through a wave-uniform buffer descriptor: voffset = lane*16 (loop invariant),
 // soffset = scalar cursor, imm = column-tile offset -> zero vector ALU per load.
-#ifdef SC_EXP
-__constant__ int g_exp_wand = -1;  // experiment builds only: confine the weight stream to a small window (L1/L2-hot)
-#endif
 __device__ __forceinline__ bf16x8 wload(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
     typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-#ifdef SC_EXP
-    soff &= g_exp_wand;
-#endif
     u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
     return __builtin_bit_cast(bf16x8, v);
 }

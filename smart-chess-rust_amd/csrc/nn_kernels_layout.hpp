@@ -5,7 +5,6 @@
 namespace scnn {
 struct NetLayout {
     int n_blocks, C;
-    int tower32;  // 1: trunk/head convs packed for k_tower32 (32x32x16 A fragments), 0: the experiment-only pixel-major kernel (tools/experiments/nn_tower16.hpp, 16x16x32 B fragments)
     int fp8;      // 1: the conv weights (stem, blocks, head convs) are OCP e4m3 fragments for v_mfma_scale_f32_32x32x64_f8f6f4 with
                   // per-output-channel power-of-two scales (f_scales); the SE / value FC layers stay bf16
     // element offsets (units of 2 bytes) into the GEMM-operand blob (MFMA fragment order)

@@ -91,30 +91,6 @@ __device__ __forceinline__ uint32_t pk_fp8x4(float a, float b, float c, float d)
     return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
 }
 
-// experiment builds (-DSC_EXP, tools/build_exp.sh): per-wave cycle stamps of the block phases, dumped with dbg_stage 2000
-#ifdef SC_EXP
-struct Stamp {
-    bool on;
-    long long prev;
-    long long t[40];
-    __device__ __forceinline__ void start() { if (on) prev = clock64(); }
-    __device__ __forceinline__ void mark(int k) {
-        if (on && k >= 0) {
-            long long now = clock64();
-            t[k] += now - prev;
-            prev = now;
-        }
-    }
-};
-#define SC_STAMP_ARG , Stamp &stampv, int sk0
-#define SC_STAMP_PASS(k) , stampv, (k)
-#define SC_MARK(k) stampv.mark(k)
-#else
-#define SC_STAMP_ARG
-#define SC_STAMP_PASS(k)
-#define SC_MARK(k)
-#endif
-
 // GEMM pixel (tile pt, lane-in-tile i) -> board pixel (rank*8 + file); see the header comment
 __device__ inline int gpix2board(int pt, int i) {
     const bool inA = (i < 4) || (i >= 12 && i < 16) || (i >= 20 && i < 28);
@@ -243,20 +219,16 @@ __device__ __forceinline__ void conv_mma32(int xoff, const bf16_t* __restrict__ 
 #pragma unroll
         for (int u = 0; u < SPG; u++) {
             const int slot = u % RS;
-#ifndef SC_EXP_NOWLOAD   // experiment builds: the loop without its weight stream / without its image reads
 #pragma unroll
             for (int ct = 0; ct < CT; ct++)
                 bq[(slot + PD) % RS][ct] = (u + PD < SPG) ? wload_p<P>(rsrc, voff, ct, wcur + (u + PD) * SBB)
                                                           : wload_p<P>(rsrc, voff, ct, wnext + (u + PD - SPG) * SBB);
-#endif
-#ifndef SC_EXP_NOLDS
 #pragma unroll
             for (int pt = 0; pt < 2; pt++) {
                 const int v = u + AD;
                 xq[v % AB][pt] = (v < SPG) ? lds_frag_p<P>(pc[v / KPT][pt] + (v % KPT) * KSB)
                                            : lds_frag_p<P>(pn[(v - SPG) / KPT][pt] + ((v - SPG) % KPT) * KSB);
             }
-#endif
 #pragma unroll
             for (int ct = 0; ct < CT; ct++)
 #pragma unroll
@@ -307,7 +279,7 @@ struct LnStat {
 // bias of the same part of the network (weights.hpp: pack).
 template <int CT>
 __device__ inline void ln_reduce(const f32x16 (&acc)[CT][2], LnStat& L, int count, int wave, int lane, float* s_stat2,
-                                 int& parity, int& bad SC_STAMP_ARG) {
+                                 int& parity, int& bad) {
     float2* st = reinterpret_cast<float2*>(s_stat2) + (parity & 1) * 256;
     parity ^= 1;
     const int i = lane & 31;
@@ -334,9 +306,7 @@ __device__ inline void ln_reduce(const f32x16 (&acc)[CT][2], LnStat& L, int coun
         const auto rq = __builtin_amdgcn_permlane32_swap(__float_as_uint(q[0]), __float_as_uint(q[1]), false, false);
         st[wave * 64 + lane] = make_float2(__uint_as_float(rs[0]) + __uint_as_float(rs[1]), __uint_as_float(rq[0]) + __uint_as_float(rq[1]));
     }
-    SC_MARK(sk0);
     __syncthreads();
-    SC_MARK(sk0 + 1);
     const float inv = 1.0f / (float)count;
 #pragma unroll
     for (int pt = 0; pt < 2; pt++) {
@@ -388,9 +358,9 @@ __device__ __forceinline__ void ln_apply_relu_store(const f32x16 (&acc)[CT][2], 
 // parameters already in registers (stem, heads)
 template <int CT>
 __device__ inline void layernorm32(f32x16 (&acc)[CT][2], const ChP<CT>& G, const ChP<CT>& E, int count, bool relu, int wave,
-                                   int lane, float* s_stat2, int& parity, int& bad SC_STAMP_ARG) {
+                                   int lane, float* s_stat2, int& parity, int& bad) {
     LnStat L;
-    ln_reduce<CT>(acc, L, count, wave, lane, s_stat2, parity, bad SC_STAMP_PASS(sk0));
+    ln_reduce<CT>(acc, L, count, wave, lane, s_stat2, parity, bad);
     ln_apply<CT>(acc, L, G, E, relu);
 }
 
@@ -471,12 +441,25 @@ __device__ __forceinline__ void scale_load(int (&sa)[CT], const NetDev& net, int
 
 // dynamic LDS of a tower workgroup: the haloed image (later the 4672 policy logits), the policy head's image, LayerNorm /
 // SE scratch and the staged per-block parameters.  The e4m3 images are half the size: 49 KB instead of 73 KB at C = 128,
-// which is what lets two fused step workgroups (10 KB of search scratch each) share a CU.
-constexpr int tower32_lds_bytes(int C, bool fp8 = false) {
-    const int psb = C * (fp8 ? 1 : 2) + 16, hpsb = HEAD * (fp8 ? 1 : 2) + 16;
-    const int xa = 100 * psb > 4864 * 4 ? 100 * psb : 4864 * 4;
-    return xa + 64 * hpsb + 4096 + 3072 + 1024 + 64 + 15 * C * 2;
-}
+// which is what lets two fused step workgroups (10 KB of search scratch each) share a CU.  Byte offsets inside g_smem, and
+// the total that a launch asks for.
+template <class P, int C>
+struct TowerLds {
+    static constexpr int IMG_BYTES = (100 * pix_stride<P>(C) > 4864 * 4) ? 100 * pix_stride<P>(C) : 4864 * 4;   // image; later the 4672 policy logits
+    static constexpr int HIMG_BYTES = 64 * pix_stride<P>(HEAD);
+    static constexpr int HIMG = IMG_BYTES;          // the policy head's image
+    static constexpr int STAT = HIMG + HIMG_BYTES;  // LayerNorm statistics: 2 x [4][64] float2
+    static constexpr int VEC = STAT + 4096;         // SE vectors (packed bf16); from here to the end: the heads' staged parameters
+    static constexpr int SCL = VEC + 3072;          // [C] SE scales
+    static constexpr int RED = SCL + 1024;          // softmax partials [0..7], the hand-off flag [8]
+    static constexpr int PAR = RED + 64;            // staged per-block parameters, 7.5*C floats
+    static constexpr int TOTAL = PAR + 15 * C * 2;
+    static_assert(4864 * 4 <= IMG_BYTES, "policy logits (and the softmax pass that reads 19 x 256 of them) must fit in the image area");
+    static_assert(IMG_BYTES % 16 == 0 && HIMG_BYTES % 16 == 0, "LDS regions must stay 16-byte aligned");
+    static_assert(6 * HEAD * 4 + 3 * POL_PAD * 4 <= TOTAL - VEC, "head parameters must fit in the staging area");
+};
+static_assert(TowerLds<PrecBF16, 128>::TOTAL == 73088 && TowerLds<PrecBF16, 256>::TOTAL == 102528, "bf16 tower LDS");
+static_assert(TowerLds<PrecFP8, 128>::TOTAL == 48960 && TowerLds<PrecFP8, 256>::TOTAL == 60544, "fp8 tower LDS");
 
 // tower_body: the network for position `pos`, run by the 256 threads of one workgroup.  planes_lds: the position's input
 // planes int8[64][112] in LDS, or nullptr: read them from A.boards.
@@ -511,34 +494,18 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
     constexpr int HRS = P::FP8 ? C / 64 : 8, HAB = P::FP8 ? 2 : SC_T32_AB;         // 256-wide head convs (K = C)
     constexpr int H2RS = P::FP8 ? HEAD / 64 : 16, H2AB = P::FP8 ? 2 : SC_T32_AB;   // the 73-wide one (K = 256)
     constexpr int NTW = C / 64;        // 16-column tiles per wave of the SE layers (16x16x32 vector products)
-    constexpr int XA_BYTES = (100 * PSB > 4864 * 4) ? 100 * PSB : 4864 * 4;   // image; later the 4672 policy logits
-    constexpr int RS_BYTES = 64 * HPSB;   // the policy head's image
+    typedef TowerLds<P, C> Lds;
     unsigned char* smem = g_smem;
-    float* s_stat = reinterpret_cast<float*>(smem + XA_BYTES + RS_BYTES);   // 2 x [4][64] float2
-    float* s_vec = s_stat + 1024;                                           // SE vectors (packed bf16)
-    float* s_scl = s_vec + 768;                                             // [C] SE scales
-    float* s_red = s_scl + 256;                                             // [8]
-    constexpr int PAR_OFF = XA_BYTES + RS_BYTES + 4096 + 3072 + 1024 + 64;  // staged per-block parameters, 7.5*C floats
-    bf16_t* s_xb = reinterpret_cast<bf16_t*>(s_vec);
-    float* s_z = reinterpret_cast<float*>(smem);                            // policy logits [4672], aliases Xa (after the trunk)
-    static_assert(4864 * 4 <= XA_BYTES, "policy logits (and the softmax pass that reads 19 x 256 of them) must fit in the image area");
-    static_assert(XA_BYTES % 16 == 0 && RS_BYTES % 16 == 0, "LDS regions must stay 16-byte aligned");
+    float* s_stat = reinterpret_cast<float*>(smem + Lds::STAT);
+    float* s_scl = reinterpret_cast<float*>(smem + Lds::SCL);
+    float* s_red = reinterpret_cast<float*>(smem + Lds::RED);
+    bf16_t* s_xb = reinterpret_cast<bf16_t*>(smem + Lds::VEC);
+    float* s_z = reinterpret_cast<float*>(smem);                            // policy logits [4672], aliases the image (after the trunk)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i32 = lane & 31, h = lane >> 5;
     const NetDev& net = A.net;
-#ifdef SC_EXP
-    // stage 2001 (tools/dbg_clock.py): shader-clock and wall-clock stamps around the whole tower of this workgroup
-    const bool clk_on = A.dbg && A.dbg_stage == 2001 && tid == 0;
-    const long long clk_t0 = clk_on ? clock64() : 0;
-    const unsigned long long clk_r0 = clk_on ? __builtin_amdgcn_s_memrealtime() : 0;
-    Stamp stampv;
-    stampv.on = A.dbg && A.dbg_stage == 2000 && lane == 0;
-    stampv.prev = 0;
-    for (int k = 0; k < 40; k++) stampv.t[k] = 0;
-    stampv.start();
-#endif
     const int bp[2] = {gpix2board(0, i32), gpix2board(1, i32)};            // this lane's two board pixels
     const int pixbase[2] = {hidx(bp[0]) * PSB, hidx(bp[1]) * PSB};         // their rows in the haloed image (bytes)
     const int px[2] = {pixbase[0] + h * P::FB, pixbase[1] + h * P::FB};    // + this lane's k half
@@ -549,7 +516,6 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
     scale_load<P, CT>(sa, net, 0, wave, lane);
     scale_load<P, CT>(san, net, net.n_blocks > 0 ? 1 : 1 + 2 * net.n_blocks, wave, lane);
     ChP<CT> Bn;            // bias of the NEXT conv (requested one epilogue early)
-    constexpr int PAR0 = XA_BYTES + RS_BYTES + 4096 + 3072 + 1024 + 64;   // = PAR_OFF below
     // ---- Every global read of the prologue is issued first: the input planes (7 dwords per thread) and, cooperatively,
     // the stem's bias / gamma / beta plus block 0's first bias (4*C floats, one 16-byte load per thread, staged in
     // LDS like the per-block parameters).  Their trip from HBM / L2 overlaps the zero fill instead of following it.
@@ -566,10 +532,7 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
     else if (tid < C) spv = *reinterpret_cast<const f32x4*>(net.wf + net.f_blocks + (tid - 3 * C / 4) * 4);
     // the stem's first weights too -- except for the fused kernel's search wave: its first loads are the search's (a wave's
     // loads return in order: the control block would queue behind 12 KB of weights); it fills its ring after the search
-#ifndef SC_FUSED_RING_LATE
-#define SC_FUSED_RING_LATE 1   // experiment builds: 0 = the search wave also requests its weights first
-#endif
-    if (!FUSED || wave != 0 || !SC_FUSED_RING_LATE) ring_fill<P, CT, TILES, RS>(ring, net.wb + net.o_stem, wave, lane);
+    if (!FUSED || wave != 0) ring_fill<P, CT, TILES, RS>(ring, net.wb + net.o_stem, wave, lane);
     __builtin_amdgcn_sched_barrier(0);
     // ---- zero the image (halo stays zero for the whole kernel), then write the 112 input planes
     if constexpr (FUSED) {
@@ -577,7 +540,7 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         if (wave <= 1) {   // wave 0: the search; wave 1: its helper (plane encoding)
             const bool go = pre(wave);
             if (wave == 0 && lane == 0) s_go = go ? 1 : 0;
-            if (wave == 0 && SC_FUSED_RING_LATE) ring_fill<P, CT, TILES, RS>(ring, net.wb + net.o_stem, wave, lane);
+            if (wave == 0) ring_fill<P, CT, TILES, RS>(ring, net.wb + net.o_stem, wave, lane);
         } else {
             uint4* z = reinterpret_cast<uint4*>(smem);
             for (int k = tid - 128; k < 100 * PSB / 16; k += 128) z[k] = make_uint4(0, 0, 0, 0);
@@ -609,7 +572,7 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
                 dst[2 * k + 1] = pk_bf16(f32x2{v[2], v[3]});
             }
         }
-        if (tid < C) *reinterpret_cast<f32x4*>(g_smem + PAR0 + tid * 16) = spv;
+        if (tid < C) *reinterpret_cast<f32x4*>(g_smem + Lds::PAR + tid * 16) = spv;
     }
     __syncthreads();
 
@@ -638,26 +601,21 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         }
     };
 
-    SC_MARK(38);   // prologue: input planes, zero fill, parameter staging
     // ---- conv_block (py/module.py:120-126): conv3x3 112->C (K padded to 128/tap), LN, ReLU
     {
-        ch_load_lds<CT>(Bn, PAR0, wave, h);
+        ch_load_lds<CT>(Bn, Lds::PAR, wave, h);
         acc_init<CT>(acc, Bn);
         const bf16_t* w0 = net.wb + net.o_stem;
-        SC_MARK(33);
         conv_mma32<P, 128, 9, CT, TILES, PSB, RS, TPI, true, AB>(0, w0, wave, lane, px, acc, ring, (int)((net.wb + net.o_blocks) - w0) * 2, sa);
         ChP<CT> G, E;
-        ch_load_lds<CT>(G, PAR0 + C * 4, wave, h);
-        ch_load_lds<CT>(E, PAR0 + 2 * C * 4, wave, h);
-        ch_load_lds<CT>(Bn, PAR0 + 3 * C * 4, wave, h);   // read before the barriers that let block 0 restage the area
-        SC_MARK(34);
-        layernorm32<CT>(acc, G, E, C, true, wave, lane, s_stat, ln_parity, bad SC_STAMP_PASS(35));
-        SC_MARK(37);
+        ch_load_lds<CT>(G, Lds::PAR + C * 4, wave, h);
+        ch_load_lds<CT>(E, Lds::PAR + 2 * C * 4, wave, h);
+        ch_load_lds<CT>(Bn, Lds::PAR + 3 * C * 4, wave, h);   // read before the barriers that let block 0 restage the area
+        layernorm32<CT>(acc, G, E, C, true, wave, lane, s_stat, ln_parity, bad);
     }
     store_res();
     store_image32<P, CT>(acc, pixbase, wave, h);  // every wave passed the LN barrier: the input image is dead
     __syncthreads();
-    SC_MARK(14);
     dump(0);
     const int head_conv0 = 1 + 2 * net.n_blocks;   // conv index of the value conv
 
@@ -674,12 +632,8 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         // 1 KiB wave-load through the texture path each, on the critical path of every epilogue.
         constexpr int PAR_V4 = 15 * C / 8;                // float4 count of the window
         constexpr int NPV = (PAR_V4 + 255) / 256;
-        static_assert(PAR0 == PAR_OFF, "prologue staging area");
-        constexpr int P_G1 = PAR_OFF, P_E1 = PAR_OFF + 4 * C, P_B2 = PAR_OFF + 8 * C, P_G2 = PAR_OFF + 12 * C, P_E2 = PAR_OFF + 16 * C;
-        constexpr int P_SB1 = PAR_OFF + 20 * C, P_SB2 = PAR_OFF + 22 * C, P_BN = PAR_OFF + 26 * C;
-#ifdef SC_EXP
-        stampv.start();
-#endif
+        constexpr int P_G1 = Lds::PAR, P_E1 = Lds::PAR + 4 * C, P_B2 = Lds::PAR + 8 * C, P_G2 = Lds::PAR + 12 * C, P_E2 = Lds::PAR + 16 * C;
+        constexpr int P_SB1 = Lds::PAR + 20 * C, P_SB2 = Lds::PAR + 22 * C, P_BN = Lds::PAR + 26 * C;
         f32x4 pv[NPV];
 #pragma unroll
         for (int k = 0; k < NPV; k++)
@@ -691,22 +645,19 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         for (int ct = 0; ct < CT; ct++) sa[ct] = san[ct];
         scale_load<P, CT>(san, net, 2 + 2 * b, wave, lane);
         conv_mma32<P, C, 9, CT, TILES, PSB, RS, TPI, true, AB>(0, wb, wave, lane, px, acc, ring, 9 * C * C * EB, sa);
-        SC_MARK(0);
 #pragma unroll
         for (int k = 0; k < NPV; k++)
-            if (tid + 256 * k < PAR_V4) *reinterpret_cast<f32x4*>(g_smem + PAR_OFF + (tid + 256 * k) * 16) = pv[k];
+            if (tid + 256 * k < PAR_V4) *reinterpret_cast<f32x4*>(g_smem + Lds::PAR + (tid + 256 * k) * 16) = pv[k];
         {
             LnStat L;
-            ln_reduce<CT>(acc, L, C, wave, lane, s_stat, ln_parity, bad SC_STAMP_PASS(1));   // its barrier publishes the parameters
+            ln_reduce<CT>(acc, L, C, wave, lane, s_stat, ln_parity, bad);   // its barrier publishes the parameters
             ChP<CT> G, E;
             ch_load_lds<CT>(G, P_G1, wave, h);
             ch_load_lds<CT>(E, P_E1, wave, h);
-            SC_MARK(3);
             ln_apply_relu_store<P, CT>(acc, L, G, E, pixbase, wave, h);
         }
         ch_load_lds<CT>(Bn, P_B2, wave, h);
         __syncthreads();
-        SC_MARK(4);
         // conv2 -> LN
         acc_init<CT>(acc, Bn);
         {
@@ -717,7 +668,6 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
             scale_load<P, CT>(san, net, b + 1 < net.n_blocks ? 3 + 2 * b : head_conv0, wave, lane);   // (heads reload theirs: two tiles per wave)
             conv_mma32<P, C, 9, CT, TILES, PSB, RS, TPI, true, AB>(0, wb + (size_t)9 * C * C * EB / 2, wave, lane, px, acc, ring, nxt, sa);
         }
-        SC_MARK(5);
         // squeeze-excitation weights are requested now: their L2 round trip hides under the LayerNorm (issuing them
         // before conv2 instead measured the same: the conv loop is bound by the same vector-memory path).  The
         // columns of both layers are split over the 4 waves.
@@ -728,13 +678,12 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         __builtin_amdgcn_sched_barrier(0);
         {
             LnStat L;
-            ln_reduce<CT>(acc, L, C, wave, lane, s_stat, ln_parity, bad SC_STAMP_PASS(6));
+            ln_reduce<CT>(acc, L, C, wave, lane, s_stat, ln_parity, bad);
             ChP<CT> G, E;
             ch_load_lds<CT>(G, P_G2, wave, h);
             ch_load_lds<CT>(E, P_E2, wave, h);
             ln_apply<CT>(acc, L, G, E, false);
         }
-        SC_MARK(8);
         // global average pool over the 64 pixels: in-lane over the two tiles, then a halving butterfly over the
         // 32 lanes of a half-wave (lane j of a half ends up with register index j, or j>>1 when there are 16)
         {
@@ -759,9 +708,7 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         for (int k = 0; k < NTW1; k++) sb1[k] = *reinterpret_cast<const float*>(g_smem + P_SB1 + (wave * (16 * NTW1) + (lane & 15) * NTW1 + k) * 4);
 #pragma unroll
         for (int k = 0; k < NTW; k++) sb2[k] = *reinterpret_cast<const float*>(g_smem + P_SB2 + (chan0<NTW>(wave, lane) + k) * 4);
-        SC_MARK(9);
         __syncthreads();
-        SC_MARK(10);
         bf16_t* s_hid = s_xb + 256;                              // hidden vector
         {
             // fc1: C -> C/2, ReLU
@@ -795,7 +742,6 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
                     s_scl[c0 + k] = __builtin_amdgcn_rcpf(1.0f + __expf(-(sc[k][0] + sb2[k])));
             }
         }
-        SC_MARK(11);
 #pragma unroll
         for (int ct = 0; ct < CT; ct++)
 #pragma unroll
@@ -816,22 +762,15 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         store_res();
         store_image32<P, CT>(acc, pixbase, wave, h);  // conv2 finished reading Xa before the SE barriers
         ch_load_lds<CT>(Bn, P_BN, wave, h);        // next block's conv1 bias: read before the barrier that frees the staging area
-        SC_MARK(12);
         __syncthreads();
-        SC_MARK(13);
         dump(b + 1);
     }
     dump(1000);
-#ifdef SC_EXP
-    stampv.start();
-#endif
 
     const int gpb[2] = {i32 * HPSB, (32 + i32) * HPSB};   // rows of the plain (non-haloed) policy image
     // The three heads' per-channel parameters (1920 contiguous floats) are fetched cooperatively under the value
-    // conv and staged in LDS (the SE scratch is dead now), like the per-block parameters of the trunk.
-    constexpr int HPAR = XA_BYTES + RS_BYTES + 4096;            // byte offset of the staging area (s_vec ...)
-    constexpr int HP_V = HPAR, HP_P1 = HPAR + 3 * HEAD * 4, HP_P2 = HPAR + 6 * HEAD * 4;
-    static_assert(6 * HEAD * 4 + 3 * POL_PAD * 4 <= 3072 + 1024 + 64 + 15 * C * 2, "head parameters must fit in the staging area");
+    // conv and staged in LDS from Lds::VEC on (the SE scratch is dead now), like the per-block parameters of the trunk.
+    constexpr int HP_V = Lds::VEC, HP_P1 = Lds::VEC + 3 * HEAD * 4, HP_P2 = Lds::VEC + 6 * HEAD * 4;
     f32x4 hpv[2];
 #pragma unroll
     for (int k = 0; k < 2; k++)
@@ -856,10 +795,9 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
                                                            (int)((net.wb + net.o_pconv1) - (net.wb + net.o_vconv)) * 2, sh);
         scale_load<P, 2>(sh, net, head_conv0 + 1, wave, lane);
         scale_load<P, 1>(sh2, net, head_conv0 + 2, wave, lane);
-        SC_MARK(20);
 #pragma unroll
         for (int k = 0; k < 2; k++)
-            if (tid + 256 * k < 480) *reinterpret_cast<f32x4*>(g_smem + HPAR + (tid + 256 * k) * 16) = hpv[k];
+            if (tid + 256 * k < 480) *reinterpret_cast<f32x4*>(g_smem + Lds::VEC + (tid + 256 * k) * 16) = hpv[k];
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
         ChP<2> Bv, G, E;
@@ -872,11 +810,10 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
                 for (int r = 0; r < 16; r++) hv[ct][pt][r] += Bv.v[ct][r >> 2][r & 3];
         LnStat L;
         int badv = bad;   // the trunk's NaNs and this head's own: the policy head below does not inherit the latter
-        ln_reduce<2>(hv, L, HEAD, wave, lane, s_stat, ln_parity, badv SC_STAMP_PASS(21));
+        ln_reduce<2>(hv, L, HEAD, wave, lane, s_stat, ln_parity, badv);
         ch_load_lds<2>(G, HP_V + HEAD * 4, wave, h);
         ch_load_lds<2>(E, HP_V + 2 * HEAD * 4, wave, h);
         ln_apply<2>(hv, L, G, E, true);
-        SC_MARK(23);
         // Feature order in HBM = accumulator order ([wave][ct][pt][lane][16 registers], weights.hpp packs the rows of
         // value_head.ffn.0 to match): a lane's 16 values are 32 contiguous bytes and a wave's two stores fill whole
         // cache lines.  Writing [pixel][channel] rows from this layout (8 bytes per lane, 512 B apart) cost 4.6 k cycles.
@@ -902,7 +839,6 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
                 }
             }
     }
-    SC_MARK(16);
     // ---- policy head (py/module.py:70-76): conv1x1 C->256, LN, conv1x1 256->73, LN (no ReLU between)
     {
         ChP<2> Bv, G, E;
@@ -910,13 +846,12 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         f32x16 hp[2][2];
         acc_init<2>(hp, Bv);
         conv_mma32<P, C, 1, 2, 8, PSB, HRS, 1, true, HAB>(0, net.wb + net.o_pconv1, wave, lane, px, hp, hr, 0, sh);
-        SC_MARK(24);
         // value_head.ffn.0 inside this launch: this wave's feature stores (a conv ago) have left the CU ...
         if (HAND && A.fc1_arrive) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ring_fill<P, 1, 4, H2RS>(hr2, net.wb + net.o_pconv2, wave, lane);   // hidden under the LayerNorm
         __builtin_amdgcn_sched_barrier(0);
         LnStat L;
-        ln_reduce<2>(hp, L, HEAD, wave, lane, s_stat, ln_parity, bad SC_STAMP_PASS(25));
+        ln_reduce<2>(hp, L, HEAD, wave, lane, s_stat, ln_parity, bad);
         // ... and, behind the LayerNorm's barrier, so have the other waves': one lane signals for the whole workgroup
         // (MI355X_MICROARCH.md, hand-off forms, row 1)
         if (HAND && A.fc1_arrive && tid == 0)
@@ -924,33 +859,28 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         ch_load_lds<2>(G, HP_P1 + HEAD * 4, wave, h);
         ch_load_lds<2>(E, HP_P1 + 2 * HEAD * 4, wave, h);
         ln_apply<2>(hp, L, G, E, false);
-        const int xb[2] = {XA_BYTES + gpb[0], XA_BYTES + gpb[1]};
+        const int xb[2] = {Lds::HIMG + gpb[0], Lds::HIMG + gpb[1]};
         store_image32<P, 2>(hp, xb, wave, h);   // Xh: the head image behind Xa
-        SC_MARK(27);
     }
     __syncthreads();
-    SC_MARK(17);
     {
         ChP<1> Bv, G, E;
         ch_load_lds<1>(Bv, HP_P2, wave, h);
         f32x16 z[1][2];
         acc_init<1>(z, Bv);
         const int pxh[2] = {gpb[0] + h * P::FB, gpb[1] + h * P::FB};
-        conv_mma32<P, HEAD, 1, 1, 4, HPSB, H2RS, 1, true, H2AB>(XA_BYTES, net.wb + net.o_pconv2, wave, lane, pxh, z, hr2, 0, sh2);
-        SC_MARK(28);
+        conv_mma32<P, HEAD, 1, 1, 4, HPSB, H2RS, 1, true, H2AB>(Lds::HIMG, net.wb + net.o_pconv2, wave, lane, pxh, z, hr2, 0, sh2);
         // first reading of the block's arrival counter (judged at the barrier in front of the softmax, a round trip later)
         uint32_t first = 0;
         if (HAND && A.fc1_arrive && tid == 0 && !A.fc1_acquire)
             first = __hip_atomic_load(A.fc1_arrive + (pos >> 6) * 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // padded channels (>=73) have zero weights, bias, gamma, beta: they add 0 to both LN sums
         LnStat L;
-        ln_reduce<1>(z, L, 73, wave, lane, s_stat, ln_parity, bad SC_STAMP_PASS(29));
+        ln_reduce<1>(z, L, 73, wave, lane, s_stat, ln_parity, bad);
         ch_load_lds<1>(G, HP_P2 + POL_PAD * 4, wave, h);
         ch_load_lds<1>(E, HP_P2 + 2 * POL_PAD * 4, wave, h);
         ln_apply<1>(z, L, G, E, false);
-        SC_MARK(31);
         __syncthreads();  // everyone is done with Xa/Xh: the logits may overwrite the image area
-        SC_MARK(32);
 #pragma unroll
         for (int pt = 0; pt < 2; pt++)
 #pragma unroll
@@ -962,7 +892,6 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         if (HAND && A.fc1_arrive && tid == 0) reinterpret_cast<int*>(s_red)[8] = !A.fc1_acquire && (int32_t)(first - A.fc1_target) >= 0;
     }
     __syncthreads();
-    SC_MARK(18);
     if constexpr (HAND) {
         if (A.fc1_arrive) {   // the tail's first round trips fly under the softmax
             fc1_wload(fh->w, net, pos & 63, 64, wave, lane);
@@ -1001,15 +930,13 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
     // +1.45 % in the fp8 instantiations, but the softmax / gather code then compiled differently in k_step and in k_tower32 and the fp8
     // priors of `predict` and of the search differed by a few ulps -- tests/test_gpu_netloop.py caught it.  Code that produces
     // numbers must be the same in both kernels.)
-    constexpr bool LEAN = false;
-    if (!LEAN && A.logp) {
+    if (A.logp) {
         float* lp = A.logp + (size_t)pos * 4672;
 #pragma unroll
         for (int j = 0; j < 19; j++)
             if (tid + 256 * j < 4672) lp[tid + 256 * j] = zv[j] - lse;
     }
-    SC_MARK(19);
-    if (LEAN || A.prior) {
+    if (A.prior) {
         const int n = A.n_legal[pos];
         const uint16_t* li = A.legal_idx + (size_t)pos * 224;
         float e = 0.f;
@@ -1022,16 +949,6 @@ __device__ __forceinline__ bool tower_body(const TowerArgs& A, const int pos, co
         s = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]) + 1e-5f;  // post_process_distr (chess.rs:891)
         if (tid < n) A.prior[(size_t)pos * 224 + tid] = e / s;
     }
-#ifdef SC_EXP
-    SC_MARK(15);
-    if (stampv.on)
-        for (int k = 0; k < 40; k++) A.dbg[(size_t)pos * 64 * C + wave * 40 + k] = (float)stampv.t[k];
-    if (clk_on) {
-        A.dbg[(size_t)pos * 64 * C + 0] = (float)(clock64() - clk_t0);                               // s_memtime ticks
-        A.dbg[(size_t)pos * 64 * C + 1] = (float)(__builtin_amdgcn_s_memrealtime() - clk_r0);       // 100 MHz ticks
-        A.dbg[(size_t)pos * 64 * C + 2] = (float)(clk_r0 & 0xffffff);                               // start time (low bits): who ran when
-    }
-#endif
     return true;
 }
 

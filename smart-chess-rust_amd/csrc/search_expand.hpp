@@ -233,9 +233,7 @@ __device__ __forceinline__ void dev_expand(SpParams& p, int g, int lane, Positio
     ValueTail vt;
     if (p.vf_fused) value_tail_issue(p, g, lane, vt);   // used when the leaf turns out to be a network evaluation
     __builtin_amdgcn_sched_barrier(0);
-    SC_XSTAMP(16);
     const GameCtl cs = uniform(craw);
-    SC_XSTAMP(17);
     const int pth = lane < p.max_depth ? pth_raw : 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -278,7 +276,6 @@ __device__ __forceinline__ void dev_expand(SpParams& p, int g, int lane, Positio
     }
     if (kind == LK_EVAL) {
         value = p.vf_fused ? value_tail_finish(p, vt) : p.value[g];
-        SC_XSTAMP(18);
         int n = cs.n_legal;
         if (n_nodes + n > p.node_cap || n_exp + 1 >= p.tpos_cap) {
             err = ERR_POOL_OVERFLOW;
@@ -303,7 +300,6 @@ __device__ __forceinline__ void dev_expand(SpParams& p, int g, int lane, Positio
     } else if (kind == LK_TERM_NEW) {
         if (lane == 0) H[leaf] = NodeHdr{value == 0.0f ? -2 : value > 0.0f ? -3 : -4, 0, 0};
     }
-    SC_XSTAMP(19);
     // backward (mcts.rs:90-98): every node of the path, root included
     if (inpath) {
         N[pth] = n0 + 1;
@@ -330,7 +326,6 @@ __device__ __forceinline__ void dev_expand(SpParams& p, int g, int lane, Positio
         p.slot_cnt[(size_t)g * 2] = sc_sims + 1ULL;
         if (kind == LK_EVAL) p.slot_cnt[(size_t)g * 2 + 1] = sc_evals + 1ULL;
     }
-    SC_XSTAMP(20);
     cs_out.n_nodes = n_nodes;
     cs_out.n_exp = n_exp;
     cs_out.sim = sim;

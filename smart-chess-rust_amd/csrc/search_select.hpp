@@ -142,20 +142,10 @@ __device__ inline float gamma03(uint64_t st) {
 // ------------------------------------------------------------------ select (src/mcts.rs:132-227)
 constexpr int DEPTH_LDS = 1024;  // path entries tracked in LDS (a deeper path sets ERR_DEPTH_OVERFLOW)
 
-#ifdef SC_EXP   // experiment builds: stamps inside the expansion (slots 16..), tools/dbg_expand.py
-#define SC_XSTAMP(k) SC_STAMP(k)
-#else
-#define SC_XSTAMP(k)
-#endif
 // Cycle stamps of the search's phases (tools/dbg_cycles.py).  Compiled into the kernel that runs every step they cost 0.7 % of
 // the headline even while switched off (same-box A/B, tools/ab_r02.py): SC_ST is a template argument of the functions that carry
 // them -- true in k_mcts and in the stamped instantiation of the fused step kernel, which the engine launches only while stamps are
-// switched on; experiment builds stamp everywhere.
-#ifdef SC_EXP
-#define SC_ST_DEFAULT true
-#else
-#define SC_ST_DEFAULT false
-#endif
+// switched on.
 #define SC_STAMP(k)                                                                       \
     do {                                                                                  \
         if constexpr (SC_ST) {                                                            \

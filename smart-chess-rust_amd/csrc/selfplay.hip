@@ -218,15 +218,9 @@ static int create_attach(sc_selfplay* sp) {
     // (the narrow fp8 tower's workgroup is small enough -- 59 KB of LDS, 249 VGPRs -- for two fused workgroups per CU; the
     // runtime's occupancy answer is used, capped at 2: a third would leave CUs empty at 512 games.  The bf16 one is not.)
     sp->fused = net && !cfg.own_stream && cfg.n_slots <= e->n_cu * e->step_blocks_per_cu;
-#ifdef SC_EXP
-    if (getenv("SC_FUSED")) sp->fused = getenv("SC_FUSED")[0] != '0';   // experiment builds: A/B
-#endif
     // One launch per step: value_head.ffn.0's 64-position tiles are computed by the step kernel's own workgroups (workgroup g:
     // tile (g / 64, K chunk g % 64), step_kernels.hip) -- when the slots fill whole blocks and the split is the kernel's 64.
     sp->fc1_in_step = sp->fused && cfg.n_slots % 64 == 0 && e->ksplit == 64;
-#ifdef SC_FC1_IN_STEP_OFF   // A/B builds
-    sp->fc1_in_step = false;
-#endif
     if (sp->fc1_in_step) sp->fc1_in_step = fc1_stream_acquire(sp->device, sp->stream);
     return 0;
 }

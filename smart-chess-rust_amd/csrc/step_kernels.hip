@@ -35,12 +35,6 @@ __device__ __forceinline__ void fc1_tail(const scnn::TowerArgs& A, const sc::SpP
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int mb = g >> 6, ks = g & 63;
     uint32_t* ctr = A.fc1_arrive + mb * 32;
-#ifdef SC_EXP   // experiment builds: stamps of the tail's phases (100 MHz), read by tools/dbg_tail.py
-#define TSTAMP(k) do { if (p.dbg_cycles && tid == 0) p.dbg_cycles[(size_t)g * 32 + 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define TSTAMP(k)
-#endif
-    TSTAMP(0);
     // a workgroup whose leaf needed no network has nothing to publish (its row keeps the last evaluation's features; the
     // partials computed from it are never read), but the others count on its arrival
     // (a workgroup that ran the network requested the tile's weights and a first reading of the counter under its softmax)
@@ -51,10 +45,6 @@ __device__ __forceinline__ void fc1_tail(const scnn::TowerArgs& A, const sc::SpP
     }
     const scnn::Fc1W& w = fh.w;
     const bool have_a = ran && fh.have_a;   // (uniform over the workgroup)
-#ifdef SC_EXP
-    if (p.dbg_cycles && tid == 0) p.dbg_cycles[(size_t)g * 32 + 14] = have_a;
-    if (have_a) { TSTAMP(1); TSTAMP(2); }
-#endif
     if (tid == 0 && !have_a) {
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();   // 100 MHz
         uint32_t seen = ran ? fh.early : __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -71,23 +61,15 @@ __device__ __forceinline__ void fc1_tail(const scnn::TowerArgs& A, const sc::SpP
             if (waited > 100000ull && (__hip_atomic_load(&p.cnt->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & sc::ERR_HANDOFF_TIMEOUT)) break;
             seen = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        TSTAMP(1);
         if (A.fc1_acquire) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        TSTAMP(2);
     }
     __syncthreads();   // the poll has matched (and the tower's last LDS reads are done: the tile is staged over its image)
     scnn::bf16_t* s_a = reinterpret_cast<scnn::bf16_t*>(scnn::g_smem);
     if (!have_a) scnn::fc1_load_a(fh.a, A.hval, mb, ks, tid);
     scnn::fc1_put_a(s_a, fh.a, tid);
     __syncthreads();
-    TSTAMP(3);
     scnn::fc1_mma_store(w, s_a, A.vpart, A.n_pos, mb, ks, 64, wave, lane);
-    TSTAMP(4);
-#ifdef SC_EXP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    TSTAMP(5);
-#endif
 }
 
 // STAMPS: the instantiation with the launch's phase stamps (bench.py's per-phase split; the headline's kernel only).  Compiled into
@@ -106,14 +88,8 @@ __global__ __launch_bounds__(256, 1) void k_step(scnn::TowerArgs A, sc::SpParams
     __shared__ sc::HelperBox s_box;
     const int g = blockIdx.x;
     const int lane = threadIdx.x & 63;
-#ifdef SC_EXP
-    const long long t_entry = clock64();   // experiment builds: the kernel's first instruction (tools/dbg_expand.py)
-#endif
     // the two argument blocks: 700 bytes = 11 cache lines (kernarg_prefetch, nn_kernels.hpp)
     scnn::kernarg_prefetch<sizeof(scnn::TowerArgs) + sizeof(sc::SpParams) + sizeof(int)>();
-#ifdef SC_EXP
-    if (p.dbg_cycles && threadIdx.x == 0) p.dbg_cycles[(size_t)g * 32 + 21] = t_entry;
-#endif
     // phase stamps of the launch (sc_selfplay_debug_cycles; bench.py's per-phase split): 100 MHz wall clock at kernel entry
     // [24], when the search wave has its leaf [25], at the end of the network [26] and of the value-FC tile [27]
 #define PHASE_STAMP(k, cond) do { if constexpr (STAMPS) { if (p.dbg_cycles && (cond)) p.dbg_cycles[(size_t)g * 32 + (k)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
@@ -127,7 +103,7 @@ __global__ __launch_bounds__(256, 1) void k_step(scnn::TowerArgs A, sc::SpParams
             sc::dev_encode_helper(p, g, lane, &s_box, s_stage, &s_pos, s_ps, s_hist);
             return true;
         }
-        constexpr bool SC_ST = STAMPS || SC_ST_DEFAULT;
+        constexpr bool SC_ST = STAMPS;
         SC_STAMP(0);
         sc::GameCtl cs_pre{};
         bool cs_pre_valid = false;
@@ -151,49 +127,36 @@ __global__ __launch_bounds__(256, 1) void k_step(scnn::TowerArgs A, sc::SpParams
 }  // namespace scstep
 
 namespace scl {
-#define K_STEP(P, C, RS, TPI, AB) scstep::k_step<scnn::P, C, RS, TPI, AB>
-#define K_STEP_STAMPED scstep::k_step<scnn::PrecBF16, 128, SC_T32_RS, SC_T32_TPI, SC_T32_AB, true>
+template <class T, bool STAMPS = false>
+constexpr auto step_kernel(T) { return &scstep::k_step<typename T::P, T::C, T::RS, T::TPI, T::AB, STAMPS>; }
+
 const char* step_init() {
-    const void* kn[4] = {reinterpret_cast<const void*>(&K_STEP(PrecBF16, 128, SC_T32_RS, SC_T32_TPI, SC_T32_AB)),
-                         reinterpret_cast<const void*>(&K_STEP(PrecBF16, 256, SC_T32W_RS, SC_T32W_TPI, SC_T32W_AB)),
-                         reinterpret_cast<const void*>(&K_STEP(PrecFP8, 128, SC_T8_RS, SC_T8_TPI, SC_T8_AB)),
-                         reinterpret_cast<const void*>(&K_STEP(PrecFP8, 256, SC_T8W_RS, SC_T8W_TPI, SC_T8W_AB))};
-    for (int i = 0; i < 4; i++) {
-        hipError_t e = hipFuncSetAttribute(kn[i], hipFuncAttributeMaxDynamicSharedMemorySize, scnn::tower32_lds_bytes(i & 1 ? 256 : 128, i >= 2 && i < 4));
-        if (e != hipSuccess) return hipGetErrorString(e);
-    }
-    {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&K_STEP_STAMPED), hipFuncAttributeMaxDynamicSharedMemorySize, scnn::tower32_lds_bytes(128));
-        if (e != hipSuccess) return hipGetErrorString(e);
-    }
-    return nullptr;
+    for (bool fp8 : {false, true})
+        for (int C : {128, 256}) {
+            const hipError_t e = scnn::with_tower_cfg(fp8, C, [](auto cfg) {
+                return hipFuncSetAttribute(reinterpret_cast<const void*>(step_kernel(cfg)), hipFuncAttributeMaxDynamicSharedMemorySize, cfg.LDS_BYTES);
+            });
+            if (e != hipSuccess) return hipGetErrorString(e);
+        }
+    // ... and the stamped instantiation of the headline's kernel
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(step_kernel<scnn::TowerBf16N, true>({})), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             scnn::TowerBf16N::LDS_BYTES);
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
 }
 // fused workgroups that can be resident on one CU (registers + LDS, asked of the runtime): the engine uses the fused form
 // only when every game's workgroup is resident at once
 int step_blocks_per_cu(const scnn::NetLayout& net) {
     int n = 0;
-    hipError_t e;
-    if (net.fp8 && net.C == 128)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_STEP(PrecFP8, 128, SC_T8_RS, SC_T8_TPI, SC_T8_AB), 256, scnn::tower32_lds_bytes(128, true));
-    else if (net.fp8)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_STEP(PrecFP8, 256, SC_T8W_RS, SC_T8W_TPI, SC_T8W_AB), 256, scnn::tower32_lds_bytes(256, true));
-    else if (net.C == 128)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_STEP(PrecBF16, 128, SC_T32_RS, SC_T32_TPI, SC_T32_AB), 256, scnn::tower32_lds_bytes(128));
-    else
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_STEP(PrecBF16, 256, SC_T32W_RS, SC_T32W_TPI, SC_T32W_AB), 256, scnn::tower32_lds_bytes(256));
+    const hipError_t e = scnn::with_tower_cfg(net.fp8, net.C, [&](auto cfg) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, step_kernel(cfg), 256, cfg.LDS_BYTES);
+    });
     return e == hipSuccess && n > 0 ? n : 1;
 }
 void step(const scnn::TowerArgs& a, const sc::SpParams& p, int do_expand, hipStream_t s) {
     const dim3 grid(p.n_slots), block(256);
-    if (a.net.fp8 && a.net.C == 128)
-        hipLaunchKernelGGL((K_STEP(PrecFP8, 128, SC_T8_RS, SC_T8_TPI, SC_T8_AB)), grid, block, scnn::tower32_lds_bytes(128, true), s, a, p, do_expand);
-    else if (a.net.fp8)
-        hipLaunchKernelGGL((K_STEP(PrecFP8, 256, SC_T8W_RS, SC_T8W_TPI, SC_T8W_AB)), grid, block, scnn::tower32_lds_bytes(256, true), s, a, p, do_expand);
-    else if (a.net.C == 128 && p.dbg_cycles)   // stamps switched on (sc_selfplay_debug_cycles): the stamped instantiation
-        hipLaunchKernelGGL((K_STEP_STAMPED), grid, block, scnn::tower32_lds_bytes(128), s, a, p, do_expand);
-    else if (a.net.C == 128)
-        hipLaunchKernelGGL((K_STEP(PrecBF16, 128, SC_T32_RS, SC_T32_TPI, SC_T32_AB)), grid, block, scnn::tower32_lds_bytes(128), s, a, p, do_expand);
+    if (!a.net.fp8 && a.net.C == 128 && p.dbg_cycles)   // stamps switched on (sc_selfplay_debug_cycles): the stamped instantiation
+        hipLaunchKernelGGL((step_kernel<scnn::TowerBf16N, true>({})), grid, block, scnn::TowerBf16N::LDS_BYTES, s, a, p, do_expand);
     else
-        hipLaunchKernelGGL((K_STEP(PrecBF16, 256, SC_T32W_RS, SC_T32W_TPI, SC_T32W_AB)), grid, block, scnn::tower32_lds_bytes(256), s, a, p, do_expand);
+        scnn::with_tower_cfg(a.net.fp8, a.net.C, [&](auto cfg) { hipLaunchKernelGGL(step_kernel(cfg), grid, block, cfg.LDS_BYTES, s, a, p, do_expand); });
 }
 }  // namespace scl

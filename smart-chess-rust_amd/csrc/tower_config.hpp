@@ -1,5 +1,8 @@
-// tower_config.hpp -- ring / tap-group geometries of the tower instantiations (shared by nn_kernels.hip and step_kernels.hip)
+// tower_config.hpp -- the tower's instantiations: ring / tap-group geometries and the table that maps a network to its one
+// (shared by nn_kernels.hip and step_kernels.hip)
 #pragma once
+#include "nn_tower32.hpp"   // the precision policies, TowerLds, SC_T32_AB
+
 #ifndef SC_T32_RS
 #define SC_T32_RS 12   // narrow trunk: 12-slot weight ring, all 9 taps of a conv unrolled (no tap-group loop: measured
 #define SC_T32_TPI 9   // -4 % cycles, -1 % wall over groups of 3; experiment builds may override)
@@ -25,3 +28,30 @@
 #define SC_T8W_TPI 3
 #define SC_T8W_AB 3
 #endif
+
+namespace scnn {
+
+// One tower instantiation: precision policy, trunk width, weight ring slots, taps per loop iteration, image-fragment buffers,
+// and the dynamic LDS of its workgroup.
+template <class P_, int C_, int RS_, int TPI_, int AB_>
+struct TowerCfg {
+    typedef P_ P;
+    static constexpr int C = C_, RS = RS_, TPI = TPI_, AB = AB_;
+    static constexpr int LDS_BYTES = TowerLds<P_, C_>::TOTAL;
+};
+typedef TowerCfg<PrecBF16, 128, SC_T32_RS, SC_T32_TPI, SC_T32_AB> TowerBf16N;
+typedef TowerCfg<PrecBF16, 256, SC_T32W_RS, SC_T32W_TPI, SC_T32W_AB> TowerBf16W;
+typedef TowerCfg<PrecFP8, 128, SC_T8_RS, SC_T8_TPI, SC_T8_AB> TowerFp8N;
+typedef TowerCfg<PrecFP8, 256, SC_T8W_RS, SC_T8W_TPI, SC_T8W_AB> TowerFp8W;
+
+// f(the instantiation of a network with this precision and trunk width); the engine admits C = 128 and 256 only.  (The kernels
+// stand in a unit's code object in the order of these cases.)
+template <class F>
+auto with_tower_cfg(bool fp8, int C, F&& f) {
+    if (!fp8 && C == 128) return f(TowerBf16N());
+    if (!fp8) return f(TowerBf16W());
+    if (C == 128) return f(TowerFp8N());
+    return f(TowerFp8W());
+}
+
+}  // namespace scnn

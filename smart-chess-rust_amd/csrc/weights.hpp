@@ -272,15 +272,14 @@ struct Packed {
     scnn::NetLayout lay;
 };
 
-inline Packed pack(const HostWeights& w, bool v32 = true) {
+inline Packed pack(const HostWeights& w) {
     const int C = w.C, nb = w.n_blocks, H = 256;
-    const bool fp8 = w.fp8 && v32;
+    const bool fp8 = w.fp8;
     const int EB = fp8 ? 1 : 2;   // bytes per conv weight; offsets stay in units of 2 bytes
     Packed p;
     scnn::NetLayout& L = p.lay;
     L.n_blocks = nb;
     L.C = C;
-    L.tower32 = v32 ? 1 : 0;
     L.fp8 = fp8 ? 1 : 0;
     size_t ob = 0, of = 0;
     L.o_stem = ob; ob += (size_t)9 * 128 * C * EB / 2;
@@ -331,8 +330,7 @@ inline Packed pack(const HostWeights& w, bool v32 = true) {
             return ci < 112 ? W[((size_t)n * 112 + ci) * 9 + tap] : 0.f;
         };
         if (fp8) pack8(0, 0, L.o_stem, 9 * 128, C, C / 32, get);
-        else if (v32) pack_A32(p.wb.data() + L.o_stem, 9 * 128, C / 32, get);
-        else pack_B(p.wb.data() + L.o_stem, 9 * 128, NT, NTW, get);
+        else pack_A32(p.wb.data() + L.o_stem, 9 * 128, C / 32, get);
         for (int c = 0; c < C; c++) {
             p.wf[L.f_stem + c] = w.t[1][c];
             p.wf[L.f_stem + C + c] = w.t[2][c];
@@ -350,8 +348,7 @@ inline Packed pack(const HostWeights& w, bool v32 = true) {
                 return W[((size_t)n * C + ci) * 9 + tap];
             };
             if (fp8) pack8(t0 + 4 * cv, 1 + 2 * b + cv, L.o_blocks + (size_t)b * L.blk_stride_b + (size_t)cv * 9 * C * C / 2, 9 * C, C, C / 32, get);
-            else if (v32) pack_A32(wb + (size_t)cv * 9 * C * C, 9 * C, C / 32, get);
-            else pack_B(wb + (size_t)cv * 9 * C * C, 9 * C, NT, NTW, get);
+            else pack_A32(wb + (size_t)cv * 9 * C * C, 9 * C, C / 32, get);
             for (int c = 0; c < C; c++) {
                 wf[(3 * cv + 0) * C + c] = w.t[t0 + 4 * cv + 1][c];
                 wf[(3 * cv + 1) * C + c] = w.t[t0 + 4 * cv + 2][c];
@@ -374,8 +371,7 @@ inline Packed pack(const HostWeights& w, bool v32 = true) {
         const float* W = w.t[vt].data();  // [256][C]
         auto getv = [&](int k, int n) { return W[(size_t)n * C + k]; };
         if (fp8) pack8(vt, 1 + 2 * nb, L.o_vconv, C, H, 8, getv);
-        else if (v32) pack_A32(p.wb.data() + L.o_vconv, C, 8, getv);
-        else pack_B(p.wb.data() + L.o_vconv, C, 16, 4, getv);
+        else pack_A32(p.wb.data() + L.o_vconv, C, 8, getv);
         for (int c = 0; c < H; c++) {
             p.wf[L.f_vhead + c] = w.t[vt + 1][c];
             p.wf[L.f_vhead + H + c] = w.t[vt + 2][c];
@@ -383,13 +379,10 @@ inline Packed pack(const HostWeights& w, bool v32 = true) {
         }
         const float* F1 = w.t[vt + 4].data();  // [128][16391], column = ch*64 + px
         pack_B(p.wb.data() + L.o_fc1, 64 * H, 8, 2, [&](int k, int n) {
-            int px = k / H, ch = k % H;   // pixel-major kernel (nn_tower16.hpp): features as [pixel][channel]
-            if (v32) {
-                // k_tower32 writes them in accumulator order: [wave][ct][pt][lane][register] (nn_tower32.hpp, value head)
-                const int r = k & 15, lane = (k >> 4) & 63, pt = (k >> 10) & 1, ct = (k >> 11) & 1, wave = (k >> 12) & 3;
-                ch = wave * 64 + ct * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
-                px = gpix2board32(pt, lane & 31);
-            }
+            // the tower writes the features in accumulator order: [wave][ct][pt][lane][register] (nn_tower32.hpp, value head)
+            const int r = k & 15, lane = (k >> 4) & 63, pt = (k >> 10) & 1, ct = (k >> 11) & 1, wave = (k >> 12) & 3;
+            const int ch = wave * 64 + ct * 32 + 8 * (r >> 2) + 4 * (lane >> 5) + (r & 3);
+            const int px = gpix2board32(pt, lane & 31);
             return F1[(size_t)n * (64 * H + 7) + (size_t)ch * 64 + px];
         });
         for (int j = 0; j < 128; j++) {
@@ -403,8 +396,7 @@ inline Packed pack(const HostWeights& w, bool v32 = true) {
         const float* W = w.t[pt].data();
         auto getp = [&](int k, int n) { return W[(size_t)n * C + k]; };
         if (fp8) pack8(pt, 2 + 2 * nb, L.o_pconv1, C, H, 8, getp);
-        else if (v32) pack_A32(p.wb.data() + L.o_pconv1, C, 8, getp);
-        else pack_B(p.wb.data() + L.o_pconv1, C, 16, 4, getp);
+        else pack_A32(p.wb.data() + L.o_pconv1, C, 8, getp);
         for (int c = 0; c < H; c++) {
             p.wf[L.f_phead1 + c] = w.t[pt + 1][c];
             p.wf[L.f_phead1 + H + c] = w.t[pt + 2][c];
@@ -413,8 +405,7 @@ inline Packed pack(const HostWeights& w, bool v32 = true) {
         const float* W2 = w.t[pt + 4].data();  // [73][256]
         auto getp2 = [&](int k, int n) { return n < 73 ? W2[(size_t)n * H + k] : 0.f; };
         if (fp8) pack8(pt + 4, 3 + 2 * nb, L.o_pconv2, H, 73, 4, getp2);
-        else if (v32) pack_A32(p.wb.data() + L.o_pconv2, H, 4, getp2);
-        else pack_B(p.wb.data() + L.o_pconv2, H, 8, 2, getp2);
+        else pack_A32(p.wb.data() + L.o_pconv2, H, 4, getp2);
         for (int c = 0; c < 73; c++) {
             p.wf[L.f_phead2 + c] = w.t[pt + 5][c];
             p.wf[L.f_phead2 + 128 + c] = w.t[pt + 6][c];

@@ -1,6 +1,8 @@
 """developer tool: same-box A/B of the headline configuration between two builds of the library (default: this tree's lib/ against a
 build of the round-2 tree in lib_r02/), with a minimal loader that binds only what it needs (the ABI grew since round 2).
-    python tools/ab_r02.py [libA] [libB]"""
+    python tools/ab_r02.py [libA] [libB]
+A variant of this tree to compare against (production flags, every unit):
+    python smart-chess-rust_amd/build.py --out smart-chess-rust_amd/lib_ab --define SC_T8_AB=3"""
 import ctypes as C, os, sys, time, subprocess, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "--child":

@@ -1,5 +1,4 @@
-"""developer tool: 512 bf16 games per GPU as two interleaved groups (two HIP streams), in the launch form the handles pick
-(experiment builds: SC_FUSED=1 forces the fused step kernel + value FC launch for own-stream handles too)"""
+"""developer tool: 512 bf16 games per GPU as two interleaved groups (two HIP streams), in the launch form the handles pick"""
 import sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "smart-chess-rust_amd"))
