@@ -807,6 +807,39 @@ int sc_search_from(sc_engine*, const sc_positions* bases, int i, const uint16_t*
                    float* root_q);
 int sc_selfplay_get_fen(sc_selfplay*, int slot, char* buf, int cap);
 
+/* ------------------------------------------------------------------ the search report */
+/* What a search found, read from the trees where they lie: one kernel launch for every requested slot, one copy to the host.
+ * Entry i reports slot slots[i] (slots == NULL: slot i), n entries.  All pointers are host pointers; any output may be NULL.
+ * The call completes the handle's pending work first (the expansion and backup of the last enqueued simulation, as
+ * sc_selfplay_get_tree does): the report sees a fully backed-up tree.  It works on every kind of handle -- self-play, match,
+ * external, an interactive one-slot handle -- and changes nothing the search reads: a handle that is reported on between
+ * enqueues plays bit-identical games.  A slot listed twice or out of range returns -1 and writes nothing; n == 0 is fine; a
+ * poisoned handle refuses with SC_ERR_HANDOFF.
+ * Lines: the root's child i has rank #{ j : N[j] > N[i], or N[j] == N[i] and j < i } -- visits descending, then the generator's
+ * order, so rank 0 is the FIRST most-visited child (mcts::step, src/mcts.rs:309-311; children without a visit are ranked like
+ * the rest).  Line r of an entry, 0 <= r < n_lines = min(multipv, children of the root), is the child of rank r and its
+ * principal variation: from a node the walk goes to the most-visited child, ties to the lowest index, while the node is
+ * expanded, has children and that child has a visit; it never takes more than 1024 moves (the search's depth limit).
+ * Per line, row i * multipv + r: line_child the child's index among the root's children, line_n / line_w / line_prior its visit
+ * count, value sum (White's point of view, as the search adds it up) and cached prior, line_len the FULL length of the walk,
+ * line_end what the last node is -- 0 open (unexpanded, or no visited child), 1 / 2 / 3 a terminal whose game is drawn / won by
+ * White / won by Black, 4 cut at the depth limit -- and pv[(i * multipv + r) * pv_cap ..] the first min(line_len, pv_cap) moves.
+ * Nothing else is written: rows from n_lines on, and the moves behind min(line_len, pv_cap), keep what the arrays held.
+ * Per entry, info[i]: status / ply / sim / n_nodes of the slot, n_root_children, root_children_n the sum of the root children's
+ * visits, root_n / root_w the root's own, turn the side to move at the root (1 White, 0 Black; -1 where the slot holds no game)
+ * and n_lines -- 0 where the slot is idle or finished, the root is unexpanded (sim == 0), terminal or without children.
+ * sc_selfplay_report_last_timing: measurement aid (tools/report_rate.py) -- HIP-event time of the kernel and host time of the
+ * whole call, of the calling thread's last sc_selfplay_report. */
+struct sc_report_slot {
+    int32_t status, ply, sim, n_nodes, n_root_children, root_children_n, root_n, turn, n_lines, pad;
+    float root_w;
+};
+typedef struct sc_report_slot sc_report_slot;
+int sc_selfplay_report(sc_selfplay*, int n, const int32_t* slots /* NULL: slots 0..n-1 */, int multipv /* 1..224 */, int pv_cap /* 0..1024 */,
+                       sc_report_slot* info /*[n]*/, int32_t* line_child, int32_t* line_n, float* line_w, float* line_prior,
+                       int32_t* line_len, int32_t* line_end /* each [n][multipv] */, uint16_t* pv /*[n][multipv][pv_cap]*/);
+int sc_selfplay_report_last_timing(float* kernel_ms, float* total_ms);
+
 /* test aid: find_max (src/mcts.rs:78-88, Iterator::max_by: the LAST maximum wins) as the descent computes it, on n <= 256
  * caller-provided finite values: out[0] = the one-round form used for nodes with <= 64 children (-2 if n > 64),
  * out[1] = the four-round (value, index) form used for wider nodes. */

@@ -83,6 +83,21 @@ pub struct ScTraceInfo {
 }
 
 #[repr(C)]
+pub struct ScReportSlot {
+    pub status: i32,
+    pub ply: i32,
+    pub sim: i32,
+    pub n_nodes: i32,
+    pub n_root_children: i32,
+    pub root_children_n: i32,
+    pub root_n: i32,
+    pub turn: i32,
+    pub n_lines: i32,
+    pub pad: i32,
+    pub root_w: f32,
+}
+
+#[repr(C)]
 pub struct ScEngine {
     _p: [u8; 0],
 }
@@ -148,6 +163,11 @@ extern "C" {
                       child_q: *mut f32, child_prior: *mut f32, root_q: *mut f32) -> c_int;
     fn sc_selfplay_set_openings_from(sp: *mut ScSelfplay, n_lines: c_int, bases: *const ScPositions, base_idx: *const i32,
                                      moves: *const u16, move_off: *const u32, status: *mut i32) -> c_int;
+    // the search report (chess_play_inspect and a UCI engine's info lines): ranked lines and principal variations of many slots
+    fn sc_selfplay_report(sp: *mut ScSelfplay, n: c_int, slots: *const i32, multipv: c_int, pv_cap: c_int, info: *mut ScReportSlot,
+                          line_child: *mut i32, line_n: *mut i32, line_w: *mut f32, line_prior: *mut f32, line_len: *mut i32,
+                          line_end: *mut i32, pv: *mut u16) -> c_int;
+    fn sc_selfplay_report_last_timing(kernel_ms: *mut f32, total_ms: *mut f32) -> c_int;
 }
 
 fn last_error() -> String {

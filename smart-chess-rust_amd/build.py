@@ -40,10 +40,10 @@ def _run(cmd):
 HIP_UNITS = [
     ("mcts_kernels.hip", ["-ffp-contract=off"]), ("external_kernels.hip", ["-ffp-contract=off"]), ("encode_kernels.hip", ["-ffp-contract=off"]),
     ("nn_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
-    ("score_kernels.hip", ["-ffp-contract=off"]),
+    ("score_kernels.hip", ["-ffp-contract=off"]), ("report_kernels.hip", ["-ffp-contract=off"]),
     ("batch_kernels.hip", []), ("merge_kernels.hip", []), ("perft_kernels.hip", []), ("scan_kernels.hip", []), ("san_kernels.hip", []),
     ("san_write_kernels.hip", []), ("fen_kernels.hip", []), ("trace_kernels.hip", []), ("trace_write_kernels.hip", []),
-    ("positions.hip", []), ("traces.hip", []), ("trace_write.hip", []), ("perft.hip", []), ("engine.hip", []), ("encode_steps.hip", []),
+    ("positions.hip", []), ("traces.hip", []), ("trace_write.hip", []), ("perft.hip", []), ("report.hip", []), ("engine.hip", []), ("encode_steps.hip", []),
     ("device_calls.hip", []), ("selfplay.hip", []), ("match_play.hip", []), ("external_play.hip", []), ("selfplay_io.hip", []),
     ("debug_calls.hip", []),
 ]

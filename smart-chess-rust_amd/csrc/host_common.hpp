@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host units of libsc_engine.so share (engine.hip, encode_steps.hip, device_calls.hip, selfplay.hip,
-// match_play.hip, selfplay_io.hip, debug_calls.hip): error state, the handles' structs, the described source of an encode
+// match_play.hip, selfplay_io.hip, report.hip, debug_calls.hip): error state, the handles' structs, the described source of an encode
 // (EncodeSrc) and one helper for each piece of plumbing.  Host only: no kernel unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -258,7 +258,7 @@ struct TraceWriter {
     void release();   // (the owner's device is current)
 };
 
-// ------------------------------------------------------- self-play (selfplay.hip, match_play.hip, selfplay_io.hip, debug_calls.hip)
+// ------------------------------------------------------- self-play (selfplay.hip, match_play.hip, selfplay_io.hip, report.hip, debug_calls.hip)
 struct sc_selfplay {
     sc_engine* engine = nullptr;
     int device = 0;
@@ -310,6 +310,10 @@ struct sc_selfplay {
     bool enc_pending = false;
     // sc_selfplay_traces_json / sc_selfplay_write_traces_json: the handle's trace writer, created by the first such call
     TraceWriter* writer = nullptr;
+    // sc_selfplay_report: the packed buffer the report kernel writes (report_types.hpp scrp::Packed), grown on demand, and the
+    // event pair around the kernel, created by the first such call
+    DevBuf<char> d_report;
+    hipEvent_t report_ev[2] = {nullptr, nullptr};
     // search wave + tower in one launch (step_kernels.hip).  Chosen at creation: only with at most one game per compute
     // unit and a single group -- with more games than CUs the separate search launch runs all of them at once while the
     // fused workgroups (83 KB of LDS: one per CU) would take turns, and with several interleaved groups one group's search

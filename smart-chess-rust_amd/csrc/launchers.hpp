@@ -18,6 +18,7 @@ void exclusive_scan_u32(uint32_t n, const uint32_t* d_in, uint32_t* d_tile_sum, 
 #include "merge_types.hpp"
 #include "encode_types.hpp"
 #include "perft_types.hpp"
+#include "report_types.hpp"
 #include "trace_types.hpp"
 #include "trace_write_types.hpp"
 
@@ -113,4 +114,7 @@ void perft_div_ones(int n, const int32_t* d_n_div, unsigned long long* d_div_nod
 void perft_count(const scpf::Level& lv, uint32_t* d_cnt, hipStream_t s);
 void perft_expand(const scpf::ExpandArgs& a, hipStream_t s);
 void perft_leaf(const scpf::Level& lv, const scpf::LeafOut& lo, const scpf::Totals& t, hipStream_t s);
+// report_kernels.hip (compiled with -ffp-contract=off): the search report (sc_selfplay_report); the argument block is
+// report_types.hpp's.  One wavefront per (entry, line): a.n * a.multipv workgroups of 64 threads; nothing for a.n == 0
+void report(const scrp::ReportArgs& a, hipStream_t s);
 }  // namespace scl

@@ -269,6 +269,9 @@ void sc_selfplay_destroy(sc_selfplay* sp) {
         (void)hipEventDestroy(sp->enc_ev);
     }
     delete sp->writer;
+    sp->d_report.release();
+    for (hipEvent_t ev : sp->report_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (sp->own_stream && sp->stream) (void)hipStreamDestroy(sp->stream);
     delete sp;
 }

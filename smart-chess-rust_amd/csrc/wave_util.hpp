@@ -46,6 +46,14 @@ __device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// ... and the butterfly maximum: an arg-max over packed keys (value << 32 | tie-break), the result in every lane
+__device__ inline unsigned long long wave_max_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_xor(v, o, 64);
+        v = x > v ? x : v;
+    }
+    return v;
+}
 
 // the exclusive prefix sum of v over the lanes of the wave (off the hot path, every lane active); *total = the wave's sum
 __device__ inline uint32_t wave_excl_scan_u32(uint32_t v, uint32_t* total) {

@@ -113,6 +113,8 @@ ABI = {
     "sc_selfplay_write_trace_json": (_i, [_vp, _i, C.c_char_p]),
     "sc_selfplay_write_pgn": (_i, [_vp, _i, _vp, C.c_char_p, _i, C.c_char_p, C.c_char_p, C.c_char_p]),
     "sc_selfplay_get_tree": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_selfplay_report": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sc_selfplay_report_last_timing": (_i, [C.POINTER(_f), C.POINTER(_f)]),
     "sc_selfplay_get_slot": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sc_selfplay_set_noise": (_i, [_vp, _i, _vp, _i]),
     "sc_selfplay_get_noise": (_i, [_vp, _i, _vp, _i]),

@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import EngineError, _check, _count, _Handle, _p, lib, move_uci
+from .binding import MAX_MOVES, EngineError, _check, _count, _Handle, _p, lib
 
 # sc_positions_status: what a negative code says (include/sc_engine.h)
 STATUS_TEXT = {0: "playable", 1: "the game is over here", -1: "not exactly one king per side", -2: "a pawn on rank 1 or 8",
@@ -86,12 +86,17 @@ def bases_of(fens, n, device):
     return Positions(texts, device), idx, True
 
 
-def analyse(engine, fens, rollout, cpuct=2.5, best=None, evaluator="net", seed=0, device=0, trees=False):
+def analyse(engine, fens, rollout, cpuct=2.5, best=None, evaluator="net", seed=0, device=0, trees=False, multipv=1, pv_cap=64):
     """A suite of positions in `rollout` launches: one position per slot of one handle (SelfPlay.set_position from a base for
-    each), one enqueue of `rollout` simulations, the root children of every slot.
-    -> dict(results=[dict(fen, move, children=[(uci, N, Q, prior), ...]) per position], solved=count or None).  move: the first
-    most-visited child.  best: per position a UCI move or a collection of them (an EPD `bm`, once resolved through scamd.san);
-    solved counts the positions whose move is among them.  trees: every result also carries the slot's whole tree (SelfPlay.tree)."""
+    each), one enqueue of `rollout` simulations, then ONE report of every slot (SelfPlay.report): the root children, the move
+    and the lines come from it.
+    -> dict(results=[dict(fen, move, children=[(uci, N, Q, prior), ...], pv, score, lines) per position], solved=count or None).
+    move: the first most-visited child; pv / score: its principal variation (UCI strings, pv_cap >= 1 of them at most) and
+    ("cp", c) or ("mate", m); lines: the first `multipv` lines by visits as scamd.report.Report.lines gives them.  best: per
+    position a UCI move or a collection of them (an EPD `bm`, once resolved through scamd.san); solved counts the positions whose
+    move is among them.  trees: every result also carries the slot's whole tree (SelfPlay.tree)."""
+    if not 1 <= multipv <= MAX_MOVES or not 1 <= pv_cap <= 1024:
+        raise ValueError("analyse: 1 <= multipv <= 224 and 1 <= pv_cap <= 1024")
     from .selfplay import SelfPlay
     pos = fens if isinstance(fens, Positions) else Positions(fens, engine.device if engine is not None else device)
     owned = pos is not fens
@@ -112,14 +117,15 @@ def analyse(engine, fens, rollout, cpuct=2.5, best=None, evaluator="net", seed=0
             sp.enqueue(rollout)
             sp.sync()
             sp.check_flags("analyse")   # (a blocked position searched deeper than 1024 levels: no numbers from such a tree)
+            rep = sp.report(multipv=MAX_MOVES, pv_cap=pv_cap)   # every root child of every slot is a line: one launch, one copy
             for i in range(n):
-                t = sp.tree(i)
-                fc, nc = (int(t["first_child"][0]), int(t["n_child"][0])) if t["n"].size and t["first_child"][0] >= 0 else (0, 0)
-                ch = [(move_uci(t["move"][fc + k]), int(t["n"][fc + k]), float(t["q"][fc + k]), float(t["prior"][fc + k])) for k in range(nc)]
-                mv = ch[int(np.argmax([c[1] for c in ch]))][0] if ch else None
-                r = dict(fen=pos.fen(i), move=mv, children=ch)
+                lines = rep.lines(i)
+                ch = [(ln["move"], ln["n"], ln["w"], ln["prior"]) for ln in sorted(lines, key=lambda ln: ln["child"])]
+                r = dict(fen=pos.fen(i), move=lines[0]["move"] if lines else None, children=ch)
                 if trees:
-                    r["tree"] = t
+                    r["tree"] = sp.tree(i)
+                r.update(pv=lines[0]["pv"] if lines else [], score=lines[0]["score"] if lines else None, lines=lines[:multipv])
+                mv = r["move"]
                 results.append(r)
                 if best is not None:
                     want = {best[i]} if isinstance(best[i], str) else set(best[i])

@@ -282,6 +282,14 @@ class SelfPlay(_Handle):
                                            _p(out["move"]), _p(out["first_child"]), _p(out["n_child"])))
         return out
 
+    def report(self, slots=None, multipv=1, pv_cap=64):
+        """sc_selfplay_report: what the searches of `slots` (None: all) found, read on the GPU in one launch and one copy -> a
+        scamd.report.Report: a dict of numpy arrays (status, ply, sim, n_nodes, n_root_children, root_children_n, root_n, root_w,
+        turn, n_lines per entry; line_child, line_n, line_w, line_prior, line_len, line_end [n][multipv]; pv [n][multipv][pv_cap])
+        whose lines(i) gives entry i's lines by visits as dicts with move, pv, n, q, prior, len, end and score"""
+        from .report import report
+        return report(self, slots, multipv, pv_cap)
+
     def debug_cycles(self, enable=True, read=False):
         """sc_selfplay_debug_cycles: switch the stamps on / read those of the last launch -> uint64[n_slots, 32] (or None)"""
         out = np.zeros((self.cfg.n_slots, 32), np.uint64) if read else None
