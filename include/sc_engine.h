@@ -711,6 +711,22 @@ int sc_selfplay_external_search(sc_selfplay*);
 int sc_selfplay_external_wait(sc_selfplay*, int cap, int32_t* slots, int32_t* games, int32_t* plies, char* fens, uint64_t fens_cap,
                               uint32_t* fen_off, uint16_t* moves, uint32_t moves_cap, uint32_t* move_off);
 int sc_selfplay_push_moves(sc_selfplay*, int n, const int32_t* slots, const uint16_t* moves, int32_t* status);
+/* Plays moves[i] in slot slots[i] and KEEPS the searched subtree below that move: the chosen root child becomes the root, the rest
+ * of the node pool and of the tree's position records is compacted away on the device (one workgroup per listed slot), and the
+ * next sc_selfplay_enqueue_sims goes on from it.  The tree afterwards is, array for array, what a fresh search from the position
+ * after the move holds after as many simulations as the child had visits (no root noise); an unvisited child, or a root that was
+ * never searched, gives a one-node root.  The call has sc_selfplay_push_moves's shape: it completes pending work first, a slot out
+ * of range or listed twice returns -1, n = 0 is fine, it returns the number of refused entries and a refused entry changes
+ * nothing but its status.  status[i] (may be NULL): 0 the game goes on, 1 the move ended it (outcome under the handle's
+ * outcome_gate, num_steps: the rules of a searched ply), -1 the move is not playable there -- not among the root's children, or,
+ * root not searched, not among the legal moves --, -2 the slot is not active, has a simulation in flight or holds no tree of this
+ * search.  The trace step of the ply is what the end of a searched ply records (the real visit distribution, whichever move is
+ * played); on a root that was not searched, sc_selfplay_push_moves's one-hot step.  kept (may be NULL) int32 [n][3]: n_nodes, n_exp
+ * and the new root's visit count after the call (zeros where status is not 0).
+ * Returns -1 on an external handle (its plies end on the device) and on a handle with rollout_factor > 0 (that budget is chosen
+ * when the root is the leaf, which a kept root never is).  Scratch: 4 bytes per live node of the listed slots, sized from their
+ * n_nodes, allocated by the first call, grown on demand and kept on the handle. */
+int sc_selfplay_advance(sc_selfplay*, int n, const int32_t* slots, const uint16_t* moves, int32_t* status, int32_t* kept);
 int sc_selfplay_timing(sc_selfplay*, int reset, float* ms_total, float* ms_nn, int64_t* nn_launches);
 /* Kernel launches per simulation step this handle uses with SC_EVAL_NET (steps bracketed for sc_selfplay_timing always use 3):
  * 1 = the fused step kernel with value_head.ffn.0 inside (whole 64-slot blocks, every workgroup resident, and no other

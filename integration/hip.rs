@@ -168,6 +168,8 @@ extern "C" {
                           line_child: *mut i32, line_n: *mut i32, line_w: *mut f32, line_prior: *mut f32, line_len: *mut i32,
                           line_end: *mut i32, pv: *mut u16) -> c_int;
     fn sc_selfplay_report_last_timing(kernel_ms: *mut f32, total_ms: *mut f32) -> c_int;
+    // mcts::step without the reset: the move is played and the searched subtree below it stays (kept: [n][3] nodes, evaluations, visits)
+    fn sc_selfplay_advance(sp: *mut ScSelfplay, n: c_int, slots: *const i32, moves: *const u16, status: *mut i32, kept: *mut i32) -> c_int;
 }
 
 fn last_error() -> String {

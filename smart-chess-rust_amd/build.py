@@ -38,12 +38,13 @@ def _run(cmd):
 # Every unit of libsc_engine.so, once: (HIP unit, its extra flags), and the plain C++ units (the SAN tokenizer and the FEN reader: no
 # HIP in them, so that the same units also build into stand-alone programs).  tools/isa_compare.py reads the kernel units' pairs here.
 HIP_UNITS = [
-    ("mcts_kernels.hip", ["-ffp-contract=off"]), ("external_kernels.hip", ["-ffp-contract=off"]), ("encode_kernels.hip", ["-ffp-contract=off"]),
+    ("mcts_kernels.hip", ["-ffp-contract=off"]), ("external_kernels.hip", ["-ffp-contract=off"]),
+    ("advance_kernels.hip", ["-ffp-contract=off"]), ("encode_kernels.hip", ["-ffp-contract=off"]),
     ("nn_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]), ("step_kernels.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     ("score_kernels.hip", ["-ffp-contract=off"]), ("report_kernels.hip", ["-ffp-contract=off"]),
     ("batch_kernels.hip", []), ("merge_kernels.hip", []), ("perft_kernels.hip", []), ("scan_kernels.hip", []), ("san_kernels.hip", []),
     ("san_write_kernels.hip", []), ("fen_kernels.hip", []), ("trace_kernels.hip", []), ("trace_write_kernels.hip", []),
-    ("positions.hip", []), ("traces.hip", []), ("trace_write.hip", []), ("perft.hip", []), ("report.hip", []), ("engine.hip", []), ("encode_steps.hip", []),
+    ("positions.hip", []), ("traces.hip", []), ("trace_write.hip", []), ("perft.hip", []), ("report.hip", []), ("advance.hip", []), ("engine.hip", []), ("encode_steps.hip", []),
     ("device_calls.hip", []), ("selfplay.hip", []), ("match_play.hip", []), ("external_play.hip", []), ("selfplay_io.hip", []),
     ("debug_calls.hip", []),
 ]

@@ -1,5 +1,5 @@
 // host_common.hpp -- what the host units of libsc_engine.so share (engine.hip, encode_steps.hip, device_calls.hip, selfplay.hip,
-// match_play.hip, selfplay_io.hip, report.hip, debug_calls.hip): error state, the handles' structs, the described source of an encode
+// match_play.hip, selfplay_io.hip, report.hip, advance.hip, debug_calls.hip): error state, the handles' structs, the described source of an encode
 // (EncodeSrc) and one helper for each piece of plumbing.  Host only: no kernel unit includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -314,6 +314,10 @@ struct sc_selfplay {
     // event pair around the kernel, created by the first such call
     DevBuf<char> d_report;
     hipEvent_t report_ev[2] = {nullptr, nullptr};
+    // sc_selfplay_advance (advance.hip): the call's arrays (slots, moves, status, kept, offsets) and the marks of k_advance, one
+    // word per LIVE node of the listed slots (never node_cap x n_slots); made by the first such call, grown on demand
+    DevBuf<char> d_adv;
+    DevBuf<uint32_t> d_adv_marks;
     // search wave + tower in one launch (step_kernels.hip).  Chosen at creation: only with at most one game per compute
     // unit and a single group -- with more games than CUs the separate search launch runs all of them at once while the
     // fused workgroups (83 KB of LDS: one per CU) would take turns, and with several interleaved groups one group's search

@@ -21,6 +21,7 @@ void exclusive_scan_u32(uint32_t n, const uint32_t* d_in, uint32_t* d_tile_sum, 
 #include "report_types.hpp"
 #include "trace_types.hpp"
 #include "trace_write_types.hpp"
+#include "advance_types.hpp"
 
 struct sc_fen_fields;   // include/sc_engine.h
 
@@ -49,6 +50,9 @@ void push_moves(const sc::SpParams& p, int n, const int32_t* d_slots, const uint
 void external_boundary(const sc::SpParams& p, int external_mode, hipStream_t s);
 void external_wait(const sc::SpParams& p, int external_mode, int32_t* d_list, int32_t* d_count, sc::Position* d_recs, int32_t* d_ep_legal,
                    int4* d_info, hipStream_t s);
+// advance_kernels.hip (compiled with -ffp-contract=off): entry i plays a.moves[i] in slot a.slots[i] and keeps the subtree below the
+// move (sc_selfplay_advance); the argument block is advance_types.hpp's.  One workgroup per entry; nothing for a.n == 0
+void advance(const sc::SpParams& p, const scad::AdvanceArgs& a, hipStream_t s);
 // encode_kernels.hip (compiled with -ffp-contract=off); the argument blocks are encode_types.hpp's
 void encode_positions(const sc::GameWalk& w, const sc::PlyRows& rows, int32_t* outcome, hipStream_t s);   // one position per "game"
 // training tensors (sc_encode_steps, sc_encode_steps_device, sc_selfplay_encode_traces): see encode_kernels.hip

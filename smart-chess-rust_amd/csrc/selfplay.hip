@@ -270,6 +270,8 @@ void sc_selfplay_destroy(sc_selfplay* sp) {
     }
     delete sp->writer;
     sp->d_report.release();
+    sp->d_adv.release();
+    sp->d_adv_marks.release();
     for (hipEvent_t ev : sp->report_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (sp->own_stream && sp->stream) (void)hipStreamDestroy(sp->stream);

@@ -104,6 +104,7 @@ ABI = {
     "sc_selfplay_external_search": (_i, [_vp]),
     "sc_selfplay_external_wait": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32, _vp]),
     "sc_selfplay_push_moves": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "sc_selfplay_advance": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "sc_selfplay_set_openings": (_i, [_vp, _i, _vp, _vp, _vp]),
     "sc_selfplay_get_opening": (_i, [_vp, _i, _vp, _i]),
     "sc_selfplay_enable_timing": (_i, [_vp, _i]),

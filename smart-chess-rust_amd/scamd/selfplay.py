@@ -83,6 +83,20 @@ class SelfPlay(_Handle):
         _count(self.L.sc_selfplay_push_moves(self.h, n, _p(slots) if n else None, _p(_moves(moves)) if n else None, _p(status)))
         return [int(x) for x in status[:n]]
 
+    def advance(self, slots, moves):
+        """sc_selfplay_advance: plays moves[i] (UCI string or uint16) in slot slots[i] and keeps the searched subtree below it: the
+        chosen root child becomes the root and the next enqueue goes on from it -> (status, kept): status per entry 0 the game goes
+        on, 1 the move ended it, -1 the move is not among the root's children (root not searched: the legal moves), -2 the slot
+        is not active or has a simulation in flight; kept int32 [n][3]: n_nodes, n_exp and the new root's visits"""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = slots.size
+        if len(moves) != n:
+            raise ValueError("one move per slot")
+        status = np.zeros(max(n, 1), np.int32)
+        kept = np.zeros((max(n, 1), 3), np.int32)
+        _count(self.L.sc_selfplay_advance(self.h, n, _p(slots) if n else None, _p(_moves(moves)) if n else None, _p(status), _p(kept)))
+        return [int(x) for x in status[:n]], kept[:n]
+
     def set_openings(self, lines):
         """sc_selfplay_set_openings: game k of a match handle starts from line opening_of_game(k, len(lines), colours); a line
         is a list of UCI strings or uint16 moves (empty: the start position), or a pair (fen, moves): the moves start from that
@@ -362,8 +376,11 @@ class Play:
     python-chess board object; the tree keeps only the current subtree (the reference also keeps the never revisited
     siblings of played moves), so `dump_search_tree()` shows the played line as a chain of single children."""
 
-    def __init__(self, engine, initial_moves=(), fen=None, evaluator="net", seed=0):
-        """fen: the position `initial_moves` start from (a FEN string; None: the start position)"""
+    def __init__(self, engine, initial_moves=(), fen=None, evaluator="net", seed=0, keep_tree=False):
+        """fen: the position `initial_moves` start from (a FEN string; None: the start position).  keep_tree: apply_move keeps the
+        searched subtree below the move (SelfPlay.advance) instead of starting from a fresh node; a move the tree refuses -- or one
+        that ends the game -- falls back to the fresh node.  The pool holds 60 000 evaluations per game then, not per search."""
+        self.keep_tree = bool(keep_tree)
         self.engine = engine
         self.moves = [m if isinstance(m, str) else move_uci(m) for m in initial_moves]
         self._seed = seed
@@ -423,9 +440,12 @@ class Play:
         return mv
 
     def apply_move(self, mov):
-        """chess_play_apply_move: play `mov` and continue from a fresh node"""
-        self.moves.append(mov if isinstance(mov, str) else move_uci(mov))
-        self._set_position()
+        """chess_play_apply_move: play `mov` and continue from a fresh node -- with keep_tree from the searched subtree below it"""
+        mov = mov if isinstance(mov, str) else move_uci(mov)
+        kept = self.keep_tree and self.sp.advance([0], [mov])[0][0] == 0
+        self.moves.append(mov)
+        if not kept:
+            self._set_position()
 
     def inspect(self):
         """chess_play_inspect -> (None, move stack newest first, q_value of the current node, [(move, N, Q), ...])"""

@@ -6,7 +6,11 @@ flags, report(multipv) -> dict(sim, lines) and close() -- and is tested without 
 library: one slot, a node pool for 60 000 simulations, built like scamd.Play.
 
 Every `go` starts from a fresh one-node tree, as the reference discards the subtree between moves (src/mcts.rs:319-323): `go nodes
-N` gives the result of sc_search for the same position, cpuct and evaluator, noise off.  The search runs in chunks of `Chunk`
+N` gives the result of sc_search for the same position, cpuct and evaluator, noise off.  With the option KeepTree the tree lives
+on instead: a `position` with the current base whose move list extends the current one is applied by advancing move by move
+(searcher.advance(move) -> (nodes, visits) kept, or None: the tree refuses the move and the position is set up afresh), answered
+with `info string kept <nodes> nodes <visits> visits`, and `go nodes N` runs N MORE simulations on what was kept.  Any other
+`position`, and `ucinewgame`, restart.  The search runs in chunks of `Chunk`
 simulations; between chunks the engine drains the reader's queue (`stop`, `quit`, `isready`), looks at the clock and, at most once
 per `InfoEvery` milliseconds and always before `bestmove`, prints one `info` line per MultiPV rank from the device's report."""
 import queue
@@ -15,7 +19,8 @@ import time
 
 MAX_NODES = 59999          # the node pool holds a search of 60 000 simulations
 START_FEN = "rnbqkbnr/pppppppp/8/8/8/8/PPPPPPPP/RNBQKBNR w KQkq - 0 1"
-OPTIONS = {"MultiPV": ("spin", 1, 1, 224), "CPuct": ("string", "2.5"), "Chunk": ("spin", 64, 1, 4096), "InfoEvery": ("spin", 500, 0, 3600000)}
+OPTIONS = {"MultiPV": ("spin", 1, 1, 224), "CPuct": ("string", "2.5"), "Chunk": ("spin", 64, 1, 4096), "InfoEvery": ("spin", 500, 0, 3600000),
+           "KeepTree": ("check", "false")}
 _MOVE = re.compile(r"[a-h][1-8][a-h][1-8][nbrq]?$")
 
 
@@ -74,7 +79,10 @@ class Protocol:
     def __init__(self, searcher, write, clock=time.monotonic, name="smart-chess MI355X", author="the smart-chess-rust_amd authors"):
         self.s, self.write, self.clock, self.name, self.author = searcher, write, clock, name, author
         self.opt = {"MultiPV": 1, "CPuct": 2.5, "Chunk": 64, "InfoEvery": 500}
+        if hasattr(searcher, "advance"):   # KeepTree is offered by a searcher that can keep its tree
+            self.opt["KeepTree"] = False
         self.fen, self.moves = None, []
+        self.live = False   # KeepTree: the searcher holds a searched tree of (self.fen, self.moves)
         self.black_to_move = False
         self.quit = False
         self.pending = []   # commands that arrived during a search, served after it
@@ -99,20 +107,29 @@ class Protocol:
                 self.write(f"id name {self.name}")
                 self.write(f"id author {self.author}")
                 for k, spec in OPTIONS.items():
+                    if k not in self.opt:
+                        continue
                     self.write(f"option name {k} type spin default {spec[1]} min {spec[2]} max {spec[3]}" if spec[0] == "spin"
+                               else f"option name {k} type check default {str(bool(self.opt[k])).lower()}" if spec[0] == "check"
                                else f"option name {k} type string default {spec[1]}")
                 self.write("uciok")
             elif cmd == "isready":
                 self.write("readyok")
             elif cmd == "ucinewgame":
                 self.s.new_game()
+                self.live = False
             elif cmd == "setoption":
                 self._setoption(rest)
             elif cmd == "position":
-                self.fen, self.moves = parse_position(rest)
+                fen, moves = parse_position(rest)
+                extends = self.live and fen == self.fen and len(moves) > len(self.moves) and moves[:len(self.moves)] == self.moves
+                done = self.moves
+                self.fen, self.moves = fen, moves
                 base_black = self.fen is not None and self.fen.split()[1] == "b"
                 self.black_to_move = base_black != bool(len(self.moves) & 1)
-                self.s.set_position(self.fen, self.moves)
+                self.live = extends and self._advance(moves[len(done):])
+                if not self.live:
+                    self.s.set_position(self.fen, self.moves)
             elif cmd == "go":
                 self._go(parse_go(rest), q if q is not None else queue.Queue())
             elif cmd == "quit":
@@ -121,12 +138,22 @@ class Protocol:
         except ValueError as e:
             self.write(f"info string {e}")
 
+    def _advance(self, moves):
+        """KeepTree: the searcher's tree follows `moves`, move by move -> False as soon as it refuses one"""
+        kept = None
+        for m in moves:
+            kept = self.s.advance(m)
+            if kept is None:
+                return False
+        self.write(f"info string kept {kept[0]} nodes {kept[1]} visits")
+        return True
+
     def _setoption(self, words):
         if "name" not in words or "value" not in words:
             raise ValueError("setoption name <id> value <x> expected")
         name = " ".join(words[words.index("name") + 1:words.index("value")])
         value = " ".join(words[words.index("value") + 1:])
-        key = {k.lower(): k for k in OPTIONS}.get(name.lower())
+        key = {k.lower(): k for k in self.opt}.get(name.lower())
         if key is None:
             raise ValueError(f"setoption: no option '{name}'")
         spec = OPTIONS[key]
@@ -134,6 +161,11 @@ class Protocol:
             v = int(value)
             if not spec[2] <= v <= spec[3]:
                 raise ValueError(f"setoption: {key} must lie in {spec[2]} .. {spec[3]}")
+        elif spec[0] == "check":
+            if value.lower() not in ("true", "false"):
+                raise ValueError(f"setoption: {key} must be true or false")
+            v = value.lower() == "true"
+            self.live = False
         else:
             v = float(value)
             if not v > 0:
@@ -178,7 +210,11 @@ class Protocol:
         nodes, ms, infinite = self._limits(go)
         t0 = self.clock()
         elapsed = lambda: (self.clock() - t0) * 1000.0   # noqa: E731
-        self.s.start(self.opt["CPuct"])
+        if self.opt.get("KeepTree"):
+            self.s.start(self.opt["CPuct"], self.live)   # (a live tree is searched on)
+            self.live = True
+        else:
+            self.s.start(self.opt["CPuct"])
         last, last_info, stopped = None, None, False
         done = 0
         while done < nodes and not stopped:
@@ -220,6 +256,7 @@ class LibSearcher:
         self.engine, self.evaluator, self.salt, self.seed = engine, evaluator, salt, seed
         self.device = engine.device if engine is not None else device
         self.sp, self.base, self.moves, self.dirty, self.over = None, None, [], False, False
+        self.used = 1   # an upper bound of the handle's position records in use (n_exp): kept ones and the simulations since
         self._open()
 
     def _open(self):
@@ -249,7 +286,20 @@ class LibSearcher:
             self.base.close()
         self.base, self.moves = base, list(moves)
 
-    def start(self, cpuct):
+    def advance(self, move):
+        """plays `move` on the live tree (SelfPlay.advance) -> (nodes, visits) kept, or None: the tree refuses the move, the move
+        ends the game or the handle is flagged, and the caller sets the position up afresh"""
+        if self.over or self.dirty:
+            return None
+        st, kept = self.sp.advance([0], [move])
+        if st[0] != 0:
+            return None
+        self.moves.append(move)
+        self.used = int(kept[0][1])
+        return int(kept[0][0]), int(kept[0][2])
+
+    def start(self, cpuct, live=False):
+        """live: the handle's tree is the current position's (a search ran there, or advance led there) and is searched on"""
         from .binding import _check
         # a base where the game is over (mate, stalemate) cannot be searched: there is no move to report
         self.over = self.base is not None and int(self.base.status[0]) == 1 and not self.moves
@@ -257,13 +307,21 @@ class LibSearcher:
             return
         if self.dirty:
             self._open()   # the error flags of a handle stay: a flagged search leaves a new one behind
+            live = False
         # the whole move list goes to the handle (chess_play_new's way): the search sees the game's repetitions
-        self.sp.set_position(0, self.moves, fen=None if self.base is None else (self.base, 0))
+        if not live:
+            self.sp.set_position(0, self.moves, fen=None if self.base is None else (self.base, 0))
+            self.used = 1
         _check(self.sp.L.sc_selfplay_set_search(self.sp.h, cpuct, 0.15, 0))
 
     def run(self, n):
         if self.over:
             return 0
+        # the pool holds MAX_NODES + 1 position records: per search, and per game where trees are kept
+        n = min(n, MAX_NODES + 1 - self.used)
+        if n <= 0:
+            return 0
+        self.used += n
         self.sp.enqueue(n)
         self.sp.sync()
         flags = self.sp.stats()["error_flags"]

@@ -2,10 +2,12 @@
 
   python tools/uci_engine.py -w net.scw [--fp8] [--evaluator net|synth|synth_coarse|synth_uniform] [--salt S] [--device N]
                              [--blocks B --channels C --net-seed S]     (a random network when no weights are given)
+                             [--keep-tree]                              (the option KeepTree starts as true)
 
 Options over the protocol: MultiPV, CPuct, Chunk (simulations between two looks at the input and the clock), InfoEvery (ms).
-Every `go` searches from a fresh tree; `go nodes N` is one sc_search of N simulations (scamd/uci.py).  The synthetic evaluators
-need no network: they exist for tests.
+Every `go` searches from a fresh tree; `go nodes N` is one sc_search of N simulations (scamd/uci.py).  With KeepTree (a check
+option; --keep-tree sets it from the start) a `position` that extends the current game keeps the searched subtree below the moves
+played, and `go nodes N` runs N more simulations on it.  The synthetic evaluators need no network: they exist for tests.
 
 The reader thread is started FIRST and the GPU is opened after it: no HIP call precedes the thread's start, and the program starts
 no child process."""
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--channels", type=int, default=256)
     ap.add_argument("--net-seed", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--keep-tree", action="store_true", help="start with the option KeepTree set")
     a = ap.parse_args()
 
     q = queue.Queue()
@@ -56,7 +59,9 @@ def main():
     if a.evaluator == "net":
         eng = scamd.Engine(a.blocks, a.channels, seed=a.net_seed, weights=a.weights, precision="fp8" if a.fp8 else "bf16", device=a.device)
     searcher = uci.LibSearcher(eng, evaluator=a.evaluator, salt=a.salt, seed=a.seed, device=a.device)
-    rc = uci.Protocol(searcher, write).run(q)
+    proto = uci.Protocol(searcher, write)
+    proto.opt["KeepTree"] = a.keep_tree
+    rc = proto.run(q)
     if eng is not None:
         eng.close()
     return rc
