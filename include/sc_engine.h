@@ -74,7 +74,13 @@ typedef struct {
                               matrix cores -- OCP e4m3 operands, per-output-channel power-of-two weight scales, fp32
                               accumulate; LayerNorm / residual stream / softmax fp32 and the SE + value FC layers bf16 as
                               before.  Stated tolerance vs the fp32 reference vectors: prior total
-                              variation < 0.05, |value| error < 0.05. */
+                              variation < 0.05, |value| error < 0.05 -- on init-scale outputs, where it is met.  On the
+                              reference's vectors at a trained net's output range (policy gain x 4) the forward test measures
+                              a prior total variation of 0.145 and asserts 0.25 (tests/test_gpu_parity2.py).  In the search
+                              (sharp 6 x 128 networks, 48 positions, rollout 96, against the fp32 network's root visit
+                              shares; tests/test_gpu_sharp_search.py): mean total variation 0.067
+                              (gain x 4, value layer x 2) and 0.101 (gain x 8), the fp32 network's most visited move among
+                              the engine's on 44 and 41 of 48; bf16: 0.005 and 0.006, 48 of 48. */
     int32_t reserved;
 } sc_net_config;
 

@@ -13,6 +13,15 @@ WIDE137 = ("h2h4 g8h6 a2a4 h6g4 f2f4 g4h6 a4a5 h6g4 d2d4 g4f2 e1f2 b8a6 h4h5 a6b
            "e4e5 a4a3 e5e6 a3a2 e6e7 a2b1q a1a6 b1f5 d5d6 f5f7 d6d7 f7d5 a6g6 h7g6 e7f8q g8h7 "
            "d8e7 d5f7 d7d8q h8g8 e8f7 h7h8 h6h7 g8f8 b4b5 f8g8 b5b6 g8e8 b6b7 e8g8 b7b8q g8e8 "
            "h1h2 e8g8 c4c2 g8e8 e7e4 e8g8 a8a3 g8e8 f7e8 h8g7 f2g3 f3f2 e8e5 g7f7 h7h8q f2g1b").split()
+# five roots for the tests that put the network inside the search, and the slots of a 64-slot handle they are set in
+LINES = [
+    [],                                                        # start position: history planes empty
+    ["e2e4", "c7c5", "g1f3"],                                  # Black to move: rotated view, short history
+    ["f2f3", "e7e5", "g2g4"],                                  # mate in one among the children: terminal leaves
+    WIDE,                                                      # 82 legal moves (two rounds of lanes), full 8-board history
+    ["g1f3", "g8f6", "f3g1", "f6g8", "g1f3", "g8f6", "f3g1"],  # repetition planes set, Black to move
+]
+SLOTS = [0, 17, 31, 40, 63]
 MATED = ["f2f3", "e7e5", "g2g4", "d8h4"]   # White is checkmated: a game set to this line ends after its first search
 
 # public perft known answers: FEN -> node counts at depth 1, 2, ...

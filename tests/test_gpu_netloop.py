@@ -17,19 +17,10 @@ import numpy as np
 import pytest
 
 from helpers import GpuPredictEvaluator, _assert_same, random_games
-from lines import WIDE
+from lines import LINES, SLOTS
 from support import scamd_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-LINES = [
-    [],                                                        # start position: history planes empty
-    ["e2e4", "c7c5", "g1f3"],                                  # Black to move: rotated view, short history
-    ["f2f3", "e7e5", "g2g4"],                                  # mate in one among the children: terminal leaves
-    WIDE,                                                      # 82 legal moves (two rounds of lanes), full 8-board history
-    ["g1f3", "g8f6", "f3g1", "f6g8", "g1f3", "g8f6", "f3g1"],  # repetition planes set, Black to move
-]
-SLOTS = [0, 17, 31, 40, 63]
 
 
 CASES = [(10, 128, "bf16"), (10, 256, "bf16"), (10, 128, "fp8"), (3, 256, "fp8")]
