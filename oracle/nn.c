@@ -260,7 +260,11 @@ static void conv(const float* in, int Cin, const float* w, const float* bias, in
         }
     }
 }
+/* orc_net_ln_ratios: where the statistics of the LayerNorm inputs go, and the index of the next LayerNorm */
+static _Thread_local double* ln_ratios = NULL;
+static _Thread_local int ln_index = 0;
 static void layernorm(float* x, int C, const float* g, const float* b, int relu) {
+    int site = ln_ratios ? ln_index++ : 0;
     for (int p = 0; p < 64; p++) {
         float* v = x + (size_t)p * C;
         double m = 0;
@@ -269,6 +273,7 @@ static void layernorm(float* x, int C, const float* g, const float* b, int relu)
         double var = 0;
         for (int c = 0; c < C; c++) var += (v[c] - m) * (v[c] - m);
         var /= C;
+        if (ln_ratios && fabs(m) / sqrt(var + 1e-6) > ln_ratios[site]) ln_ratios[site] = fabs(m) / sqrt(var + 1e-6);
         float rstd = (float)(1.0 / sqrt(var + 1e-6));
         for (int c = 0; c < C; c++) {
             float y = (float)(v[c] - m) * rstd * g[c] + b[c];
@@ -375,4 +380,14 @@ void orc_net_forward(const orc_net* n, const int8_t* boards, const int32_t* meta
     free(a);
     free(t1);
     free(t2);
+}
+void orc_net_ln_ratios(const orc_net* n, const int8_t* boards, const int32_t* meta, double* ratios) {
+    float* logp = (float*)malloc(sizeof(float) * 4672);
+    float value;
+    for (int i = 0; i < 2 * n->n_blocks + 4; i++) ratios[i] = 0;
+    ln_ratios = ratios;
+    ln_index = 0;
+    orc_net_forward(n, boards, meta, logp, &value, NULL);
+    ln_ratios = NULL;
+    free(logp);
 }

@@ -105,6 +105,7 @@ def lib():
         "orc_net_set_tensor": (i32, [vp, i32, vp, C.c_int64]),
         "orc_net_get_tensor": (i32, [vp, i32, vp, C.c_int64]),
         "orc_net_forward": (None, [vp, vp, vp, vp, vp, vp]),
+        "orc_net_ln_ratios": (None, [vp, vp, vp, vp]),
         "orc_mix64": (u64, [u64]),
         "orc_pos_hash": (u64, [vp]),
         "orc_rng": (u64, [u64, u64, u64, u64, u64]),
@@ -294,6 +295,15 @@ class Net:
         lat = np.zeros((64, self.channels), np.float32) if latent else None
         self.L.orc_net_forward(self.h, _ptr(boards), _ptr(meta), _ptr(logp), _ptr(v), _ptr(lat) if latent else None)
         return (logp, float(v[0]), lat) if latent else (logp, float(v[0]))
+
+    def ln_ratios(self, boards, meta):
+        """the largest |mean| / sqrt(var + 1e-6) over the 64 pixels of every LayerNorm's input, in float64: [2 n_blocks + 4] in the
+        order stem, (LN1, LN2) of each block, policy LN1, the 73-wide policy LayerNorm, value LayerNorm"""
+        boards = np.ascontiguousarray(boards, np.int8)
+        meta = np.ascontiguousarray(meta, np.int32)
+        out = np.zeros(2 * self.n_blocks + 4, np.float64)
+        self.L.orc_net_ln_ratios(self.h, _ptr(boards), _ptr(meta), _ptr(out))
+        return out
 
 
 def eval_fn(name):

@@ -29,6 +29,10 @@ int orc_net_get_tensor(const orc_net*, int t, float* out, int64_t numel);
  * dbg_latent (optional): trunk output [64][C]. */
 void orc_net_forward(const orc_net*, const int8_t* boards, const int32_t* meta, float* logp, float* value,
                      float* dbg_latent);
+/* the float64 statistics of every LayerNorm's input in one forward pass (tests/ln_offset_ref.py: R_REQ): ratios[2 n_blocks + 4] =
+ * the largest |mean| / sqrt(var + 1e-6) over the 64 pixels, in the order stem, (LN1, LN2) of each block, policy LN1, the 73-wide
+ * policy LayerNorm, value LayerNorm */
+void orc_net_ln_ratios(const orc_net*, const int8_t* boards, const int32_t* meta, double* ratios);
 
 #ifdef __cplusplus
 }

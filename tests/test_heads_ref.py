@@ -180,3 +180,31 @@ def test_oracle_meets_the_rounding_forms_of_the_heads(orc, site, C, prec):
 def test_wrong_rounding_rules_are_caught_in_the_heads(orc, site, prec):
     """truncation, ties away from zero and, in e4m3, flushed subnormals, a clamp at 240 and no clamp: rounding_ref.check_wrong_rules"""
     rr.check_wrong_rules(orc, site, 128, prec)
+
+
+# ---------------------------------------------------------------------------------- LayerNorm rows with a large common offset
+import ln_offset_ref as lo  # noqa: E402
+
+HEAD_LN = ("p73", "vln", "pln1")
+
+
+@pytest.mark.parametrize("C", [128, 256])
+@pytest.mark.parametrize("mode", list(lo.MODES))
+def test_oracle_is_the_two_pass_layernorm_at_every_offset_in_the_heads(orc, mode, C):
+    """ln_offset_ref.check_oracle at the 73-wide policy LayerNorm (padded channels add nothing, 1 / 73 is rounded), the value
+    head's LayerNorm and the policy head's first: assertion 1 and assertion 2 on EVERY rung, in the oracle's three modes"""
+    lo.check_oracle(orc, C, mode, HEAD_LN)
+
+
+@pytest.mark.parametrize("C,prec", INST, ids=IDS)
+def test_offset_probes_of_the_heads_meet_their_conditions(C, prec):
+    """rows exact in float32, no ReLU cut behind a lift, at most `cap` elements on a tie up to R_REQ, a wrong operand shows"""
+    lo.check_conditions(C, prec, HEAD_LN)
+
+
+@pytest.mark.parametrize("C,prec", INST, ids=IDS)
+def test_a_one_pass_layernorm_is_caught_in_the_heads(C, prec):
+    """ln_offset_ref.one_pass32 in place of the LayerNorm, every other layer exact: within the one-pass bound on every rung, the
+    operation up to a break rung above R_REQ, not the operation from there on"""
+    for site in HEAD_LN:
+        assert lo.check_wrong_ln(C, prec, site) in lo.RUNGS[2:]

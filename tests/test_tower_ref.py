@@ -278,3 +278,46 @@ def test_oracle_meets_the_rounding_forms_of_the_trunk(orc, site, C, prec):
 def test_wrong_rounding_rules_are_caught_in_the_trunk(orc, site, prec):
     """truncation, ties away from zero and, in e4m3, flushed subnormals, a clamp at 240 and no clamp: rounding_ref.check_wrong_rules"""
     rr.check_wrong_rules(orc, site, 128, prec)
+
+
+# ---------------------------------------------------------------------------------- LayerNorm rows with a large common offset
+import ln_offset_ref as lo  # noqa: E402
+from support import GOLD  # noqa: E402
+
+TRUNK_LN = ("stem", "ln1", "ln2")
+
+
+@pytest.mark.parametrize("C", [128, 256])
+@pytest.mark.parametrize("mode", list(lo.MODES))
+def test_oracle_is_the_two_pass_layernorm_at_every_offset_in_the_trunk(orc, mode, C):
+    """ln_offset_ref.check_oracle at the stem LayerNorm, LN1 and LN2: the oracle, two-pass in double, meets assertion 1 and
+    assertion 2 on EVERY rung, in its fp32 mode and in both emulating modes"""
+    lo.check_oracle(orc, C, mode, TRUNK_LN)
+
+
+@pytest.mark.parametrize("C,prec", INST, ids=IDS)
+def test_offset_probes_of_the_trunk_meet_their_conditions(C, prec):
+    """rows exact in float32, no ReLU cut behind a lift, at most `cap` elements on a tie up to R_REQ, a wrong operand shows"""
+    assert [r[0] for r in lo.rows()].count(64) == 8 and len(lo.rows()) == 25 and {r[1] for r in lo.rows()} == {1, -1}
+    lo.check_conditions(C, prec, TRUNK_LN)
+
+
+@pytest.mark.parametrize("C,prec", INST, ids=IDS)
+def test_a_one_pass_layernorm_is_caught_in_the_trunk(C, prec):
+    """ln_offset_ref.one_pass32 in place of the LayerNorm, every other layer exact: within the one-pass bound on every rung, the
+    operation up to a break rung above R_REQ, not the operation from there on"""
+    for site in TRUNK_LN:
+        assert lo.check_wrong_ln(C, prec, site) in lo.RUNGS[2:]
+
+
+def test_mean_over_sigma_of_the_projects_networks(orc):
+    """R_REQ: the table of ln_offset_ref.RATIOS measured again with the oracle's float64 statistics, its
+    largest entry, and the rung that follows from it"""
+    got = lo.measure_ratios(orc, GOLD)
+    assert set(got) == set(lo.RATIOS) == {n[0] for n in lo.NETWORKS}
+    for name, want in lo.RATIOS.items():
+        print(f"mean / sigma, {name}: " + ", ".join(f"{s} {got[name][s]:.3f}" for s in lo.LN_SITES))
+        assert np.allclose([got[name][s] for s in lo.LN_SITES], want, rtol=0, atol=6e-4), name
+    top = max(max(v) for v in lo.RATIOS.values())
+    assert top == lo.LARGEST_RATIO and lo.required_rung(top) == lo.R_REQ
+    assert all(env is None or env > lo.R_REQ for env in lo.ENVELOPE.values()) and len(lo.ENVELOPE) == 24

@@ -40,7 +40,14 @@ on the tests' sets; tests/test_tower_ref.py asserts at most 25 % and that every 
 
 BOUNDS, first order in U = 2^-24, computed from the data, one term per rounding (the constants below cite their lines).  The one-pass
 variance carries its cancellation term (roundings of Q/C and mean^2 against their difference) through rstd; `__expf` is
-tail_ref.exp_rel, `rcp` one 2^-23 term."""
+tail_ref.exp_rel, `rcp` one 2^-23 term.
+
+TWO YARDSTICKS IN `ln`.  Its VALUE is the float64 two-pass LayerNorm, the operation of the reference (F.layer_norm) and of the oracle;
+its BOUND models the engine's one-pass fp32 formula, so it grows with (mean / sigma)^2 as that formula's error does and never fails
+on a large common offset by itself.  Every form of this module, of heads_ref and of rounding_ref keeps mean / sigma below a few, where
+the two coincide.  tests/ln_offset_ref.py takes them apart on rows with mean / sigma up to 32768: its assertion 1 (finite, no worse
+than the one-pass formula) uses the bound, its assertion 2 (the operation itself, up to the required ratio R_REQ) uses the value with
+a tolerance taken from the operand formats, not from this model."""
 import numpy as np
 
 import scw
