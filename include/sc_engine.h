@@ -87,7 +87,10 @@ typedef struct {
 /* Replaces backend construction in src/main.rs:83-128 (ChessTS / ChessEP / ChessOnnx).
  * weights_path: NULL, or a blob written by tools/scw.py / tools/ckpt_to_scw.py from a reference state_dict: SCW1 (fp32
  * tensors; quantised at load as cfg->precision asks) or SCW2 (the fp8 export: e4m3 conv weights + their channel scales;
- * the blob's precision wins). */
+ * the blob's precision wins).  An SCW2 channel may carry any exponent in [-100, 100]; it is kept as it is (E8M0 scale byte
+ * 127 + e).  Contract: any lossless split of a channel -- every way to write its weights as e4m3 * 2^e -- gives the same
+ * network: the same real weights, the same bits wherever the partial sums of a conv leave the fp32 accumulator bits to spare,
+ * and elsewhere results that differ by the accumulator's last bits only (tests/test_gpu_fp8_splits.py). */
 int sc_engine_create(const sc_net_config* cfg, const char* weights_path, int device_id, sc_engine** out);
 void sc_engine_destroy(sc_engine*);
 int sc_engine_max_batch(const sc_engine*);

@@ -21,6 +21,8 @@ u32 ndim, u32 shape[4], u64 numel, u32 encoding and
                 convs, the three head convs); everything else stays float32.
 Quantisation rules (identical in smart-chess-rust_amd/csrc/weights.hpp and oracle/nn.c): OCP e4m3, round to nearest even,
 subnormals kept, |x| > 448 clamps; channel exponent = the smallest e with max|w| / 2^e <= 448.
+A blob may carry any other exponent in [-100, 100] under which the channel's weights are e4m3 without loss (write_scw's `exps`): every
+such split stands for the same real weights and the loader keeps it as it is (tests/fp8_split_ref.py).
 """
 import struct
 
@@ -104,12 +106,21 @@ def channel_exps(w):
     return np.clip(np.where(m > 0, e, 0), -100, 100).astype(np.int8)
 
 
-def quantize_fp8(w):
-    """conv weight -> (exponents int8[O], e4m3 bytes uint8[w.shape], dequantised float32)"""
+def quantize_fp8(w, e=None):
+    """conv weight -> (exponents int8[O], e4m3 bytes uint8[w.shape], dequantised float32).  e: the exponent of every output channel,
+    int[O], in place of the rule of channel_exps; such a split must be lossless (asserted): w / 2^e is an e4m3 value, so that every
+    split of a tensor stands for the same real weights"""
     w = np.asarray(w, np.float32)
-    e = channel_exps(w)
+    given = e is not None
+    assert not given or (np.abs(np.asarray(e, np.int64)) <= 100).all(), "a channel exponent outside [-100, 100]"
+    e = np.asarray(e, np.int8) if given else channel_exps(w)
+    assert e.shape == (w.shape[0],), (e.shape, w.shape)
     sh = (-1,) + (1,) * (w.ndim - 1)
-    r = e4m3_round(np.ldexp(w, -e.astype(np.int32).reshape(sh)))
+    with np.errstate(over="ignore"):
+        x = np.ldexp(w, -e.astype(np.int32).reshape(sh))
+    r = e4m3_round(x)
+    if given:
+        assert np.array_equal(r, x) and (np.abs(x) <= 448).all(), "the given channel exponents do not split the weights losslessly"
     return e, e4m3_encode(r), np.ldexp(r, e.astype(np.int32).reshape(sh)).astype(np.float32)
 
 
@@ -130,11 +141,15 @@ def prng_state_dict(n_blocks, C=256, seed=0):
             for i, (name, shape, kind, fan) in enumerate(tensor_table(n_blocks, C))}
 
 
-def write_scw(path, state_dict, n_blocks, C=256, fp8=False):
+def write_scw(path, state_dict, n_blocks, C=256, fp8=False, exps=None):
     """state_dict: name -> array (names as in the reference; a leading 'model.' is stripped,
-    as reference py/module.py:168-175 does for Lightning checkpoints).  fp8: write the SCW2 fp8 export."""
+    as reference py/module.py:168-175 does for Lightning checkpoints).  fp8: write the SCW2 fp8 export.
+    exps (fp8 only): name of an e4m3 conv tensor -> int[O], its channel exponents in place of the rule of channel_exps; the split
+    must be lossless (quantize_fp8 asserts it).  Tensors that are not named keep the rule."""
     sd = {(k[6:] if k.startswith("model.") else k): np.asarray(v, np.float32) for k, v in state_dict.items()}
     table = tensor_table(n_blocks, C)
+    exps = exps or {}
+    assert (fp8 or not exps) and all(is_fp8_conv(k) and k in sd for k in exps), "exps name e4m3 conv tensors of an fp8 export"
     with open(path, "wb") as f:
         if fp8:
             f.write(b"SCW2" + struct.pack("<IIII", n_blocks, C, len(table), 1))
@@ -146,7 +161,7 @@ def write_scw(path, state_dict, n_blocks, C=256, fp8=False):
             sh = list(shape) + [1] * (4 - len(shape))
             f.write(struct.pack("<I4IQ", len(shape), *sh, a.size))
             if fp8 and is_fp8_conv(name):
-                e, q, _ = quantize_fp8(a)
+                e, q, _ = quantize_fp8(a, exps.get(name))
                 f.write(struct.pack("<I", 1) + e.tobytes() + q.tobytes())
             else:
                 if fp8:
